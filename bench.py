@@ -16,6 +16,12 @@ prints the MAX over ranks; the only collective besides the barriers is the all-r
 region behind the last step (weak scaling: per-GPU batch fixed).  The reference fans out the same way, one env per std::thread
 (unit_test/bboard/performance_test.cpp:40-50,71-94).
 
+A plain run does what the headline needs and no more: set up (boards, burn-in), warm up, time --steps steps, write the outputs
+(--dump-outputs DIR), print the line.  `ms_per_step` is the timed region over --steps.  --full adds everything else this script
+measures, after the headline and outside its region: the steps timed again with HIP events (`roofline.step_ms_hip_events`), the
+per-launch timings (`roofline.launch.ms`, `launches_in_flight`), config 3, `other_configs`, `cpu_baseline` and, with several ranks,
+`config.single_gpu_base`.
+
 The JSON line carries
   roofline     — `achieved` / `frac`: the bytes the kernel REALLY moves per step (`traffic`: rocprofv3 PMC FETCH_SIZE x 2 +
                  WRITE_SIZE of this workload — the figure committed under profiles/, or measured by this very run with
@@ -328,6 +334,42 @@ def with_bytes(entry: dict, key: str, envs: int, ms_per_step: float) -> dict:
     return entry
 
 
+DUMP_SAMPLE_ENVS = 16384  # float64: 255 State values = 2,040 B per env (+ 512 B of policy memory with --policy simple): <= 42 MB
+DUMP_SAMPLE_SEED = 0x5EED  # the sample's own seed: the same envs for every run over the same batch, whatever --seed
+
+
+def _state_columns(arr, prefix: str = "state"):
+    """(name, array) for every leaf field of a STATE_DTYPE array; the agents' padding bytes are not part of the State's value"""
+    for name in arr.dtype.names:
+        if name == "pad":
+            continue
+        col = arr[name]
+        if col.dtype.names:
+            yield from _state_columns(col, f"{prefix}_{name}")
+        else:
+            yield f"{prefix}_{name}", col
+
+
+def dump_outputs(out_dir: str, env, counters: np.ndarray, with_policy_memory: bool) -> int:
+    """--dump-outputs: what a caller of the timed path holds after its last step — the States of a fixed sample of the envs (one
+    file per field), their episode counts, with --policy simple the agents' policy memory, and the step / episode counters —
+    as float64 .npy files under out_dir (float64 holds every value exactly: board items reach 2^24 + 3, beyond float32).
+    Returns the bytes written."""
+    n = env.n
+    idx = np.arange(n) if n <= DUMP_SAMPLE_ENVS else np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, DUMP_SAMPLE_ENVS, replace=False))
+    arrays = {"env_index": idx, "counters": counters, "episodes": env.episodes()[idx]}
+    arrays.update(_state_columns(env.get_state()[idx]))
+    if with_policy_memory:
+        arrays["policy_memory"] = env.policy_memory()[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    return total
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -360,6 +402,13 @@ def parse_args(argv=None):
     ap.add_argument("--traffic-probe", action="store_true", help=argparse.SUPPRESS)  # the child of measure_traffic(): steps only, no JSON extras
     ap.add_argument("--envs-per-wave", type=int, default=0)
     ap.add_argument("--lanes-per-env", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: the same steps timed again with HIP events, per-launch timings, "
+                         "BASELINE's other configs, the other sizes and call shapes, the CPU baseline, a multi-rank line's single-GPU "
+                         "base (default: the headline only — set up, warm up, time --steps steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float64): the State fields and "
+                         "episode counts of a fixed, seeded sample of rank 0's envs, and the step counters")
     args = ap.parse_args(argv)
     if args.envs <= 0:
         world = int(os.environ.get("WORLD_SIZE", "0")) or args.gpus
@@ -535,31 +584,36 @@ def worker(args) -> None:
         reduce_counters(counters, dist)
         total_steps = int(counters[CNT_STEPS].item())
     episodes_finished = int(counters[1].item())
-    # the same number of steps again between two HIP events on the launch stream (untimed: the events and the join they need
-    # would add their own latency to the region above): GPU-side time per step, all launches of a step
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    ev0.record(stream)
-    run_steps(args.steps)
-    env.flush()  # steps run as sub-batches on internal streams: order them before the event on this stream
-    ev1.record(stream)
-    torch.cuda.synchronize()
-    step_ms = ev0.elapsed_time(ev1) / args.steps
-    step_ms = reduce_max(step_ms, device, dist)
-    # a step is issued as `parts` launches of pom_step_kernel over contiguous sub-batches on parallel streams; time the
-    # individual launches too (HIP events attached to each dispatch), outside the timed region
+    dumped_bytes = None
+    if args.dump_outputs and rank == 0:  # before anything below steps the batch again (rank 0's shard; the counters are global)
+        dumped_bytes = dump_outputs(args.dump_outputs, env, counters.cpu().numpy(), args.policy == "simple")
     epw, lpe, parts = env.launch_shape()
     issue, issue_streams = env.issue_info()
-    env.profile(True)
-    run_steps(max(1, 256 // parts))
-    launch_ms, n_launch = env.profile_read()
-    env.profile(False)
+    step_ms, launch_ms, n_launch = None, 0.0, 0
+    if args.full:
+        # the same number of steps again between two HIP events on the launch stream (untimed: the events and the join they need
+        # would add their own latency to the region above): GPU-side time per step, all launches of a step
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        ev0.record(stream)
+        run_steps(args.steps)
+        env.flush()  # steps run as sub-batches on internal streams: order them before the event on this stream
+        ev1.record(stream)
+        torch.cuda.synchronize()
+        step_ms = ev0.elapsed_time(ev1) / args.steps
+        step_ms = reduce_max(step_ms, device, dist)
+        # a step is issued as `parts` launches of pom_step_kernel over contiguous sub-batches on parallel streams; time the
+        # individual launches too (HIP events attached to each dispatch), outside the timed region
+        env.profile(True)
+        run_steps(max(1, 256 // parts))
+        launch_ms, n_launch = env.profile_read()
+        env.profile(False)
 
     # BASELINE config 3 beside the headline (rank 0 of a single-GPU run, untimed region): the same boards played from the start
     # by the device SimpleAgent policy, act x4 + Step per env-step as Environment::Step does.  200 untimed ticks first: games
     # last ~190 ticks under this policy, so the batch is then a steady mix of openings, mid-games and restarts.
     config3 = None
-    if not multi and args.policy == "random" and tpl == 1 and not args.no_config3:
+    if args.full and not multi and args.policy == "random" and tpl == 1 and not args.no_config3:
         env.make_game(start)
         env.set_tick(0)
         env.step_simple(args.seed, 200)
@@ -581,7 +635,7 @@ def worker(args) -> None:
     # with the caller's stream, so no pipelining across ticks).
     other = None
     default_run = (args.envs == 65536 and args.kind == "ffa" and args.dist == "random" and not args.fresh_boards)
-    if not multi and args.policy == "random" and tpl == 1 and not args.no_config3 and default_run:
+    if args.full and not multi and args.policy == "random" and tpl == 1 and not args.no_config3 and default_run:
         other = {}
         for name, n_o, kind_o, dist_o in (("config2_4096_envs_random", 4096, "ffa", 1), ("config5_65536_envs_stress", 65536, "stress", 2)):
             e2 = BatchEnvironment(n_o, device=local_rank, mode=MODE_ENV, auto_reset=True, max_steps=args.max_steps,
@@ -838,7 +892,7 @@ def worker(args) -> None:
                     "peak proper; bytes = this size's own PMC passes"}, "big", n_big, ms_big)
     # like-for-like base of an N > 1 line: this rank's shard stepped while the other ranks' GPUs idle (same envs per GPU, same kernels)
     single_base = None
-    if multi:
+    if multi and args.full:
         barrier()
         if rank == 0:
             evA, evB = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -926,6 +980,8 @@ def worker(args) -> None:
                                     5 if (args.kind == "stress" and args.envs == 65536 and world == 1) else
                                     2 if (args.envs == 4096 and world == 1 and args.policy == "random" and args.kind == "ffa") else None),
                 "single_gpu_base": single_base,
+                # --full: the measurements beside the headline ran too (step_ms_hip_events, launch timings, other_configs, cpu_baseline, ...)
+                "full": args.full, "dumped_output_bytes": dumped_bytes,
             },
             "roofline": {
                 "bound": "hbm", "unit": "GB/s", "peak": HBM_PEAK_GBPS,
@@ -973,7 +1029,7 @@ def worker(args) -> None:
             line["config3_simple_agent"] = config3
         if other:
             line["other_configs"] = other
-        if not multi and not args.no_cpu_baseline:
+        if args.full and not multi and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(start, args.seed, dist_id, args.max_steps)
         print(json.dumps(line), flush=True)
     env.close()

@@ -5,10 +5,10 @@ TAG=$1
 OUT=${GRAFT_REPO_ROOT:-/root/repo}/gpurun_out/bench_$TAG
 mkdir -p $OUT
 cd ${GRAFT_REPO_ROOT:-/root/repo}
-Q="--no-cpu-baseline --no-config3 --no-traffic"
+Q="--full --no-cpu-baseline --no-config3 --no-traffic"
 if [ "${2:-all}" = all ]; then
-python3 bench.py 2>/dev/null | tail -1 > $OUT/bench.json && echo default done
-for i in 1 2 3 4 5; do python3 bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1; done > $OUT/bench_driver_shape.jsonl && echo driver-shape done
+python3 bench.py --full 2>/dev/null | tail -1 > $OUT/bench.json && echo default done
+for i in 1 2 3 4 5; do python3 bench.py --gpus 1 --steps 20 --warmup 5 --full 2>/dev/null | tail -1; done > $OUT/bench_driver_shape.jsonl && echo driver-shape done
 fi
 python3 bench.py --envs 262144 --steps 200 --warmup 20 $Q 2>/dev/null | tail -1 > $OUT/bench_262144_envs.json
 python3 bench.py --envs 32768 --steps 300 --warmup 20 $Q 2>/dev/null | tail -1 > $OUT/bench_32768_envs.json

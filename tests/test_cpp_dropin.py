@@ -149,7 +149,11 @@ def test_reference_simple_agents_play_through_bboard_environment(hip_lib, oracle
     if not os.path.exists(exe):
         pytest.skip("oracle/_ref/env_game_ref is built only where /root/reference exists")
     trace = tmp_path / "trace_ref.bin"
-    out = subprocess.run([exe, str(trace), "6", "300"], capture_output=True, text=True, timeout=300)
+    # the binary is built in one tree and may be run from another (or reached through a link, where $ORIGIN names the link's
+    # target): point the loader at THIS tree's library, the one hip_lib built and loaded
+    lib_dir = os.path.join(ROOT, "pomcpp_amd")
+    env = dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join(p for p in (lib_dir, os.environ.get("LD_LIBRARY_PATH")) if p))
+    out = subprocess.run([exe, str(trace), "6", "300"], capture_output=True, text=True, timeout=300, env=env)
     assert out.returncode == 0 and "env games ok" in out.stdout, f"rc={out.returncode}\n{out.stdout}\n{out.stderr}"
     games, steps, _ = _replay(trace, oracle)
     assert games == 6 and steps > 200

@@ -134,7 +134,7 @@ def test_bench_launcher_runs_two_real_ranks_on_one_gpu(hip_lib):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--envs", "8192", "--steps", "12", "--warmup", "3",
-                          "--burn-in", "40", "--no-cpu-baseline", "--no-config3"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+                          "--burn-in", "40", "--no-cpu-baseline", "--no-config3", "--full"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -166,7 +166,7 @@ def test_bench_multi_rank_path_under_rccl_with_one_rank(hip_lib):
     env = dict(os.environ, POM_BENCH_RCCL_SOLO="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-config3"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-config3", "--full"],
                          capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
