@@ -139,6 +139,39 @@ int pom_batch_generate(PomBatch* h, uint64_t board_seed);
 /* games started so far by envs [first, first+count) (0 = still the first one), uint32 each */
 int pom_batch_episodes(PomBatch* h, int64_t first, int64_t count, uint32_t* out);
 
+/*
+ * Copy and restore games by index on the device (tree search, Monte-Carlo rollouts, population methods): env first + i becomes a
+ * copy of env src[i], for i in [0, count).  Indices are int64.  The host variant reads src_host now; the device variant reads
+ * src_dev on the handle's stream, in stream order like the moves of pom_batch_step_device.
+ *
+ * Aliasing: the result is as if every source had been read before any destination was written.  Sources may lie inside
+ * [first, first + count) and may repeat: an in-place resample src = before[perm_with_repeats] is the main case.
+ *
+ * Default (the source's CURRENT state): the destination takes over the source's record (board, timeStep, agents, bomb and flame
+ * queues, status, ubflags), its SimpleAgent memory (if allocated), its episode counter (pom_batch_episodes) and, with
+ * POM_RESET_AT_END, its terminal record and last results.  Afterwards nothing the API can read tells the destination from the
+ * source but its env index — and that index keys the pom_rng.h move stream, the SimpleAgent's draw and fresh boards, so clones
+ * of one root DIVERGE under pom_batch_step_random / _step_simple: what rollouts want.
+ * POM_COPY_FROM_SNAPSHOT: the source is env src[i]'s restart snapshot instead of its current state; the destination gets fresh
+ *   agent memory (as after pom_batch_upload), its episode counter and terminal record stay as they were.  src[i] = first + i
+ *   puts a game back on its start.
+ * POM_COPY_SET_SNAPSHOT: the copied record also becomes the destination's snapshot, status and ubflags cleared as
+ *   pom_batch_snapshot does: a clone's restart point is its root.
+ * Entries src[i] < 0 leave env first + i untouched (a masked copy or reset).  The device variant also leaves entries >= n
+ * untouched; the host variant rejects them with POM_E_ARG before anything is changed.  A range outside [0, n) or unknown flags:
+ * POM_E_ARG.  Counters (POM_CNT_*) and the handle's tick do not change.  Like pom_batch_upload the call first settles chained
+ * launches; the copy itself is queued on the handle's stream and does not block.
+ *
+ * How it moves (pom_copy.h): one wavefront per destination tile gathers the tile with its new columns into a scratch image (state
+ * columns are 124 bytes at byte c * 16 + e % 16 plus dwords 31..79 at dword d * 16 + e % 16 of the tile; snapshot and terminal
+ * records are dense 80-dword records), then a second kernel writes the image back in whole tiles.  The scratch (320 B + 36 B per
+ * env, + 320 B with POM_RESET_AT_END) is allocated on first use and freed by pom_batch_destroy.  The host variant skips the
+ * scratch when no source lies in [first, first + count) (fan-out): the same bytes, one pass.
+ */
+enum { POM_COPY_FROM_SNAPSHOT = 1, POM_COPY_SET_SNAPSHOT = 2 };
+int pom_batch_copy_envs(PomBatch* h, const int64_t* src_host, int64_t first, int64_t count, int32_t flags);
+int pom_batch_copy_envs_device(PomBatch* h, const int64_t* src_dev, int64_t first, int64_t count, int32_t flags);
+
 /* one tick with explicit moves: int32[n_envs][4], host or device memory */
 int pom_batch_step(PomBatch* h, const int32_t* moves_host);
 int pom_batch_step_device(PomBatch* h, const int32_t* moves_dev);
@@ -229,8 +262,10 @@ int pom_chain_litmus(int32_t device, int64_t tiles, int32_t launches, int32_t st
 int pom_batch_stream(PomBatch* h, void** stream);
 
 /* zero-copy view for device-side consumers (policies, observation kernels): packed records in tiles of 16 envs,
- * dword d of env e at base[(e / 16) * (16 * rec_dwords) + d * 16 + e % 16]; n_pad = envs the buffer holds (a multiple of 64);
- * layout in pomcpp_amd/csrc/pom_packed.h */
+ * dword d >= 31 (timeStep, agents, bomb and flame queues) of env e at base[(e / 16) * (16 * rec_dwords) + d * 16 + e % 16]; the
+ * board (dwords 0..30 of the tile) is laid out by cell: cell c of env e is BYTE c * 16 + e % 16 of its tile, i.e. of
+ * (uint8_t*)base + (e / 16) * 64 * rec_dwords; n_pad = envs the buffer holds (a multiple of 64); layout in
+ * pomcpp_amd/csrc/pom_packed.h */
 int pom_batch_device_view(PomBatch* h, void** base, int64_t* n_pad, int32_t* rec_dwords);
 
 /*

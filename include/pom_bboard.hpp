@@ -479,6 +479,17 @@ public:
         pom_check(pom_batch_download(h_, &states_[size_t(e)], e, 1));
         return states_[size_t(e)];
     }
+    // game first + i becomes a copy of game src[i] (pom_batch_copy_envs: every source read before any destination is written;
+    // entries < 0 leave their game alone; flags POM_COPY_FROM_SNAPSHOT / POM_COPY_SET_SNAPSHOT).  CopyGames takes host indices,
+    // CopyGamesDevice an int64 array in device memory, read on the batch's stream.  Tree search: fan a root out, put a child back.
+    void CopyGames(const int64_t* src, int64_t first, int64_t count, int flags = 0)
+    {
+        pom_check(pom_batch_copy_envs(h_, src, first, count, flags));
+    }
+    void CopyGamesDevice(const int64_t* srcDev, int64_t first, int64_t count, int flags = 0)
+    {
+        pom_check(pom_batch_copy_envs_device(h_, srcDev, first, count, flags));
+    }
     bool IsDone(int64_t e) { return Query(e, 0) != 0; }
     bool IsDraw(int64_t e) { return Query(e, 2) != 0; }
     int GetWinner(int64_t e) { return Query(e, 1); }

@@ -30,6 +30,7 @@ RESET_OFF, RESET_AT_START, RESET_AT_END = 0, 1, 2  # PomBatchOptions.auto_reset 
 DIST_HARMLESS, DIST_RANDOM, DIST_STRESS = 0, 1, 2
 CNT_STEPS, CNT_EPISODES, CNT_RESETS, CNT_UB_TICKS = 0, 1, 2, 3
 ISSUE_AUTO, ISSUE_DIRECT, ISSUE_THREADS, ISSUE_GRAPH, ISSUE_CHAIN = 0, 1, 2, 3, 4  # PomBatchOptions.issue_mode
+COPY_FROM_SNAPSHOT, COPY_SET_SNAPSHOT = 1, 2  # pom_batch_copy_envs flags
 UB_LOST_AGENT, UB_NULL_BOMB, UB_QUEUE_OVERFLOW, UB_REVERT_LOOP, UB_BAD_INDEX = 1, 2, 4, 8, 16
 
 
@@ -94,6 +95,9 @@ def load_library() -> C.CDLL:
     lib.pom_batch_upload.argtypes = [P, VP, I64, I64]
     lib.pom_batch_download.argtypes = [P, VP, I64, I64]
     lib.pom_batch_snapshot.argtypes = [P]
+    if not os.environ.get("POM_LIB") or hasattr(lib, "pom_batch_copy_envs"):
+        lib.pom_batch_copy_envs.argtypes = [P, VP, I64, I64, I32]
+        lib.pom_batch_copy_envs_device.argtypes = [P, VP, I64, I64, I32]
     lib.pom_batch_step.argtypes = [P, VP]
     lib.pom_batch_step_device.argtypes = [P, VP]
     if not os.environ.get("POM_LIB") or hasattr(lib, "pom_batch_step_device_many"):
@@ -238,6 +242,63 @@ class BatchEnvironment:
 
     def snapshot(self) -> None:
         _check(self._lib, self._lib.pom_batch_snapshot(self._h))
+
+    # ---- copy / restore games by index (tree search, rollouts, populations) ---------------------------
+    def copy_envs(self, src, first: int = 0, *, from_snapshot: bool = False, set_snapshot: bool = False,
+                  count: Optional[int] = None) -> None:
+        """Env first + i becomes a copy of env src[i] (pom_batch_copy_envs): record, SimpleAgent memory, episode counter and, with
+        RESET_AT_END, the last finished episode — as if every source were read before any destination is written (sources may lie
+        in the range and repeat).  Entries < 0 leave their env alone.  from_snapshot: copy src[i]'s restart snapshot instead (fresh
+        agents; episode and terminal record stay).  set_snapshot: the copy also becomes the destination's snapshot.
+        src: a numpy integer array (host variant: entries >= n raise), a torch int64 tensor on this handle's device (device variant,
+        read in stream order behind torch's current stream; entries >= n are left alone too), or a raw device address of int64
+        with `count`."""
+        flags = (COPY_FROM_SNAPSHOT if from_snapshot else 0) | (COPY_SET_SNAPSHOT if set_snapshot else 0)
+        if hasattr(src, "data_ptr"):
+            shape = tuple(getattr(src, "shape", ()))
+            if len(shape) != 1 or (count is not None and count != shape[0]):
+                raise ValueError(f"src must be a 1-d int64 tensor, got shape {shape}")
+            if "int64" not in str(getattr(src, "dtype", "")):
+                raise ValueError(f"src must be int64, got {getattr(src, 'dtype', None)}")
+            if hasattr(src, "is_contiguous") and not src.is_contiguous():
+                raise ValueError("src must be contiguous")
+            dev = getattr(src, "device", None)
+            if dev is not None and (getattr(dev, "type", "cuda") != "cuda" or getattr(dev, "index", self.device) not in (None, self.device)):
+                raise ValueError(f"src lives on {dev}, the batch on device {self.device}")
+            self._after_torch(src)
+            _check(self._lib, self._lib.pom_batch_copy_envs_device(self._h, src.data_ptr(), int(first), shape[0], flags))
+        elif isinstance(src, (int, np.integer)) and not isinstance(src, bool):
+            if count is None:
+                raise ValueError("a raw device address needs `count`")
+            _check(self._lib, self._lib.pom_batch_copy_envs_device(self._h, int(src), int(first), int(count), flags))
+        else:
+            idx = np.asarray(src)
+            if idx.ndim != 1 or not np.issubdtype(idx.dtype, np.integer):
+                raise ValueError("src must be a 1-d integer array")
+            idx = np.ascontiguousarray(idx, dtype=np.int64)
+            if count is not None and count != idx.size:
+                raise ValueError(f"count {count} does not match src of {idx.size} entries")
+            _check(self._lib, self._lib.pom_batch_copy_envs(self._h, idx.ctypes.data, int(first), idx.size, flags))
+
+    def restore(self, envs) -> None:
+        """Put the given envs back on their restart snapshot with fresh agents: a boolean mask of n, or a list of env indices.
+        A thin wrapper over copy_envs(..., from_snapshot=True)."""
+        envs = np.asarray(envs)
+        if envs.dtype == bool:
+            if envs.shape != (self.n,):
+                raise ValueError(f"a mask must have {self.n} entries, got {envs.shape}")
+            src = np.where(envs, np.arange(self.n, dtype=np.int64), -1)
+            self.copy_envs(src, 0, from_snapshot=True)
+            return
+        idx = np.unique(np.ascontiguousarray(envs, dtype=np.int64).reshape(-1))
+        if idx.size == 0:
+            return
+        if idx[0] < 0 or idx[-1] >= self.n:
+            raise ValueError(f"env indices must lie in [0, {self.n})")
+        lo, hi = int(idx[0]), int(idx[-1]) + 1
+        src = np.full(hi - lo, -1, dtype=np.int64)
+        src[idx - lo] = idx
+        self.copy_envs(src, lo, from_snapshot=True)
 
     # ---- Environment::Step --------------------------------------------------------------------
     def step(self, moves: np.ndarray) -> None:

@@ -7,6 +7,7 @@
 #include <mutex>
 
 #include "pom_runtime.h"
+#include "pom_copy.h"
 
 extern "C" {
 
@@ -43,6 +44,8 @@ int pom_batch_destroy(PomBatch* h)
     (void)hipFree(h->agent_mem);
     (void)hipFree(h->episode);
     (void)hipFree(h->staging);
+    (void)hipFree(h->copy_scratch);
+    (void)hipFree(h->copy_idx);
     (void)hipFree(h->wave_counters);
     (void)hipFree(h->totals_dev);
     (void)hipFree(h->first_bad);
@@ -313,6 +316,105 @@ int pom_batch_snapshot(PomBatch* h)
     pom_snapshot_kernel<<<dim3((unsigned)((h->n_pad + 255) / 256)), dim3(256), 0, h->stream>>>(h->state, h->snap, h->n_pad);
     HIPCHK(hipGetLastError());
     return POM_OK;
+}
+
+/* pom_batch_copy_envs / _device (pom_copy.h): K1 gathers every destination tile with its new columns, K2 writes the images back;
+ * direct = K1 writes the batch's arrays itself (the host variant, where it has seen that no source is a destination) */
+static int copy_envs(PomBatch* h, const int64_t* src_dev, int64_t first, int64_t count, int32_t flags, bool direct)
+{
+    if (count == 0) return POM_OK;
+    CopyParams p;
+    p.src = src_dev;
+    p.first = first;
+    p.count = count;
+    p.n = h->n;
+    p.n_pad = h->n_pad;
+    p.tile0 = first / POM_TILE_ENVS;
+    p.flags = flags;
+    p.state = h->state;
+    p.snap = h->snap;
+    p.agent_mem = h->agent_mem;
+    p.episode = h->episode;
+    p.terminal = h->terminal;
+    if (direct) {
+        p.out_state = h->state;
+        p.out_agent_mem = h->agent_mem;
+        p.out_episode = h->episode;
+        p.out_terminal = h->terminal;
+    } else {
+        const size_t np = (size_t)h->n_pad;
+        if (!h->copy_scratch) { /* state image, agent memory [2][4 * n_pad], episode, terminal: laid out like the real arrays */
+            const size_t words = np * (POM_REC_DWORDS + 9 + (h->terminal ? POM_REC_DWORDS : 0));
+            hipError_t e = hipMalloc((void**)&h->copy_scratch, words * 4);
+            if (e != hipSuccess) {
+                h->copy_scratch = nullptr;
+                set_err("pom_batch_copy_envs: scratch", e);
+                return e == hipErrorOutOfMemory ? POM_E_NOMEM : POM_E_HIP;
+            }
+        }
+        p.out_state = h->copy_scratch;
+        p.out_agent_mem = h->copy_scratch + np * POM_REC_DWORDS;
+        p.out_episode = p.out_agent_mem + np * 8;
+        p.out_terminal = h->terminal ? p.out_episode + np : nullptr;
+    }
+    const unsigned tiles = (unsigned)((first + count - 1) / POM_TILE_ENVS - p.tile0 + 1);
+    pom_copy_gather_kernel<<<dim3(tiles), dim3(64), 0, h->stream>>>(p);
+    HIPCHK(hipGetLastError());
+    if (!direct) {
+        pom_copy_scatter_kernel<true><<<dim3(tiles), dim3(64), 0, h->stream>>>(p);
+        HIPCHK(hipGetLastError());
+    } else if (flags & POM_COPY_SET_SNAPSHOT) {
+        pom_copy_scatter_kernel<false><<<dim3(tiles), dim3(64), 0, h->stream>>>(p);
+        HIPCHK(hipGetLastError());
+    }
+    return POM_OK;
+}
+
+static int copy_check(PomBatch* h, const void* src, int64_t first, int64_t count, int32_t flags)
+{
+    if (int rc = check_range(h, first, count)) return rc;
+    if ((flags & ~(POM_COPY_FROM_SNAPSHOT | POM_COPY_SET_SNAPSHOT)) != 0 || (!src && count > 0)) {
+        snprintf(g_err, sizeof g_err, "pom_batch_copy_envs: unknown flags 0x%x or no index array", (unsigned)flags);
+        return POM_E_ARG;
+    }
+    return POM_OK;
+}
+
+int pom_batch_copy_envs(PomBatch* h, const int64_t* src_host, int64_t first, int64_t count, int32_t flags)
+{
+    if (int rc = copy_check(h, src_host, first, count, flags)) return rc;
+    bool overlap = false;
+    for (int64_t i = 0; i < count; i++) {
+        const int64_t s = src_host[i];
+        if (s >= h->n) {
+            snprintf(g_err, sizeof g_err, "pom_batch_copy_envs: src[%lld] = %lld is not an env of the batch (n = %lld)", (long long)i,
+                     (long long)s, (long long)h->n);
+            return POM_E_ARG;
+        }
+        overlap |= s >= first && s < first + count;
+    }
+    if (count == 0) return POM_OK;
+    HIPCHK(hipSetDevice(h->device));
+    if (int jr = quiesce(h)) return jr;
+    if (!h->copy_idx) {
+        hipError_t e = hipMalloc((void**)&h->copy_idx, (size_t)h->n_pad * sizeof(int64_t));
+        if (e != hipSuccess) {
+            h->copy_idx = nullptr;
+            set_err("pom_batch_copy_envs: index buffer", e);
+            return e == hipErrorOutOfMemory ? POM_E_NOMEM : POM_E_HIP;
+        }
+    }
+    HIPCHK(hipMemcpyAsync(h->copy_idx, src_host, (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    return copy_envs(h, h->copy_idx, first, count, flags, !overlap);
+}
+
+int pom_batch_copy_envs_device(PomBatch* h, const int64_t* src_dev, int64_t first, int64_t count, int32_t flags)
+{
+    if (int rc = copy_check(h, src_dev, first, count, flags)) return rc;
+    if (count == 0) return POM_OK;
+    HIPCHK(hipSetDevice(h->device));
+    if (int jr = quiesce(h)) return jr;
+    return copy_envs(h, src_dev, first, count, flags, false);
 }
 
 

@@ -159,6 +159,62 @@ POM_HD void pom_rec_set_cell(uint32_t* rec, int64_t stride, int c, int code, int
 }
 
 /*
+ * Moving one env's record between places, item by item (pom_batch_copy_envs, pom_copy.h).  A record is POM_COL_ITEMS items: the
+ * 124 board bytes (cells 0..120 and the three zero bytes behind them), then dwords 31..79.  Item k of the column of env number
+ * `lane` (0..15) of a tile (`tile` = the tile's first dword) is byte k * 16 + lane of the tile for k < 124, dword
+ * (31 + k - 124) * 16 + lane otherwise; item k of a dense record (snapshot, terminal) is byte k for k < 124, dword 31 + k - 124
+ * otherwise.  A wavefront moves a record with its lanes taking items lane, lane + 64, lane + 128; the host tests loop over k.
+ */
+enum { POM_COL_BOARD_ITEMS = 4 * POM_REC_BOARD_DWORDS, POM_COL_ITEMS = POM_COL_BOARD_ITEMS + POM_REC_DWORDS - POM_REC_TIMESTEP /* 173 */ };
+
+/* tile column -> tile column */
+POM_HD void pom_col_copy_item(uint32_t* dst_tile, int dst_lane, const uint32_t* src_tile, int src_lane, int k)
+{
+    if (k < POM_COL_BOARD_ITEMS)
+        reinterpret_cast<uint8_t*>(dst_tile)[k * POM_TILE_ENVS + dst_lane] = reinterpret_cast<const uint8_t*>(src_tile)[k * POM_TILE_ENVS + src_lane];
+    else {
+        const int d = POM_REC_TIMESTEP + k - POM_COL_BOARD_ITEMS;
+        dst_tile[d * POM_TILE_ENVS + dst_lane] = src_tile[d * POM_TILE_ENVS + src_lane];
+    }
+}
+/* dense record -> tile column */
+POM_HD void pom_rec_to_col_item(uint32_t* dst_tile, int dst_lane, const uint32_t* rec, int k)
+{
+    if (k < POM_COL_BOARD_ITEMS)
+        reinterpret_cast<uint8_t*>(dst_tile)[k * POM_TILE_ENVS + dst_lane] = reinterpret_cast<const uint8_t*>(rec)[k];
+    else {
+        const int d = POM_REC_TIMESTEP + k - POM_COL_BOARD_ITEMS;
+        dst_tile[d * POM_TILE_ENVS + dst_lane] = rec[d];
+    }
+}
+/* tile column -> dense record; as_snapshot: status and ubflags come out clear (the top bytes of agent words 35, 37, 39 = bytes 1..3
+ * of meta2), as pom_batch_snapshot leaves them */
+POM_HD void pom_col_to_rec_item(uint32_t* rec, const uint32_t* src_tile, int src_lane, int k, bool as_snapshot)
+{
+    if (k < POM_COL_BOARD_ITEMS)
+        reinterpret_cast<uint8_t*>(rec)[k] = reinterpret_cast<const uint8_t*>(src_tile)[k * POM_TILE_ENVS + src_lane];
+    else {
+        const int d = POM_REC_TIMESTEP + k - POM_COL_BOARD_ITEMS;
+        const uint32_t v = src_tile[d * POM_TILE_ENVS + src_lane];
+        const bool meta2_hi = d == POM_REC_AGENTS + 3 || d == POM_REC_AGENTS + 5 || d == POM_REC_AGENTS + 7;
+        rec[d] = as_snapshot && meta2_hi ? v & 0x00FFFFFFu : v;
+    }
+}
+/* whole records, for host code and tests */
+POM_HD void pom_col_copy(uint32_t* dst_tile, int dst_lane, const uint32_t* src_tile, int src_lane)
+{
+    for (int k = 0; k < POM_COL_ITEMS; k++) pom_col_copy_item(dst_tile, dst_lane, src_tile, src_lane, k);
+}
+POM_HD void pom_rec_to_col(uint32_t* dst_tile, int dst_lane, const uint32_t* rec)
+{
+    for (int k = 0; k < POM_COL_ITEMS; k++) pom_rec_to_col_item(dst_tile, dst_lane, rec, k);
+}
+POM_HD void pom_col_to_rec(uint32_t* rec, const uint32_t* src_tile, int src_lane, bool as_snapshot)
+{
+    for (int k = 0; k < POM_COL_ITEMS; k++) pom_col_to_rec_item(rec, src_tile, src_lane, k, as_snapshot);
+}
+
+/*
  * Pack one boundary State into a record.  `rec` is addressed with a stride so
  * the same code fills a column of a device tile (stride = POM_TILE_ENVS) and a dense
  * record in host-side tests (stride = 1).  Returns 0, or 1 if a field does not

@@ -49,6 +49,9 @@ struct PomBatch {
     uint64_t board_seed = 0;
     int fresh = 0;
     int32_t* staging = nullptr;     /* staging_envs x 251 dwords (AoS), also status scratch */
+    uint32_t* copy_scratch = nullptr; /* pom_batch_copy_envs: K1's image of state, agent memory, episode (and terminal), allocated on
+                                         first use (pom_copy.h) */
+    int64_t* copy_idx = nullptr;      /* ... and the host variant's indices on the device, n_pad int64 */
     int64_t staging_envs = 0;
     int64_t* wave_counters = nullptr;
     int64_t* totals_dev = nullptr;
