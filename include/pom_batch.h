@@ -331,7 +331,8 @@ int pom_bench_policy(const uint8_t* codes_dev, int32_t* moves_dev, int64_t first
  * calling thread gets a pinned page and a stream of its own (up to 64 threads; more share), so threads stepping their own
  * States do not wait for each other.  Code that steps many States should still hand them to one PomBatch
  * (pom_batch_upload / pom_batch_step): a launch per State is latency, not throughput.
- * POM_E_UNREPRESENTABLE: the State holds a value the device record cannot hold; it is left as it is. */
+ * POM_E_UNREPRESENTABLE: the State holds a value the device record cannot hold, or one that ticks could push out of it (the upload
+ * bounds of pom_packed.h: bombCount -108..107, maxBombCount <= 32646, bombStrength 0..134, aliveAgents >= -124); it is left as it is. */
 int pom_step(void* state_1004, const int32_t moves[4]);
 
 /* The same with Environment::Step's bookkeeping after the tick (src/bboard/environment.cpp:148-168): timeStep++, then

@@ -10,7 +10,7 @@
  * reference — the episode is restarted instead.  Lost-agent ticks (Q-UB1) are
  * run through the padded-moves shim and counted separately.
  *
- * usage: fuzz_diff <scenario 0..3> <steps> <seed>
+ * usage: fuzz_diff <scenario 0..4> <steps> <seed>
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -19,6 +19,7 @@
 
 #include "pom_oracle.h"
 #include "pom_rng.h"
+#include "pom_testgen.h" /* scenario 4 */
 
 void ref_step(void *state, const int *moves);
 void ref_init_state(void *p);
@@ -128,13 +129,15 @@ int main(int argc, char **argv)
         printf("layout mismatch: reference State is %d bytes\n", ref_state_size());
         return 2;
     }
-    int dist = scenario == 0 ? POM_DIST_HARMLESS : scenario == 2 ? POM_DIST_STRESS : POM_DIST_RANDOM;
+    int dist = scenario == 0 ? POM_DIST_HARMLESS : scenario == 2 || scenario == 4 ? POM_DIST_STRESS : POM_DIST_RANDOM;
+    PomTestRng trng = {pom_splitmix64(seed) | 1};
 
     PomState cur, a, b;
     long long done = 0, compared = 0, lost = 0, lost_mismatch = 0, skipped = 0, episodes = 0;
-    long long ubcount[5] = { 0 };
+    long long ubcount[6] = { 0 }, over20 = 0, max_flames = 0;
     while (done < steps) {
-        gen_board(&cur, scenario);
+        if (scenario == 4) pom_testgen_board(&cur, scenario, &trng); /* (0..3: this file's own boards, as the logs have them) */
+        else gen_board(&cur, scenario);
         episodes++;
         for (int t = 0; t < 800 && done < steps; t++) {
             int32_t mv[4];
@@ -143,8 +146,8 @@ int main(int argc, char **argv)
             uint32_t ub = pom_oracle_step(&a, mv);
             a.timeStep++;
             done++;
-            for (int k = 0; k < 5; k++) if (ub & (1u << k)) ubcount[k]++;
-            if (ub & ~(uint32_t)POM_UB_LOST_AGENT) { skipped++; break; } /* reference would crash */
+            for (int k = 0; k < 6; k++) if (ub & (1u << k)) ubcount[k]++;
+            if (ub & ~(uint32_t)(POM_UB_LOST_AGENT | POM_UB_FLAME_QUEUE_RANGE)) { skipped++; break; } /* reference would crash */
             b = cur;
             ref_step(&b, mv);
             b.timeStep++;
@@ -163,13 +166,16 @@ int main(int argc, char **argv)
                     return 1;
                 }
             }
+            over20 += a.flames.count > 20;
+            if (a.flames.count > max_flames) max_flames = a.flames.count;
             cur = a;
             if (cur.aliveAgents <= 1) break;
         }
     }
     printf("scenario %d seed %llu: steps %lld episodes %lld compared %lld mismatches 0 | lost-agent ticks %lld (mismatch %lld) | "
-           "skipped-UB ticks %lld | flags lost %lld null_bomb %lld overflow %lld revert %lld badidx %lld\n",
+           "skipped-UB ticks %lld | flags lost %lld null_bomb %lld overflow %lld revert %lld badidx %lld flame_queue_range %lld | "
+           "ticks with > 20 flames queued %lld (max %lld)\n",
            scenario, (unsigned long long)seed, done, episodes, compared, lost, lost_mismatch, skipped, ubcount[0],
-           ubcount[1], ubcount[2], ubcount[3], ubcount[4]);
+           ubcount[1], ubcount[2], ubcount[3], ubcount[4], ubcount[5], over20, max_flames);
     return 0;
 }

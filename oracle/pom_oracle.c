@@ -192,6 +192,7 @@ static void spawn_flame(PomState *s, int x, int y, int strength, uint32_t *ub) /
     f->timeLeft = POM_FLAME_LIFETIME;
     int signature = (uint16_t)((x + N * y) << 3);
     s->flames.count++;
+    if (s->flames.count > 255) *ub |= POM_UB_FLAME_QUEUE_RANGE; /* the device record holds it at 255 (pom_state.h) */
 
     if (s->board[y][x] >= POM_AGENT0)
         kill_agent(s, s->board[y][x] - POM_AGENT0, ub);
@@ -236,10 +237,14 @@ static void pop_flame(PomState *s) /* bboard.cpp:148-180 */
     s->flames.count--;
 }
 
-static void tick_flames(PomState *s) /* step_utility.cpp:208-222 */
+static void tick_flames(PomState *s, uint32_t *ub) /* step_utility.cpp:208-222 */
 {
     for (int i = 0; i < s->flames.count; i++)
         s->flames.queue[fq(s, i)].timeLeft--;
+    /* the values stay the reference's; the flag says that the device record holds this one at -128 (pom_state.h) */
+    for (int i = 0; i < s->flames.count && i < QN; i++)
+        if (s->flames.queue[fq(s, i)].timeLeft < -128)
+            *ub |= POM_UB_FLAME_QUEUE_RANGE;
     int n = s->flames.count;
     for (int i = 0; i < n; i++)
         if (s->flames.queue[fq(s, 0)].timeLeft == 0)
@@ -405,7 +410,7 @@ uint32_t pom_oracle_step(void *state, const int32_t *moves)
     PomState *s = (PomState *)state;
     uint32_t ub = 0;
 
-    tick_flames(s); /* step.cpp:15 */
+    tick_flames(s, &ub); /* step.cpp:15 */
 
     /* step.cpp:21-26 with step_utility.cpp:130-170; dead agents take part */
     Pos old_pos[POM_AGENT_COUNT], dest[POM_AGENT_COUNT];

@@ -22,14 +22,16 @@ static inline uint32_t ptg_rnd(PomTestRng *r)
 }
 static inline int ptg_rndn(PomTestRng *r, int n) { return (int)(ptg_rnd(r) % (uint32_t)n); }
 
-/* scenario 0/1: reference distribution; 2: kick/chain stress (config 5); 3: powerup-rich, mixed agents */
+/* scenario 0/1: reference distribution; 2: kick/chain stress (config 5); 3: powerup-rich, mixed agents; 4: crowded flame queue —
+ * 18 bombs queued at the start in two waves, agents with room for 8 bombs each: more than 20 flames get queued and heads step
+ * over 0 (the >20-flame path of TickFlames, step_utility.cpp:208-222) */
 static inline void pom_testgen_board(PomState *s, int scenario, PomTestRng *r)
 {
     pom_oracle_init_state(s);
     int woods[121], nw = 0;
     int32_t *cells = &s->board[0][0];
     for (int c = 0; c < 121; c++) {
-        int k = ptg_rndn(r, scenario == 2 ? 14 : 7);
+        int k = ptg_rndn(r, scenario == 2 || scenario == 4 ? 14 : 7);
         int v = POM_PASSAGE;
         if (k == 1) v = POM_RIGID;
         else if (k == 2) { v = POM_WOOD; woods[nw++] = c; }
@@ -62,6 +64,19 @@ static inline void pom_testgen_board(PomState *s, int scenario, PomTestRng *r)
                 int *b = &s->bombs.queue[(s->bombs.index + before) % 20];
                 *b = (*b & ~0xF00000) + ((1 + ptg_rndn(r, 4)) << 20);
             }
+        }
+    }
+    if (scenario == 4) {
+        for (int i = 0; i < 4; i++) {
+            s->agents[i].canKick = 1;
+            s->agents[i].maxBombCount = 8;
+            s->agents[i].bombStrength = 1 + ptg_rndn(r, 2);
+        }
+        /* two waves in queue order: the second goes off while the first one's flames are still queued */
+        for (int k = 0; k < 60 && s->bombs.count < 18; k++) {
+            int x = 1 + ptg_rndn(r, 9), y = 1 + ptg_rndn(r, 9);
+            if (s->board[y][x] != POM_PASSAGE) continue;
+            pom_oracle_plant_bomb(s, x, y, k & 3, s->bombs.count < 10 ? 2 : 4 + (s->bombs.count >= 14), 1);
         }
     }
     if (scenario == 3) {

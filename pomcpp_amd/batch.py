@@ -31,7 +31,7 @@ DIST_HARMLESS, DIST_RANDOM, DIST_STRESS = 0, 1, 2
 CNT_STEPS, CNT_EPISODES, CNT_RESETS, CNT_UB_TICKS = 0, 1, 2, 3
 ISSUE_AUTO, ISSUE_DIRECT, ISSUE_THREADS, ISSUE_GRAPH, ISSUE_CHAIN = 0, 1, 2, 3, 4  # PomBatchOptions.issue_mode
 COPY_FROM_SNAPSHOT, COPY_SET_SNAPSHOT = 1, 2  # pom_batch_copy_envs flags
-UB_LOST_AGENT, UB_NULL_BOMB, UB_QUEUE_OVERFLOW, UB_REVERT_LOOP, UB_BAD_INDEX = 1, 2, 4, 8, 16
+UB_LOST_AGENT, UB_NULL_BOMB, UB_QUEUE_OVERFLOW, UB_REVERT_LOOP, UB_BAD_INDEX, UB_FLAME_QUEUE_RANGE = 1, 2, 4, 8, 16, 32
 
 
 class PomError(RuntimeError):

@@ -1853,7 +1853,7 @@ __global__ __launch_bounds__(64) void pom_step_one_kernel(StepOneParams q)
     }
     const int32_t alive = st[122], bIdx = st[167], bCnt = st[168], fIdx = st[249], fCnt = st[250];
     if (lane == 61) {
-        bad |= (alive < -128) | (alive > 127);
+        bad |= pom_pack_alive_bad(alive);
         bad |= (bIdx < 0) | (bIdx >= POM_MAX_BOMBS) | (bCnt < 0) | (bCnt > POM_MAX_BOMBS);
         bad |= (fIdx < 0) | (fIdx >= POM_MAX_BOMBS) | (fCnt < 0) | (fCnt > 255);
         tile[POM_REC_TIMESTEP * 16] = (uint32_t)st[121];
@@ -1863,8 +1863,7 @@ __global__ __launch_bounds__(64) void pom_step_one_kernel(StepOneParams q)
         const uint32_t flags = (uint32_t)a[5];
         const int kick = (flags & 0xFF) != 0, dead = ((flags >> 8) & 0xFF) != 0;
         bad |= (a[0] < 0) | (a[0] >= POM_BOARD_SIZE) | (a[1] < 0) | (a[1] >= POM_BOARD_SIZE);
-        bad |= (a[2] < -128) | (a[2] > 127);
-        bad |= (a[3] < -32768) | (a[3] > 32767) | (a[4] < 0) | (a[4] > 255);
+        bad |= pom_pack_agent_bad(a[2], a[3], a[4]);
         /* the top bytes: aliveAgents, bombs.index, bombs.count, flames.index in the agents' first words; flames.count (and the clear
          * status and flags) in their second words (pom_packed.h) */
         const uint32_t m0 = (uint32_t)(lane == 0 ? alive : lane == 1 ? bIdx : lane == 2 ? bCnt : fIdx) & 0xFFu, m1 = lane == 0 ? (uint32_t)fCnt & 0xFFu : 0u;

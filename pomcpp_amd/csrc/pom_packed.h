@@ -215,6 +215,31 @@ POM_HD void pom_col_to_rec(uint32_t* rec, const uint32_t* src_tile, int src_lane
 }
 
 /*
+ * Upload bounds of the narrow fields, chosen so that NO sequence of ticks can take a field out of its width (a state beyond them
+ * is refused with POM_E_UNREPRESENTABLE; games start at bombCount 0, maxBombCount 1, bombStrength 1, aliveAgents 4):
+ *   bombCount (8 bits, signed)  goes up by one per bomb its agent plants and down by one per bomb of its agent that explodes
+ *        (bboard.cpp:95,116,144), and every planted bomb is queued: bombCount - (the agent's bombs in the queue) never changes.
+ *        The queue holds 0..20 bombs, so bombCount stays within 20 of where it started.
+ *   maxBombCount (16 bits, signed), bombStrength (8 bits)  grow by one per EXTRABOMB / INCRRANGE picked up and never shrink
+ *        (step_utility.cpp:247-256).  A power-up comes from a cell (a power-up, a wood or a flagged flame of the start state) and
+ *        picking it up uses it up; nothing puts a new one on the board.  So all agents together pick up at most 121.
+ *        ag_strength_inc's hold at 255 (pom_step_body.h) is then a guard that no uploaded state reaches.
+ *   aliveAgents (8 bits, signed)  goes down by one per agent that dies, and State::Kill kills an agent once (bboard.hpp:474-481).
+ */
+enum {
+    POM_PACK_BOMBCOUNT_MIN = -128 + POM_MAX_BOMBS, POM_PACK_BOMBCOUNT_MAX = 127 - POM_MAX_BOMBS, /* -108 .. 107 */
+    POM_PACK_MAXBOMBS_MAX = 32767 - POM_CELLS,                                                /* 32646 (and >= -32768) */
+    POM_PACK_STRENGTH_MAX = 255 - POM_CELLS,                                                   /* 134 (and >= 0) */
+    POM_PACK_ALIVE_MIN = -128 + POM_AGENT_COUNT                                                /* -124 (and <= 127) */
+};
+POM_HD int pom_pack_agent_bad(int32_t bomb_count, int32_t max_bombs, int32_t strength)
+{
+    return (bomb_count < POM_PACK_BOMBCOUNT_MIN) | (bomb_count > POM_PACK_BOMBCOUNT_MAX) | (max_bombs < -32768) |
+           (max_bombs > POM_PACK_MAXBOMBS_MAX) | (strength < 0) | (strength > POM_PACK_STRENGTH_MAX);
+}
+POM_HD int pom_pack_alive_bad(int32_t alive) { return (alive < POM_PACK_ALIVE_MIN) | (alive > 127); }
+
+/*
  * Pack one boundary State into a record.  `rec` is addressed with a stride so
  * the same code fills a column of a device tile (stride = POM_TILE_ENVS) and a dense
  * record in host-side tests (stride = 1).  Returns 0, or 1 if a field does not
@@ -238,7 +263,7 @@ POM_HD int pom_pack_state(const int32_t* st, uint32_t* rec, int64_t stride, int 
     rec[POM_REC_TIMESTEP * stride] = (uint32_t)timeStep;
 
     const int32_t bIdx = bombs[20], bCnt = bombs[21], fIdx = flames[80], fCnt = flames[81];
-    bad |= (alive < -128) | (alive > 127);
+    bad |= pom_pack_alive_bad(alive);
     bad |= (bIdx < 0) | (bIdx >= POM_MAX_BOMBS) | (bCnt < 0) | (bCnt > POM_MAX_BOMBS);
     bad |= (fIdx < 0) | (fIdx >= POM_MAX_BOMBS) | (fCnt < 0) | (fCnt > 255);
 
@@ -247,8 +272,7 @@ POM_HD int pom_pack_state(const int32_t* st, uint32_t* rec, int64_t stride, int 
         const uint32_t flags = (uint32_t)a[5];
         const int kick = (flags & 0xFF) != 0, dead = ((flags >> 8) & 0xFF) != 0;
         bad |= (a[0] < 0) | (a[0] >= POM_BOARD_SIZE) | (a[1] < 0) | (a[1] >= POM_BOARD_SIZE);
-        bad |= (a[2] < -128) | (a[2] > 127);
-        bad |= (a[3] < -32768) | (a[3] > 32767) | (a[4] < 0) | (a[4] > 255);
+        bad |= pom_pack_agent_bad(a[2], a[3], a[4]);
         rec[(POM_REC_AGENTS + 2 * i) * stride] =
             ((uint32_t)a[0] & 0xF) | (((uint32_t)a[1] & 0xF) << 4) | (((uint32_t)a[2] & 0xFF) << 8) | (kick ? (uint32_t)POM_AG_KICK : 0u) | (dead ? (uint32_t)POM_AG_DEAD : 0u);
         rec[(POM_REC_AGENTS + 2 * i + 1) * stride] = ((uint32_t)a[3] & 0xFFFF) | (((uint32_t)a[4] & 0xFF) << 16);

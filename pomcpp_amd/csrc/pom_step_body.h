@@ -181,8 +181,8 @@ POM_HD int ag_bombcount(int a0) { return pom_sext8((uint32_t)a0 >> 8); }
 POM_HD int ag_bombcount_add(int a0, int d) { return (a0 & ~0xFF00) | (int)(((uint32_t)a0 + ((uint32_t)d << 8)) & 0xFF00u); } /* d may be -1: unsigned arithmetic */
 POM_HD int ag_max_bombs(int a1) { return pom_sext16((uint32_t)a1); }
 POM_HD int ag_strength(int a1) { return (a1 >> 16) & 0xFF; }
-/* ConsumePowerup's bombStrength++ (step_utility.cpp:255): the record holds 8 bits of it — 255 stays 255 (a game would need 254 of
- * the range power-ups; the reference's int goes on counting) */
+/* ConsumePowerup's bombStrength++ (step_utility.cpp:255): the record holds 8 bits of it.  Upload refuses a strength above 134 and a
+ * game picks up at most 121 power-ups (pom_packed.h), so 255 is never reached; the hold there is only a guard */
 POM_HD int ag_strength_inc(int a1) { return ag_strength(a1) == 0xFF ? a1 : a1 + (1 << 16); }
 
 POM_HD int wrap20(int p) /* 0 <= p < 40 */
@@ -346,7 +346,9 @@ struct PomStepper {
             slot = wrap20(slot);
         }
         a.set_flame(slot, x | (y << 8) | (POM_FLAME_LIFETIME << 16) | ((strength & 0xFF) << 24));
-        L.fCnt++;
+        /* the record's count has 8 bits: held at 255 (only a queue whose head has gone below 0 gets there: pom_state.h) */
+        if (__builtin_expect(L.fCnt >= 255, 0)) L.ub |= POM_UB_FLAME_QUEUE_RANGE;
+        else L.fCnt++;
         const int c = y * POM_N + x;
         if (pc_is_agent(e)) kill(pc_agent_id(e));
         a.set_cell(c, POM_C_FLAME + c);
@@ -784,24 +786,34 @@ struct PomStepper {
 
     /* ------------------------------------------------------------------ */
     /* TickFlames, step_utility.cpp:208-222, first half: timeLeft-- of every queued flame.  Returns the head of the queue as
-     * it stands afterwards (0 if the queue is empty) and the number of rounds the pop loop may take. */
+     * it stands afterwards (0 if the queue is empty) and the number of rounds the pop loop may take.
+     * With more than 20 flames queued the reference visits a slot once per offset i = slot - index (mod 20): the head's slot at
+     * i = 0, 20, 40, ..., so the head is what the LAST of those visits leaves.  A timeLeft of -128 (the record's 8 bits) is held
+     * there and raises POM_UB_FLAME_QUEUE_RANGE: the reference's value only falls further, and a negative timeLeft never reaches 0
+     * again, so no pop and no other part of the tick can tell the two apart (pom_state.h). */
     POM_HD void flames_dec(int& top, int& n)
     {
         top = 0;
         n = L.fCnt;
         if (L.fCnt <= 0) return;
-        /* split over the lanes (offsets i and i+20 fall to the same lane) */
+        /* split over the lanes (offsets i and i+20 fall to the same lane: the head's visits all to lane 0) */
         int p = L.fIdx + a.sub();
         p = wrap20(p);
+        int held_any = 0;
         POM_NOUNROLL
         for (int i = a.sub(); i < L.fCnt; i += A::G) {
             const int f = a.flame(p);
-            const int nf = (f & ~0xFF0000) | ((f - 0x10000) & 0xFF0000);
+            const int held = (f & 0xFF0000) == 0x800000;
+            const int nf = held ? f : (f & ~0xFF0000) | ((f - 0x10000) & 0xFF0000);
+            held_any |= held;
             a.put_flame(p, nf);
-            if (i == 0) top = nf;
+            if (p == L.fIdx) top = nf;
             p = wrap20(p + A::G);
         }
-        top = a.template gbcast<0>(top);
+        /* one reduction for both: top is 0 on every lane but the head's, and bit 7 of a flame word is free (x < 11) */
+        const int v = a.gor(top | (held_any << 7));
+        top = v & ~0x80;
+        if (v & 0x80) L.ub |= POM_UB_FLAME_QUEUE_RANGE;
     }
     /* second half: PopFlame (bboard.cpp:148-180) while the head has run out, by the env's own lanes */
     POM_HD void flame_pops(int top, int n)

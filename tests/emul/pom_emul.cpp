@@ -114,12 +114,10 @@ int pom_emul_tile_roundtrip(const void* states_1004, int n, void* out_1004)
     return rc;
 }
 
-/* one tick through pack -> device body -> unpack.  status_io: the env's status byte (ENV mode).
- * returns the POM_UB_* flags of this tick, or 0xFFFFFFFF if the state is not representable */
-uint32_t pom_emul_step(void* state_1004, const int32_t* moves, int env_mode, int max_steps, uint32_t* status_io)
+/* the tick on a record that stays packed between calls, as a device buffer does (no re-pack: a field may sit beyond what upload
+ * accepts); status_io as below */
+uint32_t pom_emul_step_rec(uint32_t* rec, const int32_t* moves, int env_mode, int max_steps, uint32_t* status_io)
 {
-    uint32_t rec[POM_REC_DWORDS];
-    if (pom_pack_state((const int32_t*)state_1004, rec, 1)) return 0xFFFFFFFFu;
     ArrayEnv env;
     std::memset(&env, 0, sizeof env);
     for (int c = 0; c < POM_CELLS; c++) env.cells[c] = (uint8_t)pom_rec_cell(rec, 1, c);
@@ -151,12 +149,22 @@ uint32_t pom_emul_step(void* state_1004, const int32_t* moves, int env_mode, int
         rec[POM_REC_BOMBS + k] = (uint32_t)env.bombs[k];
         rec[POM_REC_FLAMES + k] = (uint32_t)env.flames[k];
     }
+    if (status_io) *status_io = status;
+    return L.ub;
+}
+
+/* one tick through pack -> device body -> unpack.  status_io: the env's status byte (ENV mode).
+ * returns the POM_UB_* flags of this tick, or 0xFFFFFFFF if the state is not representable */
+uint32_t pom_emul_step(void* state_1004, const int32_t* moves, int env_mode, int max_steps, uint32_t* status_io)
+{
+    uint32_t rec[POM_REC_DWORDS];
+    if (pom_pack_state((const int32_t*)state_1004, rec, 1)) return 0xFFFFFFFFu;
+    const uint32_t ub = pom_emul_step_rec(rec, moves, env_mode, max_steps, status_io);
     int32_t out[251];
     std::memset(out, 0, sizeof out);
     pom_unpack_state(rec, 1, out);
     std::memcpy(state_1004, out, POM_STATE_BYTES);
-    if (status_io) *status_io = status;
-    return L.ub;
+    return ub;
 }
 
 /* chained launches: a visit's distance from its call's first visit (pom_packed.h) */

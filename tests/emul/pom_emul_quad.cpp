@@ -285,14 +285,12 @@ extern "C" {
 
 enum { POM_EMUL_QUAD_DIVERGED = 0x40000000u };
 
-/* one tick through pack -> device body, four lanes per env -> unpack; same contract as pom_emul_step (pom_emul.cpp) plus the
- * POM_EMUL_QUAD_DIVERGED bit when the quad model's checks fail */
-uint32_t pom_emul_quad_step(void* state_1004, const int32_t* moves, int env_mode, int max_steps, uint32_t* status_io)
+/* the tick on a record that stays packed between calls, as a device buffer does (no re-pack: a field may sit beyond what upload
+ * accepts); status_io as below */
+uint32_t pom_emul_quad_step_rec(uint32_t* rec, const int32_t* moves, int env_mode, int max_steps, uint32_t* status_io)
 {
     static Workers workers;
     static Quad q; /* one call at a time (the tests are single-threaded) */
-    uint32_t rec[POM_REC_DWORDS];
-    if (pom_pack_state((const int32_t*)state_1004, rec, 1)) return 0xFFFFFFFFu;
     std::memset(q.mem, 0, sizeof q.mem);
     std::memset(q.kind, 0, sizeof q.kind);
     std::memset(q.n_dirty, 0, sizeof q.n_dirty);
@@ -338,12 +336,41 @@ uint32_t pom_emul_quad_step(void* state_1004, const int32_t* moves, int env_mode
         rec[POM_REC_BOMBS + k] = (uint32_t)q.mem[A_BOMB + k];
         rec[POM_REC_FLAMES + k] = (uint32_t)q.mem[A_FLAME + k];
     }
-    int32_t out[251];
-    std::memset(out, 0, sizeof out);
-    pom_unpack_state(rec, 1, out);
-    std::memcpy(state_1004, out, POM_STATE_BYTES);
     if (status_io) *status_io = status;
     return L.ub | extra;
 }
 
+/* one tick through pack -> device body, four lanes per env -> unpack; same contract as pom_emul_step (pom_emul.cpp) plus the
+ * POM_EMUL_QUAD_DIVERGED bit when the quad model's checks fail */
+uint32_t pom_emul_quad_step(void* state_1004, const int32_t* moves, int env_mode, int max_steps, uint32_t* status_io)
+{
+    uint32_t rec[POM_REC_DWORDS];
+    if (pom_pack_state((const int32_t*)state_1004, rec, 1)) return 0xFFFFFFFFu;
+    const uint32_t ub = pom_emul_quad_step_rec(rec, moves, env_mode, max_steps, status_io);
+    int32_t out[251];
+    std::memset(out, 0, sizeof out);
+    pom_unpack_state(rec, 1, out);
+    std::memcpy(state_1004, out, POM_STATE_BYTES);
+    return ub;
+}
+
+}
+
+extern "C" uint32_t pom_emul_step_rec(uint32_t* rec, const int32_t* moves, int env_mode, int max_steps, uint32_t* status_io); /* pom_emul.cpp */
+
+/* T ticks of one env on a record packed ONCE (the way the device keeps it), one lane or four per env: the unpacked state after
+ * every tick into states_out[T] (1004 bytes each), the tick's flags into ubs_out[T].  Returns 0, or -1 if the start state is not
+ * representable. */
+extern "C" int pom_emul_run(const void* state_1004, const int32_t* moves, int ticks, int quad, void* states_out, uint32_t* ubs_out)
+{
+    uint32_t rec[POM_REC_DWORDS];
+    if (pom_pack_state((const int32_t*)state_1004, rec, 1)) return -1;
+    for (int t = 0; t < ticks; t++) {
+        ubs_out[t] = quad ? pom_emul_quad_step_rec(rec, moves + 4 * t, 0, 0, nullptr) : pom_emul_step_rec(rec, moves + 4 * t, 0, 0, nullptr);
+        int32_t out[251];
+        std::memset(out, 0, sizeof out);
+        pom_unpack_state(rec, 1, out);
+        std::memcpy((char*)states_out + (size_t)t * POM_STATE_BYTES, out, POM_STATE_BYTES);
+    }
+    return 0;
 }

@@ -34,20 +34,30 @@ def emul_bins():
     return lib
 
 
-@pytest.mark.parametrize("scenario", [0, 1, 2, 3])
+def _over20(stdout):
+    """ticks of the run with more than 20 flames queued (emul_fuzz's summary line)"""
+    import re
+    return int(re.search(r"(\d+) ticks with > 20 flames queued", stdout).group(1))
+
+
+@pytest.mark.parametrize("scenario", [0, 1, 2, 3, 4])
 def test_device_tick_body_matches_oracle_under_random_play(emul_bins, scenario):
     out = subprocess.run([os.path.join(BUILD, "emul_fuzz"), str(scenario), "150000", "5"], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout[-3000:]
     assert "0 mismatches" in out.stdout
+    if scenario == 4:  # the scenario is there to queue more than 20 flames
+        assert _over20(out.stdout) > 0, out.stdout
 
 
-@pytest.mark.parametrize("scenario", [0, 1, 2, 3])
+@pytest.mark.parametrize("scenario", [0, 1, 2, 3, 4])
 def test_quad_tick_body_matches_oracle_under_random_play(emul_bins, scenario):
     """the shipped shape, four lanes per env: states equal the oracle's and the lanes never break what the device assumes of them
     (same cross-lane operation reached by all four, no conflicting writes, replicated registers identical)"""
     out = subprocess.run([os.path.join(BUILD, "emul_fuzz"), str(scenario), "60000", "11", "quad"], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout[-3000:]
     assert "0 mismatches" in out.stdout and "four lanes per env" in out.stdout
+    if scenario == 4:
+        assert _over20(out.stdout) > 0, out.stdout
 
 
 def test_pack_unpack_round_trip_and_rejections(emul_bins):
