@@ -60,7 +60,8 @@ typedef struct PomBatchOptions {
                                State, observation and status then show the new episode's first state (status bit "restarted"),
                                the next move is a move for it, and the finished episode's outcome and final State are kept
                                (pom_batch_last_results, pom_batch_download_terminal) until the env finishes again.  The
-                               sequence of states stepped is the same in both modes. */
+                               sequence of states stepped is the same in both modes.  In both modes a restart clears the
+                               env's ubflags (pom_batch_status): they gather the flags of the current episode only. */
     int32_t max_steps;    /* ENV mode: env is done once timeStep reaches this (0 = no limit); StartGame's bound, environment.cpp:71 */
     int64_t env_offset;   /* global index of env 0, keys the synthetic move stream when a job is sharded over GPUs */
     int32_t envs_per_wave; /* 0 = default (16); else 16, 32 or 64 envs per wavefront (results are identical) */

@@ -2,7 +2,7 @@
  * fuzz_policy.c — TEST INFRASTRUCTURE.  Pins the SimpleAgent restatement (pom_policy_oracle.c) against the compiled,
  * unmodified reference agent (oracle/_ref/libpomref.so): four reference SimpleAgents and four restated ones play the same
  * games (ticks by the already pinned pom_oracle_step); every act() must return the same Move and leave the same agent
- * memory.  usage: fuzz_policy <scenario 0..3> <agent-steps> <seed>
+ * memory.  usage: fuzz_policy <scenario 0..4> <agent-steps> <seed>
  */
 #include <stdint.h>
 #include <stdio.h>

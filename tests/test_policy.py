@@ -15,7 +15,7 @@ INC = ["-I" + os.path.join(ROOT, p) for p in ("include", "pomcpp_amd/csrc", "ora
 
 
 @pytest.mark.parametrize("floods", ["one-lane", "quad"])
-@pytest.mark.parametrize("scenario", [1, 2])
+@pytest.mark.parametrize("scenario", [1, 2, 3, 4])
 def test_device_policy_body_matches_oracle_under_play(scenario, floods):
     """floods: the two searches of an act() as one lane runs them (four registers per cell set), or through the quad-word level
     functions the kernels' wave-cooperative floods are made of (pom_quad_*_level, pom_window_word)"""

@@ -343,3 +343,78 @@ def test_edges_gpu_observation_of_the_corpus(hip_lib, gpu_batch, dtype):
                         assert np.array_equal(attrs.cpu().numpy(), want_attrs)
             if t < len(moves):
                 env.step(moves[t])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["at_start", "at_end"])
+def test_edges_gpu_env_auto_reset_every_tick(hip_lib, oracle, gpu_batch, mode):
+    """ENV mode with auto-reset and max_steps 23: entries finish by their scripts or are cut in the middle of them, restart from
+    their start states and play on (the moves of tick t are row t of the padded scripts, whichever episode it falls in).  The
+    model: oracle.env_step, and the start state on a restart.  Every tick: the states, ubflags (they gather the flags of the
+    current episode: a restart clears them, pom_batch.h), done / winner, with RESET_AT_END the finished marks, last results and
+    terminal states; at the end the step, episode and reset counters."""
+    from pomcpp_amd.batch import (CNT_EPISODES, CNT_RESETS, CNT_STEPS, MODE_ENV, RESET_AT_END, RESET_AT_START,
+                                  BatchEnvironment)
+    names, start, moves, _, _ = gpu_batch
+    n, cap, T = len(names), 23, 100
+    at_end = mode == "at_end"
+    ref = start.copy()
+    status = [dict(done=0, winner=-1, draw=0) for _ in range(n)]
+    acc = np.zeros(n, dtype=np.uint32)  # the current episode's flags
+    term, term_acc = np.zeros(n, dtype=STATE_DTYPE), np.zeros(n, dtype=np.uint32)
+    last = dict(winner=np.full(n, -1), draw=np.zeros(n, int), length=np.zeros(n, int), alive=np.zeros(n, int))
+    finished_total = restarts = 0
+    fin_prev = np.zeros(n, dtype=bool)
+
+    def compare(what, t, k, got, want, ub_acc):
+        g, w = np.frombuffer(got.tobytes(), np.uint8), np.frombuffer(want.tobytes(), np.uint8)
+        end = QUEUE_BYTES.start if ub_acc & UB_FLAME_QUEUE_RANGE else 1004
+        diff = np.nonzero(g[:end] != w[:end])[0]
+        assert diff.size == 0, f"{names[k]} (env {k}) tick {t}: {what} bytes {diff[:12].tolist()} differ"
+
+    with BatchEnvironment(n, mode=MODE_ENV, auto_reset=RESET_AT_END if at_end else RESET_AT_START, max_steps=cap) as env:
+        env.make_game(start)
+        for t in range(T):
+            mv = moves[t % len(moves)]
+            fin = np.zeros(n, dtype=bool)
+            for k in range(n):
+                if not at_end and fin_prev[k]:  # RESET_AT_START: the tick first puts the env back on its start state
+                    ref[k] = start[k]
+                    status[k] = dict(done=0, winner=-1, draw=0)
+                    acc[k] = 0
+                    restarts += 1
+                acc[k] |= oracle.env_step(ref[k:k + 1], mv[k], status[k])
+                fin[k] = bool(status[k]["done"]) or int(ref["timeStep"][k]) >= cap
+                if fin[k] and at_end:
+                    last["winner"][k], last["draw"][k] = status[k]["winner"], status[k]["draw"]
+                    last["length"][k], last["alive"][k] = ref["timeStep"][k], ref["aliveAgents"][k]
+                    ref["agents"]["pad"][k] = 0
+                    term[k], term_acc[k] = ref[k], acc[k]
+                    ref[k] = start[k]
+                    status[k] = dict(done=0, winner=-1, draw=0)
+                    acc[k] = 0
+                    restarts += 1
+            ref["agents"]["pad"] = 0
+            finished_total += int(fin.sum())
+            fin_prev = fin
+            env.step(mv)
+            got, st = env.get_state(), env.status()
+            for k in range(n):
+                compare("state", t, k, got[k], ref[k], acc[k])
+            assert st["ubflags"].tolist() == acc.tolist(), f"tick {t}: ubflags"
+            if at_end:
+                r = env.last_results()
+                assert r["finished"].astype(bool).tolist() == fin.tolist(), f"tick {t}: finished"
+                for key in ("winner", "draw", "length", "alive"):
+                    assert r[key].tolist() == last[key].tolist(), (t, key)
+                assert not st["done"].any()
+                gt = env.get_terminal_state()
+                for k in np.nonzero(fin)[0]:
+                    compare("terminal state", t, k, gt[k], term[k], term_acc[k])
+            else:
+                assert st["done"].astype(bool).tolist() == fin.tolist(), f"tick {t}: done"
+                assert st["winner"].tolist() == [s["winner"] for s in status], f"tick {t}: winner"
+        cnt = env.counters()
+    assert finished_total > n and restarts > n
+    assert cnt[CNT_STEPS] == n * T
+    assert cnt[CNT_EPISODES] == finished_total and cnt[CNT_RESETS] == restarts
