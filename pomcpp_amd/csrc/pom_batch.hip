@@ -240,7 +240,7 @@ int pom_batch_create(PomBatch** out, int64_t n_envs, const PomBatchOptions* opts
     }
     /* chained launches: the tiles' words and the probe of the workgroup -> XCD pattern, here rather than in the first step (the
      * probe synchronises the stream); where they cannot be had the handle launches sub-batches */
-    if (h->issue_mode == POM_ISSUE_CHAIN && h->quad && h->chain_parts > 1) {
+    if (chains(h)) {
         if (!chain_setup(&h->chain, h->n_pad / h->epw, h->stream) && getenv("POM_CHAIN_VERBOSE"))
             fprintf(stderr, "pom: chained launches are not available on this device (allocation failed or the workgroup -> XCD probe did not find the "
                             "eight-XCD round-robin); launching sub-batches\n");
@@ -434,7 +434,7 @@ int pom_batch_step_device_many(PomBatch* h, const int32_t* moves_dev, int32_t ti
     /* chained where the handle chains: one launch over all tiles per tick, the launches on different streams, a tile's visitor at
      * distance d from the call's first visit reads tick d of the tape (pom_chain.h).  Elsewhere, and for a single tick: plain
      * launches in a row on the caller's stream, as pom_batch_step_device. */
-    if (ticks >= 2 && runs_chain(h, false, 1)) {
+    if (ticks >= 2 && runs_chain(h, 1)) {
         StepParams p;
         memset(&p, 0, sizeof p);
         if (int rc = fill_params(h, p, moves_dev, 0, 0, 1)) return rc;
@@ -774,17 +774,11 @@ int pom_batch_step_device_range(PomBatch* h, int64_t first, int64_t count, const
     HIPCHK(hipSetDevice(h->device));
     if (int qr = quiesce(h)) return qr; /* (free, and no runtime call at all, once the handle is settled: what a graph capture needs) */
     StepParams p;
-    if (int fr = fill_params(h, p, moves_dev, 0, 0, 1)) return fr;
-    if (planes_dev) {
-        p.obs_planes = planes_dev;
-        p.obs_agent_attrs = agent_attrs_dev;
-        p.obs_env_attrs = env_attrs_dev;
-        p.obs_dtype = dtype;
-        p.obs_per_agent = per_agent ? 1 : 0;
-    }
+    const PomObserveOut obs = {planes_dev, agent_attrs_dev, env_attrs_dev, dtype, per_agent ? 1 : 0};
+    if (int fr = fill_params(h, p, moves_dev, 0, 0, 1, planes_dev ? &obs : nullptr)) return fr;
     p.block0 = first / 16;
     p.block_end = (first + count + 15) / 16;
-    const void* kernel = planes_dev ? step_observe_kernel_for(h) : step_kernel_for(h, false, true);
+    const void* kernel = reinterpret_cast<const void*>(step_kernel(h, false, 1, false, planes_dev != nullptr));
     void* args[1] = {&p};
     HIPCHK(hipLaunchKernel(kernel, dim3((unsigned)((p.block_end - p.block0 + POM_WPB - 1) / POM_WPB)), dim3(64 * POM_WPB), args, 0,
                            stream ? (hipStream_t)stream : h->stream));
@@ -1084,16 +1078,16 @@ int pom_batch_launch_shape(PomBatch* h, int32_t* envs_per_wave, int32_t* lanes_p
     if (!h) return POM_E_ARG;
     if (envs_per_wave) *envs_per_wave = h->epw;
     if (lanes_per_env) *lanes_per_env = h->quad ? 4 : 1;
-    if (launches_per_step) *launches_per_step = runs_chain(h, false, 1) ? 1 : h->parts; /* chained: one launch over all tiles per tick */
+    if (launches_per_step) *launches_per_step = runs_chain(h, 1) ? 1 : h->parts; /* chained: one launch over all tiles per tick */
     return POM_OK;
 }
 
 int pom_batch_issue_info(PomBatch* h, int32_t* issue_mode, int32_t* streams)
 {
     if (!h) return POM_E_ARG;
-    const bool chains = runs_chain(h, false, 1);
-    if (issue_mode) *issue_mode = h->issue_mode == POM_ISSUE_CHAIN && !chains ? POM_ISSUE_THREADS : h->issue_mode;
-    if (streams) *streams = !chains ? h->parts : h->chain_auto ? h->chain_last_use : h->chain_parts;
+    const bool chained = runs_chain(h, 1);
+    if (issue_mode) *issue_mode = h->issue_mode == POM_ISSUE_CHAIN && !chained ? POM_ISSUE_THREADS : h->issue_mode;
+    if (streams) *streams = !chained ? h->parts : h->chain_auto ? h->chain_last_use : h->chain_parts;
     return POM_OK;
 }
 

@@ -1214,7 +1214,7 @@ __global__ __launch_bounds__(64 * POM_WPB, (POLICY ? 4 : G == 4 ? POM_QUAD_WAVES
     /* the first tick's moves do not depend on the record: hash / fetch them while the record is on its way */
     uint64_t draw0 = 0;
     int4 moves0 = make_int4(0, 0, 0, 0);
-    /* explicit moves come one tick per launch: the several-tick quad kernel never sees any (step_kernel_for) */
+    /* explicit moves come one tick per launch: the several-tick quad kernel never sees any (step_kernel) */
     constexpr bool TAKES_MOVES = SINGLE || G == 1;
     if (!POLICY) {
         if (TAKES_MOVES && p.moves) {

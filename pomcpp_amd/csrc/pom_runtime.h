@@ -38,7 +38,7 @@ struct PomBatch {
     bool own_stream = false;
     int64_t n = 0, n_pad = 0, n_waves = 0, env_offset = 0; /* n_waves: counter slots, sized for the smallest EPW */
     int epw = 64;
-    bool quad = false; /* EPW 16 with four lanes per env (pom_step_kernel<16, 4>) */
+    bool quad = false; /* EPW 16 with four lanes per env (pom_step_kernel's G = 4) */
     int mode = POM_MODE_ENV, auto_reset = 0, max_steps = 0;
     uint32_t* state = nullptr;
     uint32_t* snap = nullptr;       /* restart snapshot, array of structs */
@@ -73,8 +73,8 @@ struct PomBatch {
     /* how the launches of a several-tick call are issued (launch_many; PomBatchOptions.issue_mode) */
     int issue_mode = POM_ISSUE_THREADS;
     struct PomIssuer* issuers[MAX_PARTS] = {}; /* POM_ISSUE_THREADS: one helper thread per sub-stream part, created on first use */
-    bool issuers_failed = false;
-    int last_kind = 0;                         /* what has been launched on the streams since they were forked: POM_KIND_SPLIT / _CHAIN */               /* a helper thread could not be started: the calling thread issues everything */
+    bool issuers_failed = false;               /* a helper thread could not be started: the calling thread issues the rest */
+    int last_kind = 0;                         /* what has been launched on the streams since they were forked: POM_KIND_SPLIT / _CHAIN */
     /* POM_ISSUE_GRAPH: multi-tick calls replay a captured chunk of launches (launch_many): POM_GRAPH_TICKS launches of every part as one HIP
      * graph per part.  tick_words[k] is the tick part k's replay starts at, read by the graph's kernels (StepParams.tick_base;
      * set by a one-lane kernel on the part's stream in front of each replay); tick_words[MAX_PARTS] stays 0 and is what every
@@ -134,14 +134,34 @@ static int ensure_sub_streams(PomBatch* h, int parts)
     return POM_OK;
 }
 
-static bool runs_fresh(const PomBatch* h);
-static bool runs_at_end(const PomBatch* h);
+/* the handle issues its several-tick calls as chained launches (pom_chain.h) where they can be had: what it was created for */
+static bool chains(const PomBatch* h) { return h->issue_mode == POM_ISSUE_CHAIN && h->quad && h->chain_parts > 1; }
+/* ... and this call can: one tick per launch, and the chain set up (or not yet tried) */
+static bool runs_chain(const PomBatch* h, int ticks_per_launch)
+{
+    return chains(h) && ticks_per_launch == 1 && !(h->chain.tried && !h->chain.ok);
+}
+
 /* how many streams launches of a kind use: the sub-batch parts, or the streams chained launches rotate over (kind 0: what the
  * handle's several-tick calls will mostly be) */
 static int streams_for(const PomBatch* h, int kind)
 {
-    const bool chains = h->issue_mode == POM_ISSUE_CHAIN && h->quad && h->chain_parts > 1;
-    return kind == POM_KIND_CHAIN || (kind == 0 && chains) ? h->chain_parts : h->parts;
+    return kind == POM_KIND_CHAIN || (kind == 0 && chains(h)) ? h->chain_parts : h->parts;
+}
+
+/* The part plan of a sub-batch step: part k of `parts` covers the step kernel's tiles [*b0, *b1) (false: none) and runs on the
+ * caller's stream (part 0 of a split step, main_part) or on sub-stream k.  Chained launches take stream k of the `parts` streams
+ * they rotate over the same way. */
+static bool part_tiles(const PomBatch* h, int k, int parts, int64_t* b0, int64_t* b1)
+{
+    const int64_t tiles = h->n_pad / h->epw;
+    *b0 = tiles * k / parts;
+    *b1 = tiles * (k + 1) / parts;
+    return *b1 > *b0;
+}
+static hipStream_t part_stream(const PomBatch* h, int k, int parts)
+{
+    return parts == 1 || k < h->main_part ? h->stream : h->sub[k];
 }
 
 /* caller's stream -> sub-streams: everything already queued on the caller's stream happens before the parts.  Streams are
@@ -187,7 +207,14 @@ static int ensure_agent_mem(PomBatch* h)
     return POM_OK;
 }
 
-static int fill_params(PomBatch* h, StepParams& p, const int32_t* moves_dev, uint64_t seed, int dist, int ticks)
+struct PomObserveOut { /* pom_batch_step_device_observe / _range: where the fused kernel writes the observation */
+    void* planes;
+    int32_t* agent_attrs;
+    int32_t* env_attrs;
+    int32_t dtype, per_agent;
+};
+static int fill_params(PomBatch* h, StepParams& p, const int32_t* moves_dev, uint64_t seed, int dist, int ticks,
+                       const PomObserveOut* obs = nullptr)
 {
     p.agent_mem = h->agent_mem;
     p.state = h->state;
@@ -219,9 +246,11 @@ static int fill_params(PomBatch* h, StepParams& p, const int32_t* moves_dev, uin
     p.tape_len = 0;
     p.chain_wait_limit = 0;
     p.chain_rot = 0;
-    p.obs_planes = nullptr;
-    p.obs_agent_attrs = p.obs_env_attrs = nullptr;
-    p.obs_dtype = p.obs_per_agent = 0;
+    p.obs_planes = obs ? obs->planes : nullptr;
+    p.obs_agent_attrs = obs ? obs->agent_attrs : nullptr;
+    p.obs_env_attrs = obs ? obs->env_attrs : nullptr;
+    p.obs_dtype = obs ? obs->dtype : 0;
+    p.obs_per_agent = obs ? obs->per_agent : 0;
 #if defined(POM_DIAG)
     if (!h->diag) {
         HIPCHK(hipMalloc((void**)&h->diag, (size_t)h->n_waves * POM_PH_N * 8));
@@ -232,10 +261,13 @@ static int fill_params(PomBatch* h, StepParams& p, const int32_t* moves_dev, uin
     return POM_OK;
 }
 
-/* Which instantiation of pom_step_kernel the handle runs.  Quad shape (the default): one instantiation per combination of
- * fresh boards / fused policy / reset at the end for launches of ONE tick, and the plain replay kernel for launches of
- * several ticks — the other several-tick combinations would need more than the 128 VGPRs that keep four wavefronts on a SIMD
- * (12-116 B of scratch each, round 2), so those modes always run one tick per launch (max_ticks_per_launch). */
+/* Which instantiation of pom_step_kernel a launch runs: the one table of them.  Quad shape (the default): one instantiation per
+ * combination of fresh boards / fused policy / reset at the end for launches of ONE tick — plain, chained (pom_chain.h; the plain
+ * one with the same flags is its twin, what chain_settle replays a tick with) and, for explicit moves, with the fused observation —
+ * and the plain replay kernel for launches of several ticks: the other several-tick combinations would need more than the 128 VGPRs
+ * that keep four wavefronts on a SIMD (12-116 B of scratch each, round 2), so those modes always run one tick per launch
+ * (max_ticks_per_launch).  The one-lane-per-env shapes: fresh boards or not.  Combinations without a kernel of their own are kept
+ * away by max_ticks_per_launch, runs_chain and pom_batch_create. */
 typedef void (*PomStepKernel)(StepParams);
 static bool runs_fresh(const PomBatch* h) { return h->fresh && h->mode == POM_MODE_ENV && h->auto_reset; }
 static bool runs_at_end(const PomBatch* h) { return h->auto_reset == POM_RESET_AT_END && h->mode == POM_MODE_ENV; }
@@ -243,114 +275,75 @@ static int max_ticks_per_launch(const PomBatch* h, bool policy)
 {
     return (!h->quad || (!policy && !runs_fresh(h) && !runs_at_end(h))) ? INT_MAX : 1;
 }
-static const void* step_kernel_for(const PomBatch* h, bool policy, bool one_tick)
+static PomStepKernel step_kernel(const PomBatch* h, bool policy, int ticks_per_launch, bool chained, bool observe)
 {
-    const bool fresh = runs_fresh(h), at_end = runs_at_end(h); /* at_end, policy: quad shape only, checked by the callers */
-    PomStepKernel k;
-    if (h->quad) {
-        static const PomStepKernel single[8] = {
-            pom_step_kernel<16, 4, false, false, false, true>, pom_step_kernel<16, 4, false, false, true, true>,
-            pom_step_kernel<16, 4, false, true, false, true>,  pom_step_kernel<16, 4, false, true, true, true>,
-            pom_step_kernel<16, 4, true, false, false, true>,  pom_step_kernel<16, 4, true, false, true, true>,
-            pom_step_kernel<16, 4, true, true, false, true>,   pom_step_kernel<16, 4, true, true, true, true>};
-        k = one_tick ? single[(fresh ? 4 : 0) | (policy ? 2 : 0) | (at_end ? 1 : 0)] : pom_step_kernel<16, 4, false, false, false, false>;
-    } else if (h->epw == 64) {
-        k = fresh ? pom_step_kernel<64, 1, true> : pom_step_kernel<64, 1, false>;
-    } else if (h->epw == 32) {
-        k = fresh ? pom_step_kernel<32, 1, true> : pom_step_kernel<32, 1, false>;
-    } else {
-        k = fresh ? pom_step_kernel<16, 1, true> : pom_step_kernel<16, 1, false>;
-    }
-    return reinterpret_cast<const void*>(k);
+    /* (listed in the order the kernels have always been emitted in: the order reaches the register allocation — 118 instead of
+     * 119 VGPRs for the fresh-board kernel of 16 envs per wavefront, one lane each, when listed otherwise) */
+    static const struct {
+        PomStepKernel one_tick[8];    /* [fresh * 4 + policy * 2 + at_end] */
+        PomStepKernel several_ticks;
+        PomStepKernel one_lane[3][2]; /* [64 / 32 / 16 envs per wavefront][fresh ? 0 : 1] */
+        PomStepKernel observe[4];     /* [fresh * 2 + at_end] (explicit moves: no policy) */
+        PomStepKernel chained[8];     /* as one_tick */
+    } k = {
+        {pom_step_kernel<16, 4, false, false, false, true>, pom_step_kernel<16, 4, false, false, true, true>,
+         pom_step_kernel<16, 4, false, true, false, true>, pom_step_kernel<16, 4, false, true, true, true>,
+         pom_step_kernel<16, 4, true, false, false, true>, pom_step_kernel<16, 4, true, false, true, true>,
+         pom_step_kernel<16, 4, true, true, false, true>, pom_step_kernel<16, 4, true, true, true, true>},
+        pom_step_kernel<16, 4, false, false, false, false>,
+        {{pom_step_kernel<64, 1, true>, pom_step_kernel<64, 1, false>},
+         {pom_step_kernel<32, 1, true>, pom_step_kernel<32, 1, false>},
+         {pom_step_kernel<16, 1, true>, pom_step_kernel<16, 1, false>}},
+        {pom_step_kernel<16, 4, false, false, false, true, false, true>, pom_step_kernel<16, 4, false, false, true, true, false, true>,
+         pom_step_kernel<16, 4, true, false, false, true, false, true>, pom_step_kernel<16, 4, true, false, true, true, false, true>},
+        {pom_step_kernel<16, 4, false, false, false, true, true>, pom_step_kernel<16, 4, false, false, true, true, true>,
+         pom_step_kernel<16, 4, false, true, false, true, true>, pom_step_kernel<16, 4, false, true, true, true, true>,
+         pom_step_kernel<16, 4, true, false, false, true, true>, pom_step_kernel<16, 4, true, false, true, true, true>,
+         pom_step_kernel<16, 4, true, true, false, true, true>, pom_step_kernel<16, 4, true, true, true, true, true>}};
+    const int fresh = runs_fresh(h) ? 1 : 0, at_end = runs_at_end(h) ? 1 : 0;
+    if (!h->quad) return k.one_lane[h->epw == 64 ? 0 : h->epw == 32 ? 1 : 2][1 - fresh];
+    if (observe) return k.observe[2 * fresh + at_end];
+    if (ticks_per_launch != 1) return k.several_ticks;
+    return (chained ? k.chained : k.one_tick)[4 * fresh + (policy ? 2 : 0) + at_end];
 }
 
-/* the one-tick kernel that also writes the observation of the state it leaves behind (explicit moves, quad shape) */
-static const void* step_observe_kernel_for(const PomBatch* h)
-{
-    static const PomStepKernel k[4] = {
-        pom_step_kernel<16, 4, false, false, false, true, false, true>, pom_step_kernel<16, 4, false, false, true, true, false, true>,
-        pom_step_kernel<16, 4, true, false, false, true, false, true>,  pom_step_kernel<16, 4, true, false, true, true, false, true>};
-    return reinterpret_cast<const void*>(k[(runs_fresh(h) ? 2 : 0) | (runs_at_end(h) ? 1 : 0)]);
-}
-
-/* one dispatch of the step kernel the handle is configured for, over tiles [p.block0, p.block_end) */
-static hipError_t dispatch_step(const PomBatch* h, const StepParams& p, hipStream_t st, bool policy, hipEvent_t ev0, hipEvent_t ev1)
-{
-    const dim3 grid((unsigned)((p.block_end - p.block0 + POM_WPB - 1) / POM_WPB));
-    StepParams q = p;
-    void* args[1] = {&q};
-    const void* kernel = p.obs_planes ? step_observe_kernel_for(h) : step_kernel_for(h, policy, p.ticks == 1);
-    return hipExtLaunchKernel(kernel, grid, dim3(64 * POM_WPB), args, 0, st, ev0, ev1, 0);
-}
-
-/* `one_launch`: the whole batch in ONE launch on the caller's stream.  For steps that have to be joined with the caller's stream
- * every tick (explicit moves): forking into sub-streams and joining them again costs more than the overlap gains
- * (65,536 envs, MI355X: 23.3 us per step as one launch, 43.8 as two, 60.2 as three; profiles/r02a_explicit_streams.txt). */
-struct PomObserveOut { /* pom_batch_step_device_observe: where the fused kernel writes the observation */
-    void* planes;
-    int32_t* agent_attrs;
-    int32_t* env_attrs;
-    int32_t dtype, per_agent;
-};
-static int launch_step(PomBatch* h, const int32_t* moves_dev, uint64_t seed, int dist, int ticks, bool policy = false, bool one_launch = false,
-                       const PomObserveOut* obs = nullptr)
-{
+/* A run: `count` launches of one kernel on one stream — a sub-batch part's, or those a chained call deals to one of its streams.
+ * Launch j of the run is the call's launch i = first + j * stride, with the parameters `p` but for the tick, advanced by
+ * i * tick_step (sub-batches: the ticks per launch; a chained launch keeps it, its tickets decide which tick it plays), and, where
+ * rot_mod is set, chain_rot = (rot0 + i) * rot_mul % rot_mod (the rotation of launch_many_chain). */
+struct PomRun {
+    PomStepKernel kernel = nullptr;
+    unsigned grid = 0;
+    int part = 0; /* the stream's index (part_stream; its helper: issuer_for) */
+    hipStream_t st = nullptr;
     StepParams p;
-    if (int rc = chain_settle(h)) return rc; /* an ordinary launch after chained ones: every tile must stand on the tick the host thinks it does */
-    if (int rc = fill_params(h, p, moves_dev, seed, dist, ticks)) return rc;
-    if (obs) {
-        p.obs_planes = obs->planes;
-        p.obs_agent_attrs = obs->agent_attrs;
-        p.obs_env_attrs = obs->env_attrs;
-        p.obs_dtype = obs->dtype;
-        p.obs_per_agent = obs->per_agent;
-    }
-    const int64_t tiles = h->n_pad / h->epw;
-    const int parts = one_launch ? 1 : h->parts;
-    int rc = one_launch ? join_parts(h) : fork_parts(h);
-    if (rc) return rc;
-    for (int k = 0; k < parts; k++) {
-        const int64_t b0 = tiles * k / parts, b1 = tiles * (k + 1) / parts;
-        if (b1 <= b0) continue;
-        hipStream_t st = (parts == 1 || k < h->main_part) ? h->stream : h->sub[k];
-        p.block0 = b0;
-        p.block_end = b1;
-        /* per-launch timing (pom_batch_profile): start / stop events attached to the dispatch itself, i.e. the kernel's own
-         * duration as a profiler reports it, not the stream's period (events recorded around a launch also time the gap) */
-        const bool prof = h->profiling && h->prof_n < PomBatch::PROF_RING;
+    int first = 0, stride = 1, count = 0;
+    uint32_t tick_step = 0;
+    uint32_t rot0 = 0, rot_mul = 0, rot_mod = 0;
+};
+
+/* launches [from, to) of a run, from whichever thread holds it; *queued counts what was queued.  timed: while profiling
+ * (pom_batch_profile), start / stop events attached to the dispatch itself, i.e. the kernel's own duration as a profiler reports
+ * it, not the stream's period (events recorded around a launch also time the gap) */
+static hipError_t issue_run(PomBatch* h, const PomRun& r, int from, int to, bool timed, int* queued)
+{
+    for (int j = from; j < to; j++) {
+        const uint32_t i = (uint32_t)(r.first + j * r.stride);
+        StepParams q = r.p;
+        q.tick0 += i * r.tick_step;
+        if (r.rot_mod) q.chain_rot = (uint32_t)((uint64_t)(r.rot0 + i) * r.rot_mul % r.rot_mod);
+        const bool prof = timed && h->profiling && h->prof_n < PomBatch::PROF_RING;
         hipEvent_t ev0 = prof ? h->prof_ev[2 * h->prof_n] : nullptr, ev1 = prof ? h->prof_ev[2 * h->prof_n + 1] : nullptr;
-        HIPCHK(dispatch_step(h, p, st, policy, ev0, ev1));
+        void* args[1] = {&q};
+        const hipError_t e = hipExtLaunchKernel(reinterpret_cast<const void*>(r.kernel), dim3(r.grid), dim3(64 * POM_WPB), args, 0, r.st, ev0, ev1, 0);
+        if (e != hipSuccess) return e;
         if (prof) h->prof_n++;
+        ++*queued;
     }
-    return POM_OK;
+    return hipSuccess;
 }
 
-/* ---- several ticks in one call ---------------------------------------------------------------------------------------------
- * The default up to 196,608 envs is POM_ISSUE_CHAIN (launch_many_chain below, pom_chain.h): one launch over all tiles per tick,
- * consecutive launches on different streams, a ticket word per tile ordering the tile's ticks — 9.2 us per step at 65,536 envs
- * where sub-batches take 14.5.  What follows is how SUB-BATCH launches are issued: what a handle does where launches are not
- * chained (several ticks per launch, batches from 196,608 envs up, the one-lane-per-env shapes, a handle asked for another mode).
- * A step is then `parts` launches (one per sub-batch, on parallel streams) every ~16 us at 65,536 envs: the host has ~5 us per
- * launch, and a call of K ticks is judged by how soon all parts' first launches are out and whether the queues stay fed.
- * Three ways to issue them (PomBatchOptions.issue_mode; results cannot depend on the choice: the same kernels with the same
- * arguments go to the same streams in the same per-stream order).  Measured on MI355X, 65,536 envs, 3 parts, per step
- * (profiles/r03_issue_modes.txt):
- *                                   20-tick call from an idle device (the bench driver's shape)      500-tick call
- *   POM_ISSUE_THREADS               18.0 us, run to run the same                                      15.5 us
- *   POM_ISSUE_DIRECT                17.2 .. 26.4 us: one thread issues all 60 launches (2.8 us each   15.6 - 16.0 us
- *                                   on a quiet host, then it is ahead of the device; on a busy one it is not)
- *   POM_ISSUE_GRAPH                 21.4 .. 23.5 us: queued in 48 us, but the replayed nodes run with   16.1 - 16.2 us
- *                                   wider gaps than plain launches
- * THREADS: part k's launches of ALL the ticks of the call are issued by a helper thread of its own (created on first use, one
- * per sub-stream part; the caller issues every part's first launch and the rest of its own part), the call returns when
- * everything is queued.  A helper that cannot be started is not an error: the calling thread issues its launches.
- * DIRECT: the calling thread issues everything, tick by tick; no library-owned threads.
- * GRAPH: part k's launches of POM_GRAPH_TICKS consecutive ticks are a HIP graph — a plain chain of kernel nodes, built once —
- * replayed on part k's stream with one hipGraphLaunch per part and chunk; no library-owned threads either.  The nodes'
- * arguments never change: a node carries its offset inside the chunk, and the tick the chunk starts at is a device word per
- * part (StepParams.tick_base) that a one-lane kernel sets on the part's stream in front of each replay.  (One graph holding
- * all parts as parallel branches was measured first: this runtime plays the branches one after the other — 18.5 us per step
- * in a 500-tick call.)  Ticks that do not fill a chunk are launched directly. */
+/* a helper thread: issues the launches of one sub-stream that issue_runs hands it */
 struct PomIssuer {
     std::thread th;
     std::mutex mu;
@@ -359,17 +352,10 @@ struct PomIssuer {
     std::atomic<int> posted{0}; /* bumped with every job and by pom_batch_fork: a thread that has just worked (or was told that work
                                    is coming) polls this for up to a millisecond before it goes to sleep on the condition variable
                                    — a futex wake-up costs 10-30 us, a tenth of a 20-step burst */
-    /* the job */
-    StepParams p;
-    hipStream_t st = nullptr;
-    int launches = 0, ticks_per_launch = 1, last_ticks = 1;
-    bool policy = false;
+    /* the job: launches 1 .. run.count - 1 of `run`, and how many of them were queued */
+    PomRun run;
+    int done = 0;
     hipError_t err = hipSuccess;
-    /* a job of chained launches (launch_many_chain): these parameter blocks, one launch each, on `st` */
-    std::vector<StepParams> chain_q;
-    const void* chain_kernel = nullptr;
-    unsigned chain_grid = 0;
-    int chain_done = 0; /* how many of them were queued */
 };
 
 static void issuer_main(PomBatch* h, PomIssuer* w)
@@ -394,30 +380,8 @@ static void issuer_main(PomBatch* h, PomIssuer* w)
         if (w->quit) return;
         if (!w->has_job) continue;
         w->has_job = false;
-        if (w->chain_kernel) { /* chained launches: which launch plays which tick is the tiles' tickets' business, not the order here */
-            hipError_t cerr = hipSuccess;
-            int done = 0;
-            for (StepParams& q : w->chain_q) {
-                void* args[1] = {&q};
-                cerr = hipExtLaunchKernel(w->chain_kernel, dim3(w->chain_grid), dim3(64 * POM_WPB), args, 0, w->st, nullptr, nullptr, 0);
-                if (cerr != hipSuccess) break;
-                done++;
-            }
-            w->chain_done = done;
-            w->chain_kernel = nullptr;
-            w->err = cerr;
-            w->busy = false;
-            w->cv.notify_all();
-            continue;
-        }
-        StepParams p = w->p;
-        hipError_t err = hipSuccess;
-        for (int i = 0; i < w->launches && err == hipSuccess; i++) {
-            p.ticks = i + 1 == w->launches ? w->last_ticks : w->ticks_per_launch;
-            err = dispatch_step(h, p, w->st, w->policy, nullptr, nullptr);
-            p.tick0 += (uint32_t)w->ticks_per_launch;
-        }
-        w->err = err;
+        w->done = 0;
+        w->err = issue_run(h, w->run, 1, w->run.count, false, &w->done);
         w->busy = false;
         w->cv.notify_all();
     }
@@ -439,6 +403,117 @@ static void stop_issuers(PomBatch* h)
     }
 }
 
+/* the helper of sub-stream k, started on first use; nullptr if it cannot be had (the caller then issues that stream's launches) */
+static PomIssuer* issuer_for(PomBatch* h, int k)
+{
+    if (h->issuers[k] || h->issuers_failed) return h->issuers[k];
+    PomIssuer* w = new (std::nothrow) PomIssuer();
+    if (w) {
+        try {
+            w->th = std::thread(issuer_main, h, w);
+        } catch (...) { /* std::system_error: no thread to be had — nothing may cross the C boundary */
+            delete w;
+            w = nullptr;
+        }
+    }
+    if (!w) h->issuers_failed = true;
+    h->issuers[k] = w;
+    return w;
+}
+
+/* Issues `n` runs, at most one per stream, listed in the order of their first launches; returns how many launches were queued,
+ * *err the first failure (a thread issues nothing after its own first failure, nor hands out anything after one).
+ * helpers = false: the calling thread issues everything in launch-number order, round-robin over the runs.
+ * helpers = true: the first launch of EVERY run is issued right here, the caller's own stream first: a helper thread takes 10-25 us
+ * to pick its job up (profiles/r02_region_trace.txt), and a part that starts a step late finishes a step late — alone on the
+ * device.  The rest of each sub-stream's run goes to that stream's helper thread (issuer_for), which has one step's time to wake
+ * up, while the calling thread issues the rest of its own stream's run (and of any run whose helper could not be started: the only
+ * case in which the order of the launches differs from the helpers' one).  The call returns when everything is queued. */
+static int issue_runs(PomBatch* h, const PomRun* runs, int n, bool helpers, hipError_t* err)
+{
+    int queued = 0;
+    *err = hipSuccess;
+    PomIssuer* started[PomBatch::MAX_PARTS] = {};
+    int j0 = 0;
+    if (helpers) {
+        for (int r = 0; r < n && *err == hipSuccess; r++) *err = issue_run(h, runs[r], 0, runs[r].count > 0 ? 1 : 0, true, &queued);
+        for (int r = 0; r < n && *err == hipSuccess; r++) {
+            if (runs[r].st == h->stream || runs[r].count < 2) continue;
+            PomIssuer* w = issuer_for(h, runs[r].part);
+            if (!w) continue;
+            {
+                std::lock_guard<std::mutex> g(w->mu);
+                w->run = runs[r];
+                w->busy = true;
+                w->has_job = true;
+                w->posted.fetch_add(1, std::memory_order_release);
+            }
+            w->cv.notify_all();
+            started[r] = w;
+        }
+        j0 = 1;
+    }
+    for (int j = j0, more = 1; more && *err == hipSuccess; j++) {
+        more = 0;
+        for (int r = 0; r < n && *err == hipSuccess; r++)
+            if (!started[r] && j < runs[r].count) {
+                *err = issue_run(h, runs[r], j, j + 1, true, &queued);
+                more = 1;
+            }
+    }
+    for (int r = 0; r < n; r++) { /* everything is queued when the call returns */
+        PomIssuer* w = started[r];
+        if (!w) continue;
+        std::unique_lock<std::mutex> lk(w->mu);
+        w->cv.wait(lk, [w] { return !w->busy; });
+        queued += w->done;
+        if (w->err != hipSuccess && *err == hipSuccess) *err = w->err;
+    }
+    return queued;
+}
+
+/* `launches` launches of every sub-batch part, p.ticks ticks each, from p.tick0 on; the caller advances the tick.  `one_launch`: the
+ * whole batch in ONE launch on the caller's stream.  For steps that have to be joined with the caller's stream every tick (explicit
+ * moves): forking into sub-streams and joining them again costs more than the overlap gains (65,536 envs, MI355X: 23.3 us per step
+ * as one launch, 43.8 as two, 60.2 as three; profiles/r02a_explicit_streams.txt).  `threads`: with the helper threads (issue_runs) */
+static int launch_parts(PomBatch* h, const StepParams& p, int launches, bool policy, bool one_launch, bool threads)
+{
+    const int parts = one_launch ? 1 : h->parts;
+    if (int rc = one_launch ? join_parts(h) : fork_parts(h)) return rc;
+    const PomStepKernel kernel = step_kernel(h, policy, p.ticks, false, p.obs_planes != nullptr);
+    PomRun runs[PomBatch::MAX_PARTS];
+    int n = 0;
+    for (int k = 0; k < parts; k++) {
+        int64_t b0, b1;
+        if (!part_tiles(h, k, parts, &b0, &b1)) continue;
+        PomRun& r = runs[n++];
+        r.kernel = kernel;
+        r.grid = (unsigned)((b1 - b0 + POM_WPB - 1) / POM_WPB);
+        r.part = k;
+        r.st = part_stream(h, k, parts);
+        r.p = p;
+        r.p.block0 = b0;
+        r.p.block_end = b1;
+        r.count = launches;
+        r.tick_step = (uint32_t)p.ticks;
+    }
+    hipError_t err = hipSuccess;
+    issue_runs(h, runs, n, threads, &err);
+    if (err != hipSuccess) { /* some launches may be queued, others not: the handle's tick no longer describes its state */
+        set_err("pom_step_kernel launch (the batch is in an undefined state: upload again or destroy it)", err);
+        return POM_E_HIP;
+    }
+    return POM_OK;
+}
+
+static int launch_step(PomBatch* h, const int32_t* moves_dev, uint64_t seed, int dist, int ticks, bool policy = false, bool one_launch = false,
+                       const PomObserveOut* obs = nullptr)
+{
+    StepParams p;
+    if (int rc = chain_settle(h)) return rc; /* an ordinary launch after chained ones: every tile must stand on the tick the host thinks it does */
+    if (int rc = fill_params(h, p, moves_dev, seed, dist, ticks, obs)) return rc;
+    return launch_parts(h, p, 1, policy, one_launch, false);
+}
 
 #ifndef POM_GRAPH_TICKS
 #define POM_GRAPH_TICKS 20
@@ -496,11 +571,10 @@ static PomStepGraph* step_graph(PomBatch* h, const StepParams& p, int launches, 
     g->ticks_per_launch = ticks_per_launch;
     g->policy = policy;
     hipError_t err = hipSuccess;
-    const int64_t tiles = h->n_pad / h->epw;
-    const void* fn = step_kernel_for(h, policy, ticks_per_launch == 1);
+    const PomStepKernel fn = step_kernel(h, policy, ticks_per_launch, false, false);
     for (int k = 0; k < h->parts && err == hipSuccess; k++) {
-        const int64_t b0 = tiles * k / h->parts, b1 = tiles * (k + 1) / h->parts;
-        if (b1 <= b0) continue;
+        int64_t b0, b1;
+        if (!part_tiles(h, k, h->parts, &b0, &b1)) continue;
         err = hipGraphCreate(&g->graph[k], 0);
         hipGraphNode_t prev = nullptr;
         for (int i = 0; i < launches && err == hipSuccess; i++) {
@@ -513,7 +587,7 @@ static PomStepGraph* step_graph(PomBatch* h, const StepParams& p, int launches, 
             void* args[1] = {&q};
             hipKernelNodeParams np;
             memset(&np, 0, sizeof np);
-            np.func = const_cast<void*>(fn);
+            np.func = reinterpret_cast<void*>(fn);
             np.gridDim = dim3((unsigned)((b1 - b0 + POM_WPB - 1) / POM_WPB));
             np.blockDim = dim3(64 * POM_WPB);
             np.kernelParams = args;
@@ -543,128 +617,9 @@ static PomStepGraph* step_graph(PomBatch* h, const StepParams& p, int launches, 
     return g;
 }
 
-/* POM_ISSUE_THREADS: the helper of part k, started on first use; nullptr if it cannot be had (the caller then issues that part) */
-static PomIssuer* issuer_for(PomBatch* h, int k)
-{
-    if (h->issuers[k] || h->issuers_failed) return h->issuers[k];
-    PomIssuer* w = new (std::nothrow) PomIssuer();
-    if (w) {
-        try {
-            w->th = std::thread(issuer_main, h, w);
-        } catch (...) { /* std::system_error: no thread to be had — nothing may cross the C boundary */
-            delete w;
-            w = nullptr;
-        }
-    }
-    if (!w) h->issuers_failed = true;
-    h->issuers[k] = w;
-    return w;
-}
-
-/* THREADS / DIRECT: `launches` dispatches per part; the caller advances the tick */
-static int launch_many_streams(PomBatch* h, const StepParams& p0, int launches, int ticks_per_launch, bool policy, bool threads)
-{
-    StepParams p = p0;
-    const int64_t tiles = h->n_pad / h->epw;
-    const int parts = h->parts;
-    if (int rc = chain_settle(h)) return rc;
-    if (int rc = fork_parts(h)) return rc;
-    hipError_t err = hipSuccess;
-    auto part_launch = [&](int k, const StepParams& base, int count) { /* `count` launches of part k from this thread */
-        const int64_t b0 = tiles * k / parts, b1 = tiles * (k + 1) / parts;
-        if (b1 <= b0) return;
-        StepParams q = base;
-        q.block0 = b0;
-        q.block_end = b1;
-        q.ticks = ticks_per_launch;
-        const bool own = parts == 1 || k < h->main_part;
-        for (int i = 0; i < count && err == hipSuccess; i++) {
-            err = dispatch_step(h, q, own ? h->stream : h->sub[k], policy, nullptr, nullptr);
-            q.tick0 += (uint32_t)ticks_per_launch;
-        }
-    };
-    if (!threads) { /* tick by tick, the caller's own part first */
-        for (int i = 0; i < launches && err == hipSuccess; i++) {
-            for (int k = 0; k < parts; k++) part_launch(k, p, 1);
-            p.tick0 += (uint32_t)ticks_per_launch;
-        }
-    } else {
-        /* The first launch of EVERY part is issued right here, the caller's own part(s) first: a helper thread takes 10-25 us to
-         * pick its job up (profiles/r02_region_trace.txt), and a part that starts a step late finishes a step late — alone on
-         * the device.  The helpers get the remaining launches of their parts and have one step's time to wake up. */
-        for (int pass = 0; pass < 2; pass++)
-            for (int k = 0; k < parts; k++)
-                if ((parts == 1 || k < h->main_part) == (pass == 0)) part_launch(k, p, 1);
-        p.tick0 += (uint32_t)ticks_per_launch;
-        const int rest = launches - 1;
-        PomIssuer* started[PomBatch::MAX_PARTS] = {};
-        for (int k = h->main_part; k < parts && rest > 0 && err == hipSuccess; k++) { /* the sub-stream parts: hand them to their threads */
-            const int64_t b0 = tiles * k / parts, b1 = tiles * (k + 1) / parts;
-            if (b1 <= b0) continue;
-            PomIssuer* w = issuer_for(h, k);
-            if (!w) { /* no helper: this thread does it */
-                part_launch(k, p, rest);
-                continue;
-            }
-            {
-                std::lock_guard<std::mutex> g(w->mu);
-                w->p = p;
-                w->p.block0 = b0;
-                w->p.block_end = b1;
-                w->st = h->sub[k];
-                w->launches = rest;
-                w->ticks_per_launch = ticks_per_launch;
-                w->last_ticks = ticks_per_launch;
-                w->policy = policy;
-                w->err = hipSuccess;
-                w->busy = true;
-                w->has_job = true;
-                w->posted.fetch_add(1, std::memory_order_release);
-            }
-            w->cv.notify_all();
-            started[k] = w;
-        }
-        for (int k = 0; k < (parts == 1 ? 1 : h->main_part) && rest > 0; k++) part_launch(k, p, rest); /* the rest of the caller's own part(s) */
-        for (int k = 0; k < parts; k++) { /* everything is queued when the call returns */
-            PomIssuer* w = started[k];
-            if (!w) continue;
-            std::unique_lock<std::mutex> lk(w->mu);
-            w->cv.wait(lk, [w] { return !w->busy; });
-            if (w->err != hipSuccess && err == hipSuccess) err = w->err;
-        }
-    }
-    if (err != hipSuccess) { /* some launches may be queued, others not: the handle's tick no longer describes its state */
-        set_err("pom_step_kernel launch (the batch is in an undefined state: upload again or destroy it)", err);
-        return POM_E_HIP;
-    }
-    return POM_OK;
-}
-
 #ifndef POM_CHAIN_LONG_CALL
 #define POM_CHAIN_LONG_CALL 50
 #endif
-/* POM_ISSUE_CHAIN (pom_chain.h): `launches` one-tick launches, each over the WHOLE batch, dealt round-robin to the handle's
- * streams; the tiles' ticket words order the ticks.  *used = false: not available for this handle, nothing was launched, the
- * caller takes the ordinary path. */
-static bool runs_chain(const PomBatch* h, bool policy, int ticks_per_launch)
-{
-    (void)policy; /* every one-tick instantiation of the quad shape has its chained twin */
-    return h->issue_mode == POM_ISSUE_CHAIN && h->quad && h->chain_parts > 1 && ticks_per_launch == 1 && !(h->chain.tried && !h->chain.ok);
-}
-static const PomStepKernel* chain_kernels(bool chained)
-{
-    static const PomStepKernel chained_k[8] = {
-        pom_step_kernel<16, 4, false, false, false, true, true>, pom_step_kernel<16, 4, false, false, true, true, true>,
-        pom_step_kernel<16, 4, false, true, false, true, true>,  pom_step_kernel<16, 4, false, true, true, true, true>,
-        pom_step_kernel<16, 4, true, false, false, true, true>,  pom_step_kernel<16, 4, true, false, true, true, true>,
-        pom_step_kernel<16, 4, true, true, false, true, true>,   pom_step_kernel<16, 4, true, true, true, true, true>};
-    static const PomStepKernel plain_k[8] = {
-        pom_step_kernel<16, 4, false, false, false, true>, pom_step_kernel<16, 4, false, false, true, true>,
-        pom_step_kernel<16, 4, false, true, false, true>,  pom_step_kernel<16, 4, false, true, true, true>,
-        pom_step_kernel<16, 4, true, false, false, true>,  pom_step_kernel<16, 4, true, false, true, true>,
-        pom_step_kernel<16, 4, true, true, false, true>,   pom_step_kernel<16, 4, true, true, true, true>};
-    return chained ? chained_k : plain_k;
-}
 
 /* The check behind chained launches, and the recovery (pom_chain.h).  Joins the streams, lists the tiles some visitor could not
  * play (poisoned: their records stand on the last tick they really played), waits for the answer, and plays the missing ticks of
@@ -724,7 +679,10 @@ static int chain_settle(PomBatch* h)
         fprintf(stderr, "pom: chained launches left %u tile(s) behind (flags %u: %s%s%s); replaying their ticks\n", bad, flags,
                 (flags & POM_CHAIN_E_TIMEOUT) ? "a wavefront waited out its limit " : "", (flags & POM_CHAIN_E_XCD) ? "a tile changed its XCD " : "",
                 (flags & POM_CHAIN_E_TAPE) ? "a ticket outside the move tape" : "");
-    const PomStepKernel* plain = chain_kernels(false);
+    PomRun replay; /* one launch of one tile */
+    replay.grid = 1;
+    replay.st = h->stream;
+    replay.count = 1;
     for (uint32_t k = 0; k < bad; k++) {
         const uint32_t tile = list[2 * k], stored = list[2 * k + 1];
         for (uint32_t v = stored; v != c->visits; v++) {
@@ -735,7 +693,8 @@ static int chain_settle(PomBatch* h)
                 snprintf(g_err, sizeof g_err, "a tile left behind by chained launches cannot be replayed: the batch is in an undefined state");
                 return POM_E_HIP;
             }
-            StepParams q = call->p;
+            StepParams& q = replay.p;
+            q = call->p;
             const uint32_t d = v - q.chain_seq0; /* visits after the call's first */
             q.block0 = tile;
             q.block_end = (int64_t)tile + 1;
@@ -747,9 +706,9 @@ static int chain_settle(PomBatch* h)
             q.chain_err = nullptr;
             q.chain_seq0 = 0;
             q.tape_len = 0;
-            const PomStepKernel kernel = plain[(runs_fresh(h) ? 4 : 0) | (call->policy ? 2 : 0) | (runs_at_end(h) ? 1 : 0)];
-            void* args[1] = {&q};
-            HIPCHK(hipExtLaunchKernel(reinterpret_cast<const void*>(kernel), dim3(1), dim3(64 * POM_WPB), args, 0, h->stream, nullptr, nullptr, 0));
+            replay.kernel = step_kernel(h, call->policy, 1, false, false); /* the chained kernel's twin */
+            int queued = 0;
+            HIPCHK(issue_run(h, replay, 0, 1, false, &queued));
             c->stat_ticks_replayed++;
         }
         c->stat_tiles_recovered++;
@@ -798,7 +757,7 @@ static int launch_many_chain(PomBatch* h, const StepParams& p0, int launches, bo
     p.chain_seq0 = c->visits;
     p.tape_len = p.moves ? (uint32_t)launches : 0u;
     p.chain_wait_limit = c->wait_limit;
-    const PomStepKernel kernel = chain_kernels(true)[(runs_fresh(h) ? 4 : 0) | (policy ? 2 : 0) | (runs_at_end(h) ? 1 : 0)];
+    const PomStepKernel kernel = step_kernel(h, policy, 1, true, false);
     /* Launches in flight together must be interchangeable — "the j-th visitor of a tile plays the tile's j-th tick" holds only
      * if every launch would play that tick the same way: the same kernel, seed, move distribution, mode ... and the same offset
      * between ticks and visits.  A call that differs in any of that from the chained launches still in flight waits for them
@@ -816,7 +775,6 @@ static int launch_many_chain(PomBatch* h, const StepParams& p0, int launches, bo
     c->last_key = key;
     c->last_kernel = kernel;
     if (int rc = fork_parts(h, POM_KIND_CHAIN)) return rc;
-    const dim3 grid((unsigned)(((tiles + POM_WPB - 1) / POM_WPB + 7) / 8 * 8)); /* a multiple of 8: every XCD gets as many workgroups as it has tiles */
     /* how many streams: a third launch in flight pays once the pipeline runs and costs while it fills and drains.  65,536 envs, us
      * per step on two / three streams at the round-4 kernels (with the rotation below on two): 30 ticks 10.47 / 11.13, 40 ticks
      * 10.20 / 10.76, 60 ticks 10.05 / 9.72, 100 ticks 9.79 / 9.64, 300 ticks 9.7 / 9.0.  Any mix is fine: the tickets order the
@@ -835,80 +793,29 @@ static int launch_many_chain(PomBatch* h, const StepParams& p0, int launches, bo
     const bool fills_the_chip = c->wave_slots > 0 && tiles <= c->wave_slots && tiles * 4 >= (int64_t)c->wave_slots * 3;
     const uint32_t back = (use == 2 && fills_the_chip && rot_div > 0) ? per_xcd / (uint32_t)rot_div : 0u;
     h->chain_last_use = use;
-    int issued = 0;
-    hipError_t err = hipSuccess;
-    auto params_of = [&](int i) { /* launch number i of the call */
-        StepParams q = p;
-        q.chain_rot = back ? (uint32_t)(((uint64_t)(c->visits + (uint32_t)i) * (uint64_t)(per_xcd - back)) % per_xcd) : 0u;
-        return q;
-    };
-    const uint32_t turn0 = c->turn;
-    auto part_of = [&](int i) { return (int)((turn0 + (uint32_t)i) % (uint32_t)use); };
-    /* Who issues: the first launch of every stream the calling thread, at once; then the sub-streams' remaining launches their helper
-     * threads (the ones sub-batch launches use: created on first use, spinning for a millisecond after pom_batch_fork / a job) while the
-     * calling thread issues its own stream's.  A launch costs the host 2.5 - 3 us, sometimes 6 - 9: with one thread a 20-step call is
+    PomRun runs[PomBatch::MAX_PARTS];
+    for (int r = 0; r < use; r++) { /* the call's launch i goes to stream (turn + i) % use: run r holds launches r, r + use, ... */
+        runs[r].kernel = kernel;
+        runs[r].grid = per_xcd * 8; /* a multiple of 8: every XCD gets as many workgroups as it has tiles */
+        runs[r].part = (int)((c->turn + (uint32_t)r) % (uint32_t)use);
+        runs[r].st = part_stream(h, runs[r].part, use);
+        runs[r].p = p;
+        runs[r].first = r;
+        runs[r].stride = use;
+        runs[r].count = launches > r ? (launches - r + use - 1) / use : 0;
+        runs[r].rot0 = c->visits;
+        runs[r].rot_mul = per_xcd - back;
+        runs[r].rot_mod = back ? per_xcd : 0u;
+    }
+    /* Who issues: with the helper threads (the ones sub-batch launches use: created on first use, spinning for a millisecond after
+     * pom_batch_fork / a job; issue_runs).  A launch costs the host 2.5 - 3 us, sometimes 6 - 9: with one thread a 20-step call is
      * queued in 50 - 60 us on most runs and in 120 - 180 us on one in five, late enough for the device to wait for its launches
      * (profiles/r05_issue_helpers.txt).  Any interleaving is fine: the tiles' tickets order the ticks, not the launches' order. */
     static const bool helpers_on = !(getenv("POM_CHAIN_HELPERS") && atoi(getenv("POM_CHAIN_HELPERS")) == 0);
     const bool helpers = helpers_on && !h->profiling && use >= 2 && launches >= 3 * use && !h->issuers_failed;
-    if (!helpers) {
-        for (; issued < launches; issued++) {
-            const int part = part_of(issued);
-            hipStream_t st = part < h->main_part ? h->stream : h->sub[part];
-            const bool prof = h->profiling && h->prof_n < PomBatch::PROF_RING;
-            hipEvent_t ev0 = prof ? h->prof_ev[2 * h->prof_n] : nullptr, ev1 = prof ? h->prof_ev[2 * h->prof_n + 1] : nullptr;
-            StepParams q = params_of(issued);
-            void* args[1] = {&q};
-            err = hipExtLaunchKernel(reinterpret_cast<const void*>(kernel), grid, dim3(64 * POM_WPB), args, 0, st, ev0, ev1, 0);
-            if (err != hipSuccess) break;
-            if (prof) h->prof_n++;
-        }
-    } else {
-        auto launch_here = [&](int i) {
-            const int part = part_of(i);
-            StepParams q = params_of(i);
-            void* args[1] = {&q};
-            const hipError_t e = hipExtLaunchKernel(reinterpret_cast<const void*>(kernel), grid, dim3(64 * POM_WPB), args, 0,
-                                                    part < h->main_part ? h->stream : h->sub[part], nullptr, nullptr, 0);
-            if (e == hipSuccess) issued++;
-            else if (err == hipSuccess) err = e;
-        };
-        for (int i = 0; i < use && err == hipSuccess; i++) launch_here(i); /* every stream's first launch: now */
-        PomIssuer* started[PomBatch::MAX_PARTS] = {};
-        for (int part = h->main_part; part < use && err == hipSuccess; part++) {
-            PomIssuer* w = issuer_for(h, part);
-            if (!w) continue; /* (no thread to be had: this thread issues that stream's launches below) */
-            {
-                std::lock_guard<std::mutex> g(w->mu);
-                w->chain_q.clear();
-                for (int i = use; i < launches; i++)
-                    if (part_of(i) == part) w->chain_q.push_back(params_of(i));
-                w->chain_kernel = reinterpret_cast<const void*>(kernel);
-                w->chain_grid = grid.x;
-                w->chain_done = 0;
-                w->st = h->sub[part];
-                w->err = hipSuccess;
-                w->busy = true;
-                w->has_job = true;
-                w->posted.fetch_add(1, std::memory_order_release);
-            }
-            w->cv.notify_all();
-            started[part] = w;
-        }
-        for (int i = use; i < launches && err == hipSuccess; i++) { /* the caller's own stream(s), and those without a helper */
-            const int part = part_of(i);
-            if (part < h->main_part || !started[part]) launch_here(i);
-        }
-        for (int part = 0; part < use; part++) { /* everything is queued when the call returns */
-            PomIssuer* w = started[part];
-            if (!w) continue;
-            std::unique_lock<std::mutex> lk(w->mu);
-            w->cv.wait(lk, [w] { return !w->busy; });
-            issued += w->chain_done;
-            if (w->err != hipSuccess && err == hipSuccess) err = w->err;
-        }
-    }
-    c->turn = turn0 + (uint32_t)launches;
+    hipError_t err = hipSuccess;
+    const int issued = issue_runs(h, runs, use, helpers, &err);
+    c->turn += (uint32_t)issued;
     /* what was issued is accounted for even if a launch failed half-way: the tiles' words, the log and the host's tick agree */
     if (issued > 0) {
         if (continues && !c->log.empty() && c->log.back().visit0 + c->log.back().launches == c->visits && c->log.back().policy == policy) {
@@ -926,22 +833,46 @@ static int launch_many_chain(PomBatch* h, const StepParams& p0, int launches, bo
         c->unverified = true;
         h->tick += (uint64_t)issued;
     }
+    *used = true;
     if (err != hipSuccess) {
         snprintf(g_err, sizeof g_err, "pom_step_kernel launch: %s (%d of the call's %d ticks were queued and will be played; the rest were not)",
                  hipGetErrorString(err), issued, launches);
-        *used = true;
         return POM_E_HIP;
     }
-    *used = true;
     return POM_OK;
 }
 
-/* `launches` dispatches per part, ticks_per_launch ticks each; advances h->tick by what was queued */
+/* ---- several ticks in one call ---------------------------------------------------------------------------------------------
+ * `launches` launches per part, ticks_per_launch ticks each; advances h->tick by what was queued.
+ * The default up to 196,608 envs is POM_ISSUE_CHAIN (launch_many_chain, pom_chain.h): one launch over all tiles per tick,
+ * consecutive launches on different streams, a ticket word per tile ordering the tile's ticks — 9.2 us per step at 65,536 envs
+ * where sub-batches take 14.5.  What follows is how SUB-BATCH launches are issued: what a handle does where launches are not
+ * chained (several ticks per launch, batches from 196,608 envs up, the one-lane-per-env shapes, a handle asked for another mode).
+ * A step is then `parts` launches (one per sub-batch, on parallel streams) every ~16 us at 65,536 envs: the host has ~5 us per
+ * launch, and a call of K ticks is judged by how soon all parts' first launches are out and whether the queues stay fed.
+ * Three ways to issue them (PomBatchOptions.issue_mode; results cannot depend on the choice: the same kernels with the same
+ * arguments go to the same streams in the same per-stream order).  Measured on MI355X, 65,536 envs, 3 parts, per step
+ * (profiles/r03_issue_modes.txt):
+ *                                   20-tick call from an idle device (the bench driver's shape)      500-tick call
+ *   POM_ISSUE_THREADS               18.0 us, run to run the same                                      15.5 us
+ *   POM_ISSUE_DIRECT                17.2 .. 26.4 us: one thread issues all 60 launches (2.8 us each   15.6 - 16.0 us
+ *                                   on a quiet host, then it is ahead of the device; on a busy one it is not)
+ *   POM_ISSUE_GRAPH                 21.4 .. 23.5 us: queued in 48 us, but the replayed nodes run with   16.1 - 16.2 us
+ *                                   wider gaps than plain launches
+ * THREADS: part k's launches of ALL the ticks of the call are issued by a helper thread of its own (issue_runs), the call returns
+ * when everything is queued.  A helper that cannot be started is not an error: the calling thread issues its launches.
+ * DIRECT: the calling thread issues everything, tick by tick; no library-owned threads.
+ * GRAPH: part k's launches of POM_GRAPH_TICKS consecutive ticks are a HIP graph — a plain chain of kernel nodes, built once —
+ * replayed on part k's stream with one hipGraphLaunch per part and chunk; no library-owned threads either.  The nodes'
+ * arguments never change: a node carries its offset inside the chunk, and the tick the chunk starts at is a device word per
+ * part (StepParams.tick_base) that a one-lane kernel sets on the part's stream in front of each replay.  (One graph holding
+ * all parts as parallel branches was measured first: this runtime plays the branches one after the other — 18.5 us per step
+ * in a 500-tick call.)  Ticks that do not fill a chunk are launched directly. */
 static int launch_many(PomBatch* h, uint64_t seed, int dist, int launches, int ticks_per_launch, bool policy)
 {
     static const int chunk = getenv("POM_GRAPH_TICKS") ? atoi(getenv("POM_GRAPH_TICKS")) : POM_GRAPH_TICKS;
     int done = 0;
-    if (runs_chain(h, policy, ticks_per_launch) && launches >= 1) {
+    if (runs_chain(h, ticks_per_launch) && launches >= 1) {
         StepParams p;
         memset(&p, 0, sizeof p); /* consecutive calls' parameters are compared byte for byte */
         if (int rc = fill_params(h, p, nullptr, seed, dist, 1)) return rc;
@@ -961,15 +892,12 @@ static int launch_many(PomBatch* h, uint64_t seed, int dist, int launches, int t
         if (!g) return rc;
         if (int fr = fork_parts(h)) return fr;
         for (; launches - done >= chunk; done += chunk) {
-            for (int pass = 0; pass < 2; pass++) { /* the caller's own stream first: its part starts without a wait on the fork event */
-                for (int k = 0; k < h->parts; k++) {
-                    const bool own = h->parts == 1 || k < h->main_part;
-                    if (own != (pass == 0) || !g->exec[k]) continue;
-                    hipStream_t st = own ? h->stream : h->sub[k];
-                    pom_set_word_kernel<<<dim3(1), dim3(1), 0, st>>>(h->tick_words + k, (uint32_t)h->tick);
-                    HIPCHK(hipGetLastError());
-                    HIPCHK(hipGraphLaunch(g->exec[k], st));
-                }
+            for (int k = 0; k < h->parts; k++) { /* the caller's own stream first: its part starts without a wait on the fork event */
+                if (!g->exec[k]) continue;
+                hipStream_t st = part_stream(h, k, h->parts);
+                pom_set_word_kernel<<<dim3(1), dim3(1), 0, st>>>(h->tick_words + k, (uint32_t)h->tick);
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipGraphLaunch(g->exec[k], st));
             }
             h->tick += (uint64_t)chunk * (uint64_t)ticks_per_launch;
         }
@@ -986,7 +914,7 @@ static int launch_many(PomBatch* h, uint64_t seed, int dist, int launches, int t
     if (int rc = fill_params(h, p, nullptr, seed, dist, ticks_per_launch)) return rc;
     /* (a handle of chained launches issues what cannot be chained — policy, fresh boards, several ticks per launch — with the helper threads) */
     const bool threads = (h->issue_mode == POM_ISSUE_THREADS || h->issue_mode == POM_ISSUE_CHAIN) && h->parts > 1 && launches - done >= 2;
-    if (int rc = launch_many_streams(h, p, launches - done, ticks_per_launch, policy, threads)) return rc;
+    if (int rc = launch_parts(h, p, launches - done, policy, false, threads)) return rc;
     h->tick += (uint64_t)(launches - done) * (uint64_t)ticks_per_launch;
     return POM_OK;
 }
@@ -1019,18 +947,13 @@ static int launch_policy(PomBatch* h, uint64_t seed)
     p.diag = h->diag_pol;
 #endif
     /* same split and the same streams as the tick, so that part k's policy -> tick -> policy chain pipelines */
-    const int64_t tiles = h->n_pad / 16, step_tiles = h->n_pad / h->epw;
     int rc = fork_parts(h);
     if (rc) return rc;
     for (int k = 0; k < h->parts; k++) {
-        /* the tick's part k covers envs [step_tiles*k/parts, ...) * epw: use the same env boundaries */
-        const int64_t e0 = step_tiles * k / h->parts * h->epw, e1 = step_tiles * (k + 1) / h->parts * h->epw;
-        const int64_t b0 = e0 / 16, b1 = e1 / 16;
-        if (b1 <= b0) continue;
-        (void)tiles;
-        p.block0 = b0;
-        hipStream_t st = (h->parts == 1 || k < h->main_part) ? h->stream : h->sub[k];
-        pom_policy_kernel<<<dim3((unsigned)(b1 - b0)), dim3(64), 0, st>>>(p);
+        int64_t b0, b1;
+        if (!part_tiles(h, k, h->parts, &b0, &b1)) continue;
+        p.block0 = b0 * h->epw / 16; /* the policy kernel's tiles are 16 envs: the tick's part k, env for env */
+        pom_policy_kernel<<<dim3((unsigned)((b1 - b0) * h->epw / 16)), dim3(64), 0, part_stream(h, k, h->parts)>>>(p);
         HIPCHK(hipGetLastError());
     }
     return POM_OK;
