@@ -30,6 +30,9 @@
  * counters while it chooses its bombs and the explosion frames (21 rows) from then on — the counters are read for the last time
  * before the first blast of loop B can push a frame, and a wavefront's envs go through both in step —: 116 rows = 29.7 / 14.8 /
  * 7.4 KB for 64 / 32 / 16 envs per wavefront (137 rows until round 5: 18 wavefronts of 16 envs per CU; now 22).
+ * Frame d of column A is the dword at byte (d * EPW + A) * 4 of that region, inside the counters of column ((d * EPW + A) * 4) / 124:
+ * the overlay family of tests/tile_mates.py puts a chain that goes off inside loop B in A and a bomb that is selected by its counter
+ * alone on that very byte (tests/test_tile_mates.py, the GPU tests), and fails if a frame lands before the mates have read.
  * ------------------------------------------------------------------------------------------- */
 enum {
     ROW_BOARD = POM_REC_BOARD,    /* 31 rows: four 8-bit cells per dword            */
@@ -321,8 +324,8 @@ __device__ __forceinline__ void store_tile16_x4(uint32_t* base, int64_t np, cons
     }
 }
 /*
- * The restart snapshot is kept array-of-structs: env e's record is the 328 contiguous bytes snap[e * 82 .. e * 82 + 81].
- * A restart needs ONE env's whole record, and in the column layout of the state buffer that is 82 dwords in 82
+ * The restart snapshot is kept array-of-structs: env e's record is the 320 contiguous bytes snap[e * 80 .. e * 80 + 79].
+ * A restart needs ONE env's whole record, and in the column layout of the state buffer that is 80 dwords in 80
  * different 64-byte sectors (4 useful bytes each: 18 MB of HBM fetch per step at 65,536 envs for the 3.8 % of envs that
  * restart, a fifth of the kernel's whole traffic; profiles/r02a_head1_summary.txt).  Here the whole wavefront fetches the
  * record of one restarting env — lane l takes dwords l and l + 64, whole sectors — and writes it into that env's

@@ -8,6 +8,9 @@
 
 #include "pom_packed.h"
 #include "pom_step_body.h"
+#include "pom_emul_probe.h"
+
+PomEmulProbe g_pom_probe; /* counters of the last tick, both builds (pom_emul_probe.h) */
 
 struct ArrayEnv {
     uint8_t cells[124];
@@ -27,21 +30,21 @@ struct ArrayEnv {
     void put_flame(int s, int v) { flames[s] = v; }
     void put_bdest(int i, int v) { bd[i] = (uint8_t)v; }
     int cell(int c) const { return cells[c]; }
-    void set_cell(int c, int v) { cells[c] = (uint8_t)v; }
+    void set_cell(int c, int v) { g_pom_probe.on_cell(c, v); cells[c] = (uint8_t)v; }
     int bomb(int s) const { return bombs[s]; }
-    void set_bomb(int s, int v) { bombs[s] = v; }
+    void set_bomb(int s, int v) { g_pom_probe.on_bomb(); bombs[s] = v; }
     int flame(int s) const { return flames[s]; }
     void set_flame(int s, int v) { flames[s] = v; }
     int bdest(int i) const { return bd[i]; }
     void set_bdest(int i, int v) { bd[i] = (uint8_t)v; }
     int frame(int d) const { return stack[d]; }
-    void set_frame(int d, int v) { stack[d] = v; }
+    void set_frame(int d, int v) { g_pom_probe.on_frame(d, v); stack[d] = v; }
     int ag1(int i) const { return a1w[i]; }
     void set_ag1(int i, int v) { a1w[i] = v; }
     void put_ag1(int i, int v) { a1w[i] = v; }
-    void claims_clear() { std::memset(cnt, 0, sizeof cnt); }
-    void claim(int c) { cnt[c]++; }
-    int claims(int c) const { return cnt[c]; }
+    void claims_clear() { g_pom_probe.on_clear(); std::memset(cnt, 0, sizeof cnt); }
+    void claim(int c) { g_pom_probe.on_claim(); cnt[c]++; }
+    int claims(int c) const { return g_pom_probe.on_claims_read(0, 1, cnt[c]); }
 };
 
 extern "C" {
@@ -165,6 +168,16 @@ uint32_t pom_emul_step(void* state_1004, const int32_t* moves, int env_mode, int
     pom_unpack_state(rec, 1, out);
     std::memcpy(state_1004, out, POM_STATE_BYTES);
     return ub;
+}
+
+/* the probe (pom_emul_probe.h): cleared before a tick, read after it; cap < 2 makes loop_b_todo blind to double claims, add >= 2
+ * makes it select every bomb */
+void pom_emul_probe_reset(void) { g_pom_probe.reset(); }
+void pom_emul_probe_get(int32_t* out) { g_pom_probe.get(out); }
+void pom_emul_probe_claims_cap(int cap, int add)
+{
+    g_pom_probe.claims_cap = cap;
+    g_pom_probe.claims_add = add;
 }
 
 /* chained launches: a visit's distance from its call's first visit (pom_packed.h) */

@@ -32,6 +32,7 @@
 
 #include "pom_packed.h"
 #include "pom_step_body.h"
+#include "pom_emul_probe.h"
 
 namespace {
 
@@ -182,10 +183,18 @@ struct QuadLaneEnv {
 
     int cell(int c) const { return rd(A_CELL + c); }
     void put_cell(int c, int v) { wr(A_CELL + c, v & 0xFF, W_PUT); }
-    void set_cell(int c, int v) { wr(A_CELL + c, v & 0xFF, set_kind()); }
+    void set_cell(int c, int v)
+    {
+        if (sub_ == 0) g_pom_probe.on_cell(c, v & 0xFF);
+        wr(A_CELL + c, v & 0xFF, set_kind());
+    }
     int bomb(int s) const { return rd(A_BOMB + s); }
     void put_bomb(int s, int v) { wr(A_BOMB + s, v, W_PUT); }
-    void set_bomb(int s, int v) { wr(A_BOMB + s, v, set_kind()); }
+    void set_bomb(int s, int v)
+    {
+        if (sub_ == 0) g_pom_probe.on_bomb();
+        wr(A_BOMB + s, v, set_kind());
+    }
     int flame(int s) const { return rd(A_FLAME + s); }
     void put_flame(int s, int v) { wr(A_FLAME + s, v, W_PUT); }
     void set_flame(int s, int v) { wr(A_FLAME + s, v, set_kind()); }
@@ -193,16 +202,28 @@ struct QuadLaneEnv {
     void put_bdest(int i, int v) { wr(A_BDEST + i, v & 0xFF, W_PUT); }
     void set_bdest(int i, int v) { wr(A_BDEST + i, v & 0xFF, set_kind()); }
     int frame(int d) const { return rd(A_STACK + d); }
-    void set_frame(int d, int v) { wr(A_STACK + d, v, set_kind()); }
+    void set_frame(int d, int v)
+    {
+        if (sub_ == 0) g_pom_probe.on_frame(d, v);
+        wr(A_STACK + d, v, set_kind());
+    }
     int ag1(int i) const { return rd(A_AG1 + i); }
     void put_ag1(int i, int v) { wr(A_AG1 + i, v, W_PUT); }
     void set_ag1(int i, int v) { wr(A_AG1 + i, v, set_kind()); }
-    void claims_clear() { q->claim_clear[sub_] = 1; }
-    void claim(int c) { q->claim_add[sub_][c]++; }
+    void claims_clear()
+    {
+        if (sub_ == 0) g_pom_probe.on_clear();
+        q->claim_clear[sub_] = 1;
+    }
+    void claim(int c)
+    {
+        g_pom_probe.on_claim();
+        q->claim_add[sub_][c]++;
+    }
     int claims(int c) const /* read after a sync(): nothing of this lane's own may be pending (the device reads what is committed) */
     {
         if (q->claim_add[sub_][c] || q->claim_clear[sub_]) flag(2, 20000 + c);
-        return q->claim_mem[c];
+        return g_pom_probe.on_claims_read(sub_, 4, q->claim_mem[c]);
     }
 };
 
@@ -359,18 +380,25 @@ uint32_t pom_emul_quad_step(void* state_1004, const int32_t* moves, int env_mode
 extern "C" uint32_t pom_emul_step_rec(uint32_t* rec, const int32_t* moves, int env_mode, int max_steps, uint32_t* status_io); /* pom_emul.cpp */
 
 /* T ticks of one env on a record packed ONCE (the way the device keeps it), one lane or four per env: the unpacked state after
- * every tick into states_out[T] (1004 bytes each), the tick's flags into ubs_out[T].  Returns 0, or -1 if the start state is not
- * representable. */
-extern "C" int pom_emul_run(const void* state_1004, const int32_t* moves, int ticks, int quad, void* states_out, uint32_t* ubs_out)
+ * every tick into states_out[T] (1004 bytes each), the tick's flags into ubs_out[T], and — where probe_out is given — the tick's
+ * counters (pom_emul_probe.h) into probe_out[T][POM_PROBE_WORDS].  Returns 0, or -1 if the start state is not representable. */
+extern "C" int pom_emul_run_probe(const void* state_1004, const int32_t* moves, int ticks, int quad, void* states_out, uint32_t* ubs_out, int32_t* probe_out)
 {
     uint32_t rec[POM_REC_DWORDS];
     if (pom_pack_state((const int32_t*)state_1004, rec, 1)) return -1;
     for (int t = 0; t < ticks; t++) {
+        g_pom_probe.reset();
         ubs_out[t] = quad ? pom_emul_quad_step_rec(rec, moves + 4 * t, 0, 0, nullptr) : pom_emul_step_rec(rec, moves + 4 * t, 0, 0, nullptr);
+        if (probe_out) g_pom_probe.get(probe_out + (size_t)t * POM_PROBE_WORDS);
         int32_t out[251];
         std::memset(out, 0, sizeof out);
         pom_unpack_state(rec, 1, out);
         std::memcpy((char*)states_out + (size_t)t * POM_STATE_BYTES, out, POM_STATE_BYTES);
     }
     return 0;
+}
+
+extern "C" int pom_emul_run(const void* state_1004, const int32_t* moves, int ticks, int quad, void* states_out, uint32_t* ubs_out)
+{
+    return pom_emul_run_probe(state_1004, moves, ticks, quad, states_out, ubs_out, nullptr);
 }
