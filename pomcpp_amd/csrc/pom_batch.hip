@@ -9,6 +9,41 @@
 #include "pom_runtime.h"
 #include "pom_copy.h"
 
+/* The chunked read-backs: the AoS staging buffer holds h->staging_envs States, so a range leaves in chunks of that many envs —
+ * launch, copy back, synchronise (staging is reused by the next chunk). */
+template <class Launch> /* launch(first env, envs): fills the staging buffer with the States of the chunk */
+static int download_chunks(PomBatch* h, void* states, int64_t first, int64_t count, Launch launch)
+{
+    HIPCHK(hipSetDevice(h->device));
+    if (int jr = quiesce(h)) return jr;
+    for (int64_t off = 0; off < count; off += h->staging_envs) {
+        const int64_t c = count - off < h->staging_envs ? count - off : h->staging_envs;
+        HIPCHK(hipMemsetAsync(h->staging, 0, (size_t)c * POM_STATE_BYTES, h->stream));
+        launch(first + off, c);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync((char*)states + off * POM_STATE_BYTES, h->staging, (size_t)c * POM_STATE_BYTES, hipMemcpyDeviceToHost,
+                              h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    return POM_OK;
+}
+template <class Launch> /* launch(first env, envs): leaves `nout` arrays of `envs` int32 in the staging buffer (scratch here: a few ints per env << 251) */
+static int fetch_columns(PomBatch* h, int64_t first, int64_t count, void* const* outs, int nout, Launch launch)
+{
+    HIPCHK(hipSetDevice(h->device));
+    if (int jr = quiesce(h)) return jr;
+    for (int64_t off = 0; off < count; off += h->staging_envs) {
+        const int64_t c = count - off < h->staging_envs ? count - off : h->staging_envs;
+        launch(first + off, c);
+        HIPCHK(hipGetLastError());
+        for (int k = 0; k < nout; k++)
+            if (outs[k])
+                HIPCHK(hipMemcpyAsync((int32_t*)outs[k] + off, h->staging + (int64_t)k * c, (size_t)c * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    return POM_OK;
+}
+
 extern "C" {
 
 const char* pom_last_error(void) { return g_err; }
@@ -294,18 +329,9 @@ int pom_batch_download(PomBatch* h, void* states, int64_t first, int64_t count)
 {
     int rc = check_range(h, first, count);
     if (rc || !states) return rc ? rc : POM_E_ARG;
-    HIPCHK(hipSetDevice(h->device));
-    if (int jr = quiesce(h)) return jr;
-    for (int64_t off = 0; off < count; off += h->staging_envs) {
-        const int64_t c = count - off < h->staging_envs ? count - off : h->staging_envs;
-        HIPCHK(hipMemsetAsync(h->staging, 0, (size_t)c * POM_STATE_BYTES, h->stream));
-        pom_unpack_kernel<<<dim3((unsigned)((c + 63) / 64)), dim3(64), 0, h->stream>>>(h->state, first + off, c, h->n_pad, h->staging);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync((char*)states + off * POM_STATE_BYTES, h->staging, (size_t)c * POM_STATE_BYTES, hipMemcpyDeviceToHost,
-                              h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    }
-    return POM_OK;
+    return download_chunks(h, states, first, count, [h](int64_t e0, int64_t c) {
+        pom_unpack_kernel<<<dim3((unsigned)((c + 63) / 64)), dim3(64), 0, h->stream>>>(h->state, e0, c, h->n_pad, h->staging);
+    });
 }
 
 int pom_batch_snapshot(PomBatch* h)
@@ -597,20 +623,10 @@ int pom_batch_status(PomBatch* h, int64_t first, int64_t count, int32_t* done, i
 {
     int rc = check_range(h, first, count);
     if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    if (int jr = quiesce(h)) return jr;
     void* outs[6] = {done, winner, draw, alive, time_step, ubflags};
-    /* the AoS staging buffer doubles as scratch: 6 ints per env << 251 */
-    for (int64_t off = 0; off < count; off += h->staging_envs) {
-        const int64_t c = count - off < h->staging_envs ? count - off : h->staging_envs;
-        pom_status_kernel<<<dim3((unsigned)((c + 255) / 256)), dim3(256), 0, h->stream>>>(h->state, first + off, c, h->n_pad, h->staging);
-        HIPCHK(hipGetLastError());
-        for (int k = 0; k < 6; k++)
-            if (outs[k])
-                HIPCHK(hipMemcpyAsync((int32_t*)outs[k] + off, h->staging + (int64_t)k * c, (size_t)c * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    }
-    return POM_OK;
+    return fetch_columns(h, first, count, outs, 6, [h](int64_t e0, int64_t c) {
+        pom_status_kernel<<<dim3((unsigned)((c + 255) / 256)), dim3(256), 0, h->stream>>>(h->state, e0, c, h->n_pad, h->staging);
+    });
 }
 
 int pom_batch_last_results(PomBatch* h, int64_t first, int64_t count, int32_t* finished, int32_t* winner, int32_t* draw,
@@ -622,20 +638,10 @@ int pom_batch_last_results(PomBatch* h, int64_t first, int64_t count, int32_t* f
         snprintf(g_err, sizeof g_err, "pom_batch_last_results: the batch was not created with auto_reset = POM_RESET_AT_END");
         return POM_E_ARG;
     }
-    HIPCHK(hipSetDevice(h->device));
-    if (int jr = quiesce(h)) return jr;
     void* outs[5] = {finished, winner, draw, length, alive};
-    for (int64_t off = 0; off < count; off += h->staging_envs) {
-        const int64_t c = count - off < h->staging_envs ? count - off : h->staging_envs;
-        pom_results_kernel<<<dim3((unsigned)((c + 255) / 256)), dim3(256), 0, h->stream>>>(h->state, h->terminal, first + off, c, h->n_pad,
-                                                                                            h->staging);
-        HIPCHK(hipGetLastError());
-        for (int k = 0; k < 5; k++)
-            if (outs[k])
-                HIPCHK(hipMemcpyAsync((int32_t*)outs[k] + off, h->staging + (int64_t)k * c, (size_t)c * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    }
-    return POM_OK;
+    return fetch_columns(h, first, count, outs, 5, [h](int64_t e0, int64_t c) {
+        pom_results_kernel<<<dim3((unsigned)((c + 255) / 256)), dim3(256), 0, h->stream>>>(h->state, h->terminal, e0, c, h->n_pad, h->staging);
+    });
 }
 
 int pom_batch_download_terminal(PomBatch* h, void* states, int64_t first, int64_t count)
@@ -646,18 +652,9 @@ int pom_batch_download_terminal(PomBatch* h, void* states, int64_t first, int64_
         snprintf(g_err, sizeof g_err, "pom_batch_download_terminal: the batch was not created with auto_reset = POM_RESET_AT_END");
         return POM_E_ARG;
     }
-    HIPCHK(hipSetDevice(h->device));
-    if (int jr = quiesce(h)) return jr;
-    for (int64_t off = 0; off < count; off += h->staging_envs) {
-        const int64_t c = count - off < h->staging_envs ? count - off : h->staging_envs;
-        HIPCHK(hipMemsetAsync(h->staging, 0, (size_t)c * POM_STATE_BYTES, h->stream));
-        pom_unpack_aos_kernel<<<dim3((unsigned)((c + 63) / 64)), dim3(64), 0, h->stream>>>(h->terminal, first + off, c, h->staging);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync((char*)states + off * POM_STATE_BYTES, h->staging, (size_t)c * POM_STATE_BYTES, hipMemcpyDeviceToHost,
-                              h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    }
-    return POM_OK;
+    return download_chunks(h, states, first, count, [h](int64_t e0, int64_t c) {
+        pom_unpack_aos_kernel<<<dim3((unsigned)((c + 63) / 64)), dim3(64), 0, h->stream>>>(h->terminal, e0, c, h->staging);
+    });
 }
 
 int pom_batch_counters_device(PomBatch* h, void* dev_int64x4)

@@ -6,8 +6,8 @@
  *
  * The tick itself is pom_step_body.h; this file is the data movement around it:
  *   HBM (packed records in 16-env tiles, pom_packed.h) -> LDS tile + VGPRs -> tick(s) -> HBM,
- * the SimpleAgent policy kernel, the observation export, the board generator, the pack / unpack between the boundary's 1004-byte States and the tiles,
- * status extraction and counters.
+ * the SimpleAgent policy kernel, the observation export, the board generator and counters.  The pack / unpack between the
+ * boundary's 1004-byte States and the tiles and the status extraction are pom_boundary.h, included below.
  */
 #ifndef POM_KERNELS_H_
 #define POM_KERNELS_H_
@@ -1108,6 +1108,17 @@ __device__ __forceinline__ void pom_chain_leave(unsigned long long* word, int la
     if (lane == 0) __hip_atomic_fetch_add(word, v.done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+/* XCD-aware tile order — the tile that workgroup b of a grid of nb takes: workgroups are dealt round-robin over the 8 XCDs (b
+ * and b+8 share one, each XCD has its own L2).  Neighbouring tiles are given to workgroups of the SAME XCD (bijective for any
+ * grid size): with the buffers laid out row-major over all envs (rounds 1-2) neighbouring tiles shared the 128-B lines of every
+ * record row and the second touch of a line became an L2 hit instead of a second HBM fetch; with a tile contiguous in memory
+ * (round 3) it keeps an XCD's traffic in one region of memory. */
+__device__ __forceinline__ int64_t pom_xcd_tile_order(int64_t b, int64_t nb)
+{
+    const int64_t q = nb / 8, r = nb % 8, x = b % 8;
+    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
+}
+
 /* a dword that a wavefront of an earlier, still unfinished launch may have written (chained launches): past this CU's vector cache */
 template <bool CHAIN>
 __device__ __forceinline__ uint32_t pom_load_shared(const uint32_t* ptr)
@@ -1140,12 +1151,7 @@ __global__ __launch_bounds__(64 * POM_WPB, (POLICY ? 4 : G == 4 ? POM_QUAD_WAVES
     uint8_t* const danger = reinterpret_cast<uint8_t*>(tile + POM_REC_DWORDS * EPW);
     uint32_t* const sets = tile + (POM_REC_DWORDS + 32) * EPW;
     const int lane = threadIdx.x & 63;
-    /* XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs (b and b+8 share one, each XCD has its own
-     * L2).  Neighbouring tiles are given to workgroups of the SAME XCD (bijective for any grid size): with the buffers laid
-     * out row-major over all envs (rounds 1-2) neighbouring tiles shared the 128-B lines of every record row and the
-     * second touch of a line became an L2 hit instead of a second HBM fetch; with a tile contiguous in memory (round 3) it
-     * keeps an XCD's traffic in one region of memory. */
-    int64_t tile_local;
+    int64_t tile_local; /* in XCD-aware order (pom_xcd_tile_order), or, chained, by the XCD the workgroup is on */
     uint32_t chain_xcd = 0;
     if (CHAIN) {
         /* the XCD the workgroup IS on decides its tile (launches of different queues start their round-robin at different
@@ -1166,7 +1172,8 @@ __global__ __launch_bounds__(64 * POM_WPB, (POLICY ? 4 : G == 4 ? POM_QUAD_WAVES
 #if defined(POM_NO_XCD_REMAP)
     tile_local = blockIdx.x;
 #else
-    {
+    { /* pom_xcd_tile_order(blockIdx.x, gridDim.x), written out: the call, inlined, leaves the same tiles but not the same instructions
+         in the tick behind it (signed for unsigned minima in 23 of the 27 instantiations), and this kernel's code is kept as measured */
         const int64_t b = blockIdx.x, nb = gridDim.x, q = nb / 8, r = nb % 8, x = b % 8;
         tile_local = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
     }
@@ -1635,11 +1642,7 @@ __global__ __launch_bounds__(64) void pom_policy_kernel(PolicyParams p)
     __shared__ uint32_t sets[12 * 16];
     const int lane = threadIdx.x;
     const int64_t np = p.n_pad;
-    int64_t tile_local;
-    {
-        const int64_t b = blockIdx.x, nb = gridDim.x, q = nb / 8, r = nb % 8, x = b % 8;
-        tile_local = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
-    }
+    const int64_t tile_local = pom_xcd_tile_order(blockIdx.x, gridDim.x);
     const int64_t tile_id = p.block0 + tile_local;
     const bool env_mode = p.mode == POM_MODE_ENV;
 #if defined(POM_DIAG)
@@ -1729,11 +1732,7 @@ __global__ __launch_bounds__(64) void pom_observe_kernel(ObserveParams p)
     __shared__ __attribute__((aligned(16))) uint32_t tile[POM_REC_DWORDS * 16];
     __shared__ uint4 stage[obs_stage_vecs(OBS_PASS_ENVS_ALONE)];
     const int lane = threadIdx.x;
-    int64_t tile_local;
-    {
-        const int64_t b = blockIdx.x, nb = gridDim.x, q = nb / 8, r = nb % 8, x = b % 8;
-        tile_local = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
-    }
+    const int64_t tile_local = pom_xcd_tile_order(blockIdx.x, gridDim.x);
     const int64_t tile_id = p.block0 + tile_local;
     load_tile16_x4(p.state + tile_id * POM_TILE_DWORDS, POM_TILE_ENVS, tile, lane);
     /* The builtin, not inline asm: the compiler's own wait-count bookkeeping must SEE that the LDS-DMA rows have landed before the
@@ -1768,266 +1767,8 @@ __global__ __launch_bounds__(64) void pom_generate_kernel(uint32_t* state, uint3
     }
 }
 
-/* ---- boundary kernels ----------------------------------------------------------------------- */
-__global__ void pom_pack_kernel(const int32_t* __restrict__ aos, int64_t first, int64_t count, uint32_t* state, uint32_t* snap,
-                                int64_t np, int* first_bad)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    uint32_t* col = state + pom_rec_col(first + i);
-    const int64_t rs = POM_TILE_ENVS; /* row stride of a column */
-    int bad = pom_pack_state(aos + i * (POM_STATE_BYTES / 4), col, rs, (int)((first + i) & 15));
-    /* live bombs must sit on the board and belong to a real agent: they index cells and agents */
-    {
-        const uint32_t m = pom_rec_meta(col, rs);
-        const int bIdx = (m >> 8) & 0xFF, bCnt = (m >> 16) & 0xFF;
-        if (!bad) {
-            for (int k = 0; k < bCnt; k++) {
-                const int b = (int)col[(POM_REC_BOMBS + (bIdx + k) % POM_Q) * rs];
-                bad |= (pb_x(b) >= POM_N) | (pb_y(b) >= POM_N) | (pb_id(b) >= POM_AGENT_COUNT);
-            }
-        }
-    }
-    if (bad) {
-        atomicMin(first_bad, (int)(i > INT_MAX - 1 ? INT_MAX - 1 : i));
-        for (int c = 0; c < 4 * POM_REC_BOARD_DWORDS; c++) pom_rec_set_cell(col, rs, c, 0, (int)((first + i) & 15)); /* inert blank board ... */
-        for (int d = POM_REC_TIMESTEP; d < POM_REC_DWORDS; d++) col[d * rs] = 0;
-        pom_rec_set_meta(col, rs, 0u, (uint32_t)POM_ST_DONE << 8); /* ... that is never stepped in ENV mode */
-    }
-    uint32_t* s = snap + (first + i) * POM_REC_DWORDS; /* the snapshot is array-of-structs (restart_column): a dense record */
-    for (int c = 0; c < 4 * POM_REC_BOARD_DWORDS; c++) pom_rec_set_cell(s, 1, c, pom_rec_cell(col, rs, c, (int)((first + i) & 15)));
-    for (int d = POM_REC_TIMESTEP; d < POM_REC_DWORDS; d++) s[d] = col[d * rs];
-}
-
-__global__ void pom_unpack_kernel(const uint32_t* __restrict__ state, int64_t first, int64_t count, int64_t np, int32_t* aos)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    pom_unpack_state(state + pom_rec_col(first + i), POM_TILE_ENVS, aos + i * (POM_STATE_BYTES / 4), (int)((first + i) & 15));
-}
-
-/* ---------------------------------------------------------------------------------------------
- * ONE State, one tick, one launch: the literal `bboard::Step(State*, Move*)` (POM_MODE_RAW) and `Environment::Step`'s tick +
- * bookkeeping (POM_MODE_ENV; environment.cpp:123-169) for callers that hold a single host State (pom_step, pom_env_step).
- * `io` is pinned host memory the device reads and writes directly — no staging copies, no second and third launch:
- *   dwords   0..250  in:  the State (include/pom_state.h)        252..255  in:  Move[4]
- *   dwords 256..506  out: the State after the tick               508..511  out: done, winner, draw, ubflags
- *   dword  512       out: 1 if the State is outside the representable game states (nothing else is written then)
- *   dword  513       out: `seq`, written LAST (system-scope release): the host polls it
- *   dwords 514..516  in:  mode, max_steps, seq of this request
- * One wavefront: all 64 lanes fetch, pack (pom_pack_state's fields, a dword per lane), the quad of lanes 0..3 plays the tick with
- * the same PomStepper as pom_step_kernel, all lanes unpack and write back.
- * ------------------------------------------------------------------------------------------- */
-struct StepOneParams {
-    int32_t* io_base;  /* POM_ONE_SLOTS pages of POM_ONE_PAGE_DWORDS dwords each */
-    uint64_t slots;    /* bit s: slot s holds a request; workgroup b serves the b-th set bit */
-};
-/* a slot's page: the layout above, then the request's own parameters — one launch serves whatever requests are pending, each
- * with its own mode (pom_step / pom_env_step), bound and sequence number */
-enum { POM_ONE_MOVES = 252, POM_ONE_OUT = 256, POM_ONE_STATUS = 508, POM_ONE_BAD = 512, POM_ONE_SEQ = 513, POM_ONE_MODE = 514,
-       POM_ONE_MAX_STEPS = 515, POM_ONE_REQ = 516, POM_ONE_PAGE_DWORDS = 1024, POM_ONE_SLOTS = 64 };
-
-__global__ __launch_bounds__(64) void pom_step_one_kernel(StepOneParams q)
-{
-    __shared__ __attribute__((aligned(16))) uint32_t tile[LDS_ROWS * 16];
-    __shared__ int32_t aos[256];
-    const int lane = threadIdx.x;
-    /* which slot: the blockIdx-th set bit of the request mask (wave-uniform) */
-    uint64_t slot_bits = q.slots;
-    for (unsigned b = 0; b < blockIdx.x; b++) slot_bits &= slot_bits - 1;
-    struct { int32_t* io; int32_t mode, max_steps; uint32_t seq; } p;
-    p.io = q.io_base + (int64_t)(__ffsll((unsigned long long)slot_bits) - 1) * POM_ONE_PAGE_DWORDS;
-    p.mode = p.io[POM_ONE_MODE];
-    p.max_steps = p.io[POM_ONE_MAX_STEPS];
-    p.seq = (uint32_t)p.io[POM_ONE_REQ];
-#pragma unroll
-    for (int k = 0; k < 4; k++) aos[lane + 64 * k] = p.io[lane + 64 * k]; /* State + Move[4]: four 256-B reads of host memory */
-    for (int k = lane; k < LDS_ROWS * 16; k += 64) tile[k] = 0u;           /* columns 1..15 stay blank and are never stepped */
-    __syncthreads();
-    /* pack into column 0: exactly pom_pack_state + the live-bomb test of pom_pack_kernel, a record dword per lane */
-    const int32_t* st = aos;
-    int bad = 0;
-    {
-        const int c = lane + 64, e0 = pom_cell_encode(st[lane], lane), e1 = c < POM_CELLS ? pom_cell_encode(st[c], c) : 0;
-        bad |= (e0 < 0) | (e1 < 0);
-        uint8_t* cells = reinterpret_cast<uint8_t*>(tile); /* env 0 of the tile: cell c at byte c * 16 */
-        cells[lane * 16] = (uint8_t)e0; /* (the tile was zeroed: the three bytes past cell 120 stay 0) */
-        if (c < POM_CELLS) cells[c * 16] = (uint8_t)e1;
-    }
-    const int32_t alive = st[122], bIdx = st[167], bCnt = st[168], fIdx = st[249], fCnt = st[250];
-    if (lane == 61) {
-        bad |= pom_pack_alive_bad(alive);
-        bad |= (bIdx < 0) | (bIdx >= POM_MAX_BOMBS) | (bCnt < 0) | (bCnt > POM_MAX_BOMBS);
-        bad |= (fIdx < 0) | (fIdx >= POM_MAX_BOMBS) | (fCnt < 0) | (fCnt > 255);
-        tile[POM_REC_TIMESTEP * 16] = (uint32_t)st[121];
-    }
-    if (lane < POM_AGENT_COUNT) {
-        const int32_t* a = st + 123 + 6 * lane;
-        const uint32_t flags = (uint32_t)a[5];
-        const int kick = (flags & 0xFF) != 0, dead = ((flags >> 8) & 0xFF) != 0;
-        bad |= (a[0] < 0) | (a[0] >= POM_BOARD_SIZE) | (a[1] < 0) | (a[1] >= POM_BOARD_SIZE);
-        bad |= pom_pack_agent_bad(a[2], a[3], a[4]);
-        /* the top bytes: aliveAgents, bombs.index, bombs.count, flames.index in the agents' first words; flames.count (and the clear
-         * status and flags) in their second words (pom_packed.h) */
-        const uint32_t m0 = (uint32_t)(lane == 0 ? alive : lane == 1 ? bIdx : lane == 2 ? bCnt : fIdx) & 0xFFu, m1 = lane == 0 ? (uint32_t)fCnt & 0xFFu : 0u;
-        tile[(POM_REC_AGENTS + 2 * lane) * 16] = ((uint32_t)a[0] & 0xF) | (((uint32_t)a[1] & 0xF) << 4) | (((uint32_t)a[2] & 0xFF) << 8) |
-                                                 (kick ? (uint32_t)POM_AG_KICK : 0u) | (dead ? (uint32_t)POM_AG_DEAD : 0u) | (m0 << 24);
-        tile[(POM_REC_AGENTS + 2 * lane + 1) * 16] = ((uint32_t)a[3] & 0xFFFF) | (((uint32_t)a[4] & 0xFF) << 16) | (m1 << 24);
-    }
-    if (lane >= 20 && lane < 20 + POM_MAX_BOMBS) {
-        const int k = lane - 20;
-        const int b = st[147 + k];
-        tile[(POM_REC_BOMBS + k) * 16] = (uint32_t)b;
-        /* live bombs must sit on the board and belong to a real agent: they index cells and agents (pom_pack_kernel) */
-        const int age = k - bIdx + (k < bIdx ? POM_Q : 0); /* slot k is the age-th bomb of the queue */
-        if (bIdx >= 0 && bIdx < POM_MAX_BOMBS && age < bCnt) bad |= (pb_x(b) >= POM_N) | (pb_y(b) >= POM_N) | (pb_id(b) >= POM_AGENT_COUNT);
-    }
-    if (lane >= 40 && lane < 40 + POM_MAX_BOMBS) {
-        const int32_t* f = st + 169 + 4 * (lane - 40);
-        bad |= (f[0] < 0) | (f[0] >= POM_BOARD_SIZE) | (f[1] < 0) | (f[1] >= POM_BOARD_SIZE); /* also the stale slots */
-        bad |= (f[2] < -128) | (f[2] > 127) | (f[3] < 0) | (f[3] > 255);
-        tile[(POM_REC_FLAMES + lane - 40) * 16] =
-            (uint32_t)f[0] | ((uint32_t)f[1] << 8) | (((uint32_t)f[2] & 0xFF) << 16) | ((uint32_t)f[3] << 24);
-    }
-    if (__ballot(bad != 0)) { /* the caller's State is left alone; pom_step reports POM_E_UNREPRESENTABLE */
-        if (lane == 0) {
-            p.io[POM_ONE_BAD] = 1;
-            __threadfence_system();
-            __hip_atomic_store(reinterpret_cast<uint32_t*>(p.io) + POM_ONE_SEQ, p.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-        return;
-    }
-    __syncthreads();
-
-    /* the tick: lane -> (env lane / 4, member lane % 4) as in pom_step_kernel<16, 4>; env 0 is the only one there is */
-    const int ec = lane >> 2, member = lane & 3;
-    uint32_t* t = tile + ec;
-    PomLane L;
-    int time_step = 0;
-    uint32_t status = 0;
-    lane_from_tile(L, time_step, status, t, 16);
-#if defined(POM_DIAG)
-    for (int k = 0; k < POM_PH_N; k++) L.t_acc[k] = 0;
-    L.t_last = 0;
-#endif
-#if defined(POM_TRUNC)
-    L.trunc = 990;
-#endif
-    LdsEnv<16, 4> acc(tile, ec, member);
-    PomStepper<LdsEnv<16, 4>> stepper(acc, L);
-    const bool env_mode = p.mode == POM_MODE_ENV;
-    if (ec == 0) {
-        const uint32_t mvp = stepper.pack_moves_quad(aos[POM_ONE_MOVES + member]);
-        L.ub = 0;
-        stepper.step_packed(mvp);
-        if (env_mode) {
-            time_step++;
-            status = pom_env_epilogue(L, time_step, p.max_steps, status);
-        }
-        if (member == 0) { /* the register-resident rows */
-            t[POM_REC_TIMESTEP * 16] = (uint32_t)time_step;
-#pragma unroll
-            for (int k = 0; k < 8; k++) t[(POM_REC_AGENTS + k) * 16] = pom_lane_agent_word(L, status, k, (k & 1) ? t[(POM_REC_AGENTS + k) * 16] : 0u);
-        }
-    }
-    __syncthreads();
-
-    /* unpack column 0 (pom_unpack_state, a few State dwords per lane) straight into host memory */
-    int32_t* out = p.io + POM_ONE_OUT;
-    const uint32_t m = pom_rec_meta(tile, 16), m2 = pom_rec_meta2(tile, 16);
-    out[lane] = pom_cell_decode(pom_rec_cell(tile, 16, lane, 0), lane);
-    if (lane + 64 < POM_CELLS) out[lane + 64] = pom_cell_decode(pom_rec_cell(tile, 16, lane + 64, 0), lane + 64);
-    if (lane == 61) {
-        out[121] = (int32_t)tile[POM_REC_TIMESTEP * 16];
-        out[122] = pom_sext8(m);
-        out[167] = (int32_t)((m >> 8) & 0xFF);
-        out[168] = (int32_t)((m >> 16) & 0xFF);
-        out[249] = (int32_t)(m >> 24);
-        out[250] = (int32_t)(m2 & 0xFF);
-        const uint32_t s8 = (m2 >> 8) & 0xFF;
-        p.io[POM_ONE_STATUS + 0] = (s8 & POM_ST_DONE) ? 1 : 0;
-        p.io[POM_ONE_STATUS + 1] = (int)((s8 >> POM_ST_WINNER_SHIFT) & 7) - 1;
-        p.io[POM_ONE_STATUS + 2] = (s8 & POM_ST_DRAW) ? 1 : 0;
-        p.io[POM_ONE_STATUS + 3] = (int32_t)(m2 >> 16);
-        p.io[POM_ONE_BAD] = 0;
-    }
-    if (lane < POM_AGENT_COUNT) {
-        const uint32_t a0 = tile[(POM_REC_AGENTS + 2 * lane) * 16], a1 = tile[(POM_REC_AGENTS + 2 * lane + 1) * 16];
-        int32_t* a = out + 123 + 6 * lane;
-        a[0] = ag_x((int)a0);
-        a[1] = ag_y((int)a0);
-        a[2] = ag_bombcount((int)a0);
-        a[3] = ag_max_bombs((int)a1);
-        a[4] = ag_strength((int)a1);
-        a[5] = ag_kick((int)a0) | (ag_dead((int)a0) << 8);
-    }
-    if (lane >= 20 && lane < 20 + POM_MAX_BOMBS) out[147 + lane - 20] = (int32_t)tile[(POM_REC_BOMBS + lane - 20) * 16];
-    if (lane >= 40 && lane < 40 + POM_MAX_BOMBS) {
-        const uint32_t f = tile[(POM_REC_FLAMES + lane - 40) * 16];
-        int32_t* o = out + 169 + 4 * (lane - 40);
-        o[0] = (int32_t)(f & 0xFF);
-        o[1] = (int32_t)((f >> 8) & 0xFF);
-        o[2] = pom_sext8(f >> 16);
-        o[3] = (int32_t)(f >> 24);
-    }
-    __threadfence_system(); /* every lane's stores have left before ... */
-    __syncthreads();
-    if (lane == 0) /* ... the word the host is polling changes */
-        __hip_atomic_store(reinterpret_cast<uint32_t*>(p.io) + POM_ONE_SEQ, p.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-/* out: 6 arrays of `count` int32: done, winner, draw, alive, timeStep, ubflags */
-__global__ void pom_status_kernel(const uint32_t* __restrict__ state, int64_t first, int64_t count, int64_t np, int32_t* out)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    const uint32_t* col = state + pom_rec_col(first + i);
-    const uint32_t m = pom_rec_meta(col, POM_TILE_ENVS), m2 = pom_rec_meta2(col, POM_TILE_ENVS);
-    const uint32_t st = (m2 >> 8) & 0xFF;
-    out[0 * count + i] = (st & POM_ST_DONE) ? 1 : 0;
-    out[1 * count + i] = (int)((st >> POM_ST_WINNER_SHIFT) & 7) - 1;
-    out[2 * count + i] = (st & POM_ST_DRAW) ? 1 : 0;
-    out[3 * count + i] = pom_sext8(m);
-    out[4 * count + i] = (int32_t)col[POM_REC_TIMESTEP * POM_TILE_ENVS];
-    out[5 * count + i] = (int32_t)(m2 >> 16);
-}
-
-/* POM_RESET_AT_END: out = 5 arrays of `count` int32: finished (the state's "restarted" mark), then winner, draw, length, alive
- * of the terminal record (array of structs; all-zero = no episode finished yet) */
-__global__ void pom_results_kernel(const uint32_t* __restrict__ state, const uint32_t* __restrict__ terminal, int64_t first, int64_t count,
-                                   int64_t np, int32_t* out)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    const uint32_t now = (pom_rec_meta2(state + pom_rec_col(first + i), POM_TILE_ENVS) >> 8) & 0xFF;
-    const uint32_t* rec = terminal + (first + i) * POM_REC_DWORDS;
-    const uint32_t st = (pom_rec_meta2(rec, 1) >> 8) & 0xFF;
-    out[0 * count + i] = (now & POM_ST_RESTARTED) ? 1 : 0;
-    out[1 * count + i] = (int)((st >> POM_ST_WINNER_SHIFT) & 7) - 1;
-    out[2 * count + i] = (st & POM_ST_DRAW) ? 1 : 0;
-    out[3 * count + i] = (int32_t)rec[POM_REC_TIMESTEP];
-    out[4 * count + i] = (st & POM_ST_DONE) ? pom_sext8(pom_rec_meta(rec, 1)) : 0;
-}
-
-__global__ void pom_unpack_aos_kernel(const uint32_t* __restrict__ recs, int64_t first, int64_t count, int32_t* aos)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    pom_unpack_state(recs + (first + i) * POM_REC_DWORDS, 1, aos + i * (POM_STATE_BYTES / 4));
-}
-
-__global__ void pom_snapshot_kernel(const uint32_t* __restrict__ state, uint32_t* snap, int64_t np)
-{
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= np) return;
-    const uint32_t* col = state + pom_rec_col(e);
-    uint32_t* rec = snap + e * POM_REC_DWORDS; /* array of structs (restart_column): a dense record */
-    for (int c = 0; c < 4 * POM_REC_BOARD_DWORDS; c++) pom_rec_set_cell(rec, 1, c, pom_rec_cell(col, POM_TILE_ENVS, c, (int)(e & 15)));
-    for (int d = POM_REC_TIMESTEP; d < POM_REC_DWORDS; d++) {
-        rec[d] = col[d * POM_TILE_ENVS];
-    }
-    pom_rec_set_meta(rec, 1, pom_rec_meta(rec, 1), pom_rec_meta2(rec, 1) & 0xFFu); /* a snapshot starts an episode: status and flags clear */
-}
+/* ---- boundary kernels: States in and out, the one-State call, status, snapshot */
+#include "pom_boundary.h"
 
 __global__ __launch_bounds__(1024) void pom_reduce_counters_kernel(const int64_t* __restrict__ wc, int64_t n_waves, int64_t* out)
 {

@@ -239,6 +239,92 @@ POM_HD int pom_pack_agent_bad(int32_t bomb_count, int32_t max_bombs, int32_t str
 }
 POM_HD int pom_pack_alive_bad(int32_t alive) { return (alive < POM_PACK_ALIVE_MIN) | (alive > 127); }
 
+POM_HD int32_t pom_sext8(uint32_t v) { return (int32_t)(int8_t)(v & 0xFF); }
+POM_HD int32_t pom_sext16(uint32_t v) { return (int32_t)(int16_t)(v & 0xFFFF); }
+
+/*
+ * The State <-> record mapping, one function per kind of record item and direction: what a field's bits are and what upload
+ * refuses is written here and nowhere else.  `st` is the State as 251 dwords (pom_state.h): board @0, timeStep @121,
+ * aliveAgents @122, agents @123 (6 dwords each), bombs @147 (queue, index @167, count @168), flames @169 (4 dwords a slot,
+ * index @249, count @250).  The pack functions return 1 if a field does not fit (the words they give are then not to be used).
+ * A board cell is pom_cell_encode(st[c], c) / pom_cell_decode above.
+ */
+POM_HD uint32_t pom_pack_timestep(const int32_t* st) { return (uint32_t)st[121]; }
+POM_HD void pom_unpack_timestep(uint32_t w, int32_t* st) { st[121] = (int32_t)w; }
+
+/* Agent i's two words.  Their top bytes carry a scalar of the State each (M0 / M1 in the layout above), and the agent's
+ * verdict covers the scalars it carries: aliveAgents and flames.count with agent 0, bombs.index, bombs.count, flames.index with
+ * agents 1, 2, 3.  Status and ubflags (M1 of agents 1..3) start clear. */
+POM_HD int pom_agent_m0_dword(int i) { return i == 0 ? 122 : i == 1 ? 167 : i == 2 ? 168 : 249; } /* the State dword in M0 of agent i */
+POM_HD int pom_pack_agent(const int32_t* st, int i, uint32_t& a0, uint32_t& a1)
+{
+    const int32_t* a = st + 123 + 6 * i;
+    const int32_t m0 = st[pom_agent_m0_dword(i)], fCnt = st[250];
+    const uint32_t flags = (uint32_t)a[5], m1 = i == 0 ? (uint32_t)fCnt & 0xFFu : 0u;
+    const int kick = (flags & 0xFF) != 0, dead = ((flags >> 8) & 0xFF) != 0;
+    int bad = (a[0] < 0) | (a[0] >= POM_BOARD_SIZE) | (a[1] < 0) | (a[1] >= POM_BOARD_SIZE);
+    bad |= pom_pack_agent_bad(a[2], a[3], a[4]);
+    bad |= i == 0 ? pom_pack_alive_bad(m0) | (fCnt < 0) | (fCnt > 255)
+                  : (m0 < 0) | (i == 2 ? m0 > POM_MAX_BOMBS : m0 >= POM_MAX_BOMBS); /* a count may be 20, an index not */
+    a0 = ((uint32_t)a[0] & 0xF) | (((uint32_t)a[1] & 0xF) << 4) | (((uint32_t)a[2] & 0xFF) << 8) | (kick ? (uint32_t)POM_AG_KICK : 0u) |
+         (dead ? (uint32_t)POM_AG_DEAD : 0u) | (((uint32_t)m0 & 0xFFu) << 24);
+    a1 = ((uint32_t)a[3] & 0xFFFF) | (((uint32_t)a[4] & 0xFF) << 16) | (m1 << 24);
+    return bad;
+}
+/* ... and back; the two padding bytes of the agent come out 0 */
+POM_HD void pom_unpack_agent(uint32_t a0, uint32_t a1, int32_t* st, int i)
+{
+    int32_t* a = st + 123 + 6 * i;
+    a[0] = (int32_t)(a0 & 0xF);
+    a[1] = (int32_t)((a0 >> 4) & 0xF);
+    a[2] = pom_sext8(a0 >> 8);
+    a[3] = pom_sext16(a1);
+    a[4] = (int32_t)((a1 >> 16) & 0xFF);
+    a[5] = (int32_t)(((a0 & POM_AG_KICK) ? 1u : 0u) | ((a0 & POM_AG_DEAD) ? 0x100u : 0u));
+    st[pom_agent_m0_dword(i)] = i == 0 ? pom_sext8(a0 >> 24) : (int32_t)(a0 >> 24);
+    if (i == 0) st[250] = (int32_t)(a1 >> 24);
+}
+
+/* bombs.queue slot k, raw (all 20 slots: stale slots are state) */
+POM_HD uint32_t pom_pack_bomb(const int32_t* st, int k) { return (uint32_t)st[147 + k]; }
+POM_HD void pom_unpack_bomb(uint32_t w, int32_t* st, int k) { st[147 + k] = (int32_t)w; }
+/* The device's own rule on top of the field widths: a LIVE bomb — slot k is one of the bombs.count slots from bombs.index on —
+ * must sit on the board and belong to a real agent, because the tick indexes cells and agents with it (bomb word,
+ * bboard.hpp:261-335: x:4 | y:4 | id:4 @8).  Upload to a batch and pom_step apply it; pom_pack_state alone does not (the host
+ * model packs states that rely on that).  Only asked of a queue whose index and count pom_pack_agent accepts: another is
+ * refused anyway. */
+POM_HD int pom_pack_live_bomb_bad(const int32_t* st, int k)
+{
+    const int32_t b = st[147 + k], bIdx = st[167], bCnt = st[168];
+    const int age = (int)((uint32_t)k - (uint32_t)bIdx) + (k < bIdx ? POM_MAX_BOMBS : 0); /* slot k is the age-th bomb of the queue */
+    const int live = (bIdx >= 0) & (bIdx < POM_MAX_BOMBS) & (age < bCnt);
+    return live & (((b & 0xF) >= POM_BOARD_SIZE) | (((b >> 4) & 0xF) >= POM_BOARD_SIZE) | (((b >> 8) & 0xF) >= POM_AGENT_COUNT));
+}
+
+/* flames.queue slot k, the stale slots too */
+POM_HD int pom_pack_flame(const int32_t* st, int k, uint32_t& w)
+{
+    const int32_t* f = st + 169 + 4 * k;
+    w = (uint32_t)f[0] | ((uint32_t)f[1] << 8) | (((uint32_t)f[2] & 0xFF) << 16) | ((uint32_t)f[3] << 24);
+    return (f[0] < 0) | (f[0] >= POM_BOARD_SIZE) | (f[1] < 0) | (f[1] >= POM_BOARD_SIZE) | (f[2] < -128) | (f[2] > 127) | (f[3] < 0) | (f[3] > 255);
+}
+POM_HD void pom_unpack_flame(uint32_t w, int32_t* st, int k)
+{
+    int32_t* o = st + 169 + 4 * k;
+    o[0] = (int32_t)(w & 0xFF);
+    o[1] = (int32_t)((w >> 8) & 0xFF);
+    o[2] = pom_sext8(w >> 16);
+    o[3] = (int32_t)(w >> 24);
+}
+
+/* the status byte and the flags of META2 as the C-ABI reports them */
+struct PomStatus { int32_t done, winner /* -1: nobody */, draw, ubflags; };
+POM_HD PomStatus pom_status_decode(uint32_t meta2)
+{
+    const uint32_t s8 = (meta2 >> 8) & 0xFF;
+    return {(s8 & POM_ST_DONE) ? 1 : 0, (int32_t)((s8 >> POM_ST_WINNER_SHIFT) & 7) - 1, (s8 & POM_ST_DRAW) ? 1 : 0, (int32_t)(meta2 >> 16)};
+}
+
 /*
  * Pack one boundary State into a record.  `rec` is addressed with a stride so
  * the same code fills a column of a device tile (stride = POM_TILE_ENVS) and a dense
@@ -247,84 +333,67 @@ POM_HD int pom_pack_alive_bad(int32_t alive) { return (alive < POM_PACK_ALIVE_MI
  */
 POM_HD int pom_pack_state(const int32_t* st, uint32_t* rec, int64_t stride, int lane = 0)
 {
-    const int32_t* board = st;                 /* @0    */
-    const int32_t timeStep = st[121];          /* @484  */
-    const int32_t alive = st[122];             /* @488  */
-    const int32_t* agents = st + 123;          /* @492, 6 dwords each */
-    const int32_t* bombs = st + 147;           /* @588  */
-    const int32_t* flames = st + 169;          /* @676  */
     int bad = 0;
-
     for (int c = 0; c < 4 * POM_REC_BOARD_DWORDS; c++) {
-        const int e = c < POM_CELLS ? pom_cell_encode(board[c], c) : 0; /* (the three bytes behind the board: 0) */
+        const int e = c < POM_CELLS ? pom_cell_encode(st[c], c) : 0; /* (the three bytes behind the board: 0) */
         bad |= e < 0;
         pom_rec_set_cell(rec, stride, c, e & 0xFF, lane);
     }
-    rec[POM_REC_TIMESTEP * stride] = (uint32_t)timeStep;
-
-    const int32_t bIdx = bombs[20], bCnt = bombs[21], fIdx = flames[80], fCnt = flames[81];
-    bad |= pom_pack_alive_bad(alive);
-    bad |= (bIdx < 0) | (bIdx >= POM_MAX_BOMBS) | (bCnt < 0) | (bCnt > POM_MAX_BOMBS);
-    bad |= (fIdx < 0) | (fIdx >= POM_MAX_BOMBS) | (fCnt < 0) | (fCnt > 255);
-
-    for (int i = 0; i < POM_AGENT_COUNT; i++) {
-        const int32_t* a = agents + 6 * i;
-        const uint32_t flags = (uint32_t)a[5];
-        const int kick = (flags & 0xFF) != 0, dead = ((flags >> 8) & 0xFF) != 0;
-        bad |= (a[0] < 0) | (a[0] >= POM_BOARD_SIZE) | (a[1] < 0) | (a[1] >= POM_BOARD_SIZE);
-        bad |= pom_pack_agent_bad(a[2], a[3], a[4]);
-        rec[(POM_REC_AGENTS + 2 * i) * stride] =
-            ((uint32_t)a[0] & 0xF) | (((uint32_t)a[1] & 0xF) << 4) | (((uint32_t)a[2] & 0xFF) << 8) | (kick ? (uint32_t)POM_AG_KICK : 0u) | (dead ? (uint32_t)POM_AG_DEAD : 0u);
-        rec[(POM_REC_AGENTS + 2 * i + 1) * stride] = ((uint32_t)a[3] & 0xFFFF) | (((uint32_t)a[4] & 0xFF) << 16);
-    }
-    pom_rec_set_meta(rec, stride, ((uint32_t)alive & 0xFF) | (((uint32_t)bIdx & 0xFF) << 8) | (((uint32_t)bCnt & 0xFF) << 16) | (((uint32_t)fIdx & 0xFF) << 24),
-                     (uint32_t)fCnt & 0xFF); /* status, ubflags start clear */
-    for (int k = 0; k < POM_MAX_BOMBS; k++)
-        rec[(POM_REC_BOMBS + k) * stride] = (uint32_t)bombs[k];
-    for (int k = 0; k < POM_MAX_BOMBS; k++) {
-        const int32_t* f = flames + 4 * k;
-        bad |= (f[0] < 0) | (f[0] >= POM_BOARD_SIZE) | (f[1] < 0) | (f[1] >= POM_BOARD_SIZE); /* also the stale slots */
-        bad |= (f[2] < -128) | (f[2] > 127) | (f[3] < 0) | (f[3] > 255);
-        rec[(POM_REC_FLAMES + k) * stride] =
-            (uint32_t)f[0] | ((uint32_t)f[1] << 8) | (((uint32_t)f[2] & 0xFF) << 16) | ((uint32_t)f[3] << 24);
-    }
+    rec[POM_REC_TIMESTEP * stride] = pom_pack_timestep(st);
+    for (int i = 0; i < POM_AGENT_COUNT; i++)
+        bad |= pom_pack_agent(st, i, rec[(POM_REC_AGENTS + 2 * i) * stride], rec[(POM_REC_AGENTS + 2 * i + 1) * stride]);
+    for (int k = 0; k < POM_MAX_BOMBS; k++) rec[(POM_REC_BOMBS + k) * stride] = pom_pack_bomb(st, k);
+    for (int k = 0; k < POM_MAX_BOMBS; k++) bad |= pom_pack_flame(st, k, rec[(POM_REC_FLAMES + k) * stride]);
     return bad;
 }
 
-POM_HD int32_t pom_sext8(uint32_t v) { return (int32_t)(int8_t)(v & 0xFF); }
-POM_HD int32_t pom_sext16(uint32_t v) { return (int32_t)(int16_t)(v & 0xFFFF); }
-
-/* inverse of pom_pack_state; the two padding bytes of each agent come out 0 */
+/* inverse of pom_pack_state */
 POM_HD void pom_unpack_state(const uint32_t* rec, int64_t stride, int32_t* st, int lane = 0)
 {
     for (int c = 0; c < POM_CELLS; c++) st[c] = pom_cell_decode(pom_rec_cell(rec, stride, c, lane), c);
-    st[121] = (int32_t)rec[POM_REC_TIMESTEP * stride];
-    const uint32_t m = pom_rec_meta(rec, stride), m2 = pom_rec_meta2(rec, stride);
-    st[122] = pom_sext8(m);
-    for (int i = 0; i < POM_AGENT_COUNT; i++) {
-        uint32_t a0 = rec[(POM_REC_AGENTS + 2 * i) * stride], a1 = rec[(POM_REC_AGENTS + 2 * i + 1) * stride];
-        int32_t* a = st + 123 + 6 * i;
-        a[0] = (int32_t)(a0 & 0xF);
-        a[1] = (int32_t)((a0 >> 4) & 0xF);
-        a[2] = pom_sext8(a0 >> 8);
-        a[3] = pom_sext16(a1);
-        a[4] = (int32_t)((a1 >> 16) & 0xFF);
-        a[5] = (int32_t)(((a0 & POM_AG_KICK) ? 1u : 0u) | ((a0 & POM_AG_DEAD) ? 0x100u : 0u));
+    pom_unpack_timestep(rec[POM_REC_TIMESTEP * stride], st);
+    for (int i = 0; i < POM_AGENT_COUNT; i++) pom_unpack_agent(rec[(POM_REC_AGENTS + 2 * i) * stride], rec[(POM_REC_AGENTS + 2 * i + 1) * stride], st, i);
+    for (int k = 0; k < POM_MAX_BOMBS; k++) pom_unpack_bomb(rec[(POM_REC_BOMBS + k) * stride], st, k);
+    for (int k = 0; k < POM_MAX_BOMBS; k++) pom_unpack_flame(rec[(POM_REC_FLAMES + k) * stride], st, k);
+}
+
+/*
+ * The same two directions for ONE State handled by one wavefront (pom_step / pom_env_step, pom_step_one_kernel): the record
+ * is column 0 of a zeroed tile, and lane 0..63 takes cells lane and lane + 64, lanes 0..3 an agent each, lanes 20..39 a bomb
+ * slot, lanes 40..59 a flame slot, lane 61 timeStep.  Packing applies the live-bomb rule, as upload to a batch does.  A lane's
+ * verdict covers its own items; the State is refused if any lane's is set.  The host tests call them for lane = 0..63.
+ */
+enum { POM_LANE_BOMBS = 20, POM_LANE_FLAMES = 40, POM_LANE_SCALARS = 61 };
+POM_HD int pom_pack_lane(const int32_t* st, uint32_t* tile, int lane)
+{
+    int bad = 0;
+    for (int c = lane; c < POM_CELLS; c += 64) { /* (the tile was zeroed: the three bytes past cell 120 stay 0) */
+        const int e = pom_cell_encode(st[c], c);
+        bad |= e < 0;
+        pom_rec_set_cell(tile, POM_TILE_ENVS, c, e & 0xFF);
     }
-    for (int k = 0; k < POM_MAX_BOMBS; k++)
-        st[147 + k] = (int32_t)rec[(POM_REC_BOMBS + k) * stride];
-    st[167] = (int32_t)((m >> 8) & 0xFF);
-    st[168] = (int32_t)((m >> 16) & 0xFF);
-    for (int k = 0; k < POM_MAX_BOMBS; k++) {
-        uint32_t f = rec[(POM_REC_FLAMES + k) * stride];
-        int32_t* o = st + 169 + 4 * k;
-        o[0] = (int32_t)(f & 0xFF);
-        o[1] = (int32_t)((f >> 8) & 0xFF);
-        o[2] = pom_sext8(f >> 16);
-        o[3] = (int32_t)(f >> 24);
+    if (lane == POM_LANE_SCALARS) tile[POM_REC_TIMESTEP * POM_TILE_ENVS] = pom_pack_timestep(st);
+    if (lane < POM_AGENT_COUNT)
+        bad |= pom_pack_agent(st, lane, tile[(POM_REC_AGENTS + 2 * lane) * POM_TILE_ENVS], tile[(POM_REC_AGENTS + 2 * lane + 1) * POM_TILE_ENVS]);
+    if (lane >= POM_LANE_BOMBS && lane < POM_LANE_BOMBS + POM_MAX_BOMBS) {
+        const int k = lane - POM_LANE_BOMBS;
+        tile[(POM_REC_BOMBS + k) * POM_TILE_ENVS] = pom_pack_bomb(st, k);
+        bad |= pom_pack_live_bomb_bad(st, k);
     }
-    st[249] = (int32_t)(m >> 24);
-    st[250] = (int32_t)(m2 & 0xFF);
+    if (lane >= POM_LANE_FLAMES && lane < POM_LANE_FLAMES + POM_MAX_BOMBS)
+        bad |= pom_pack_flame(st, lane - POM_LANE_FLAMES, tile[(POM_REC_FLAMES + lane - POM_LANE_FLAMES) * POM_TILE_ENVS]);
+    return bad;
+}
+POM_HD void pom_unpack_lane(const uint32_t* tile, int32_t* st, int lane)
+{
+    for (int c = lane; c < POM_CELLS; c += 64) st[c] = pom_cell_decode(pom_rec_cell(tile, POM_TILE_ENVS, c), c);
+    if (lane == POM_LANE_SCALARS) pom_unpack_timestep(tile[POM_REC_TIMESTEP * POM_TILE_ENVS], st);
+    if (lane < POM_AGENT_COUNT)
+        pom_unpack_agent(tile[(POM_REC_AGENTS + 2 * lane) * POM_TILE_ENVS], tile[(POM_REC_AGENTS + 2 * lane + 1) * POM_TILE_ENVS], st, lane);
+    if (lane >= POM_LANE_BOMBS && lane < POM_LANE_BOMBS + POM_MAX_BOMBS)
+        pom_unpack_bomb(tile[(POM_REC_BOMBS + lane - POM_LANE_BOMBS) * POM_TILE_ENVS], st, lane - POM_LANE_BOMBS);
+    if (lane >= POM_LANE_FLAMES && lane < POM_LANE_FLAMES + POM_MAX_BOMBS)
+        pom_unpack_flame(tile[(POM_REC_FLAMES + lane - POM_LANE_FLAMES) * POM_TILE_ENVS], st, lane - POM_LANE_FLAMES);
 }
 
 /* Chained launches (pom_chain.h): the tile words count visits in 28-bit fields (tickets in bits 63..36, stored visits in 27..0) and

@@ -170,6 +170,26 @@ uint32_t pom_emul_step(void* state_1004, const int32_t* moves, int env_mode, int
     return ub;
 }
 
+/* pom_emul_step through pom_step's own packer and unpacker (pom_step_one_kernel): the two per-lane functions for lane 0..63 on
+ * column 0 of a zeroed tile, the lanes' verdicts ORed as the kernel's ballot does.  Stricter than pom_pack_state by the live-bomb
+ * rule (pom_pack_live_bomb_bad). */
+uint32_t pom_emul_step_one(void* state_1004, const int32_t* moves, int env_mode, int max_steps, uint32_t* status_io)
+{
+    uint32_t tile[POM_TILE_DWORDS], rec[POM_REC_DWORDS];
+    std::memset(tile, 0, sizeof tile);
+    int bad = 0;
+    for (int lane = 0; lane < 64; lane++) bad |= pom_pack_lane((const int32_t*)state_1004, tile, lane);
+    if (bad) return 0xFFFFFFFFu;
+    pom_col_to_rec(rec, tile, 0, false);
+    const uint32_t ub = pom_emul_step_rec(rec, moves, env_mode, max_steps, status_io);
+    pom_rec_to_col(tile, 0, rec);
+    int32_t out[251];
+    std::memset(out, 0, sizeof out);
+    for (int lane = 0; lane < 64; lane++) pom_unpack_lane(tile, out, lane);
+    std::memcpy(state_1004, out, POM_STATE_BYTES);
+    return ub;
+}
+
 /* the probe (pom_emul_probe.h): cleared before a tick, read after it; cap < 2 makes loop_b_todo blind to double claims, add >= 2
  * makes it select every bomb */
 void pom_emul_probe_reset(void) { g_pom_probe.reset(); }

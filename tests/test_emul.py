@@ -28,7 +28,7 @@ def emul_bins():
         "build/pom_oracle.o", "-o", "build/emul_fuzz")
     run("g++", "-shared", "-pthread", "-o", "build/libpom_emul.so", "build/pom_emul.o", "build/pom_emul_quad.o")
     lib = C.CDLL(os.path.join(BUILD, "libpom_emul.so"))
-    for fn in (lib.pom_emul_step, lib.pom_emul_quad_step):
+    for fn in (lib.pom_emul_step, lib.pom_emul_quad_step, lib.pom_emul_step_one):
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         fn.restype = C.c_uint32
     return lib
@@ -60,7 +60,7 @@ def test_quad_tick_body_matches_oracle_under_random_play(emul_bins, scenario):
         assert _over20(out.stdout) > 0, out.stdout
 
 
-def test_pack_unpack_round_trip_and_rejections(emul_bins):
+def _round_trip_and_rejections(step):
     idle = np.zeros(4, dtype=np.int32)
     boards = pa.make_boards(64, seed=9, kind="stress")
     for i in range(len(boards)):
@@ -68,7 +68,7 @@ def test_pack_unpack_round_trip_and_rejections(emul_bins):
         s["board"][0, 5, 5] = Item.BOMB  # still a legal value
         before = s.copy()
         st = C.c_uint32(1)  # done in ENV mode: the tick is skipped, only pack -> unpack happens
-        assert emul_bins.pom_emul_step(s.ctypes.data, idle.ctypes.data, 1, 0, C.byref(st)) == 0
+        assert step(s.ctypes.data, idle.ctypes.data, 1, 0, C.byref(st)) == 0
         assert s.tobytes() == before.tobytes()
     bad = pa.new_states(1)
     for poke in (lambda s: s["board"].__setitem__((0, 3, 3), 0x5000),          # between the item ranges
@@ -80,7 +80,18 @@ def test_pack_unpack_round_trip_and_rejections(emul_bins):
                  lambda s: s["agents"]["bombStrength"].__setitem__((0, 0), 256)):
         s = bad.copy()
         poke(s)
-        assert emul_bins.pom_emul_step(s.ctypes.data, idle.ctypes.data, 0, 0, None) == 0xFFFFFFFF
+        assert step(s.ctypes.data, idle.ctypes.data, 0, 0, None) == 0xFFFFFFFF
+
+
+def test_pack_unpack_round_trip_and_rejections(emul_bins):
+    _round_trip_and_rejections(emul_bins.pom_emul_step)
+
+
+def test_pack_unpack_round_trip_and_rejections_of_pom_steps_packer(emul_bins):
+    """the same States through the per-lane packer and unpacker of pom_step's kernel (pom_pack_lane / pom_unpack_lane).  That path
+    also applies the live-bomb rule (tests/test_record_edges.py); every live bomb of these boards sits on the board and has an
+    owner, so no verdict differs here"""
+    _round_trip_and_rejections(emul_bins.pom_emul_step_one)
 
 
 def test_tile_layout_of_the_device_buffers(emul_bins):

@@ -122,11 +122,16 @@ def test_device_tick_body_matches_oracle_on_the_edge_corpus(emul_bins, edge_runs
             assert_tick_matches(e.name, t, want, want_ubs, got[t].tobytes(), ubs[t])
 
 
-def _pack_roundtrip(emul_bins, s):  # noqa: F811
+# The two State -> record -> State paths (pomcpp_amd/csrc/pom_packed.h), as exports of the host build with pom_emul_step's signature:
+# pom_pack_state / pom_unpack_state (upload and download of a batch), and the per-lane functions that pom_step's kernel runs.
+PACKERS = {"pom_pack_state": "pom_emul_step", "pom_step": "pom_emul_step_one"}
+
+
+def _pack_roundtrip(emul_bins, s, packer="pom_pack_state"):  # noqa: F811
     """pack -> unpack only (ENV mode on a finished env skips the tick): 0, or 0xFFFFFFFF if refused"""
     idle = np.zeros(4, dtype=np.int32)
     st = C.c_uint32(1)
-    return emul_bins.pom_emul_step(s.ctypes.data, idle.ctypes.data, 1, 0, C.byref(st)) & 0xFFFFFFFF
+    return getattr(emul_bins, PACKERS[packer])(s.ctypes.data, idle.ctypes.data, 1, 0, C.byref(st)) & 0xFFFFFFFF
 
 
 # (field setter, value at the bound, value one step beyond)
@@ -154,19 +159,49 @@ BOUNDS = [
 ]
 
 
-@pytest.mark.parametrize("name,poke,at,beyond", BOUNDS, ids=[b[0] for b in BOUNDS])
-def test_packer_accepts_the_bound_and_refuses_one_beyond(emul_bins, name, poke, at, beyond):  # noqa: F811
+# every bound through both packers (the ids of pom_pack_state's cases are the bounds' names alone)
+BOUND_CASES = [pytest.param(packer, *b, id=b[0] if packer == "pom_pack_state" else f"{b[0]}-{packer}") for packer in PACKERS for b in BOUNDS]
+
+
+@pytest.mark.parametrize("packer,name,poke,at,beyond", BOUND_CASES)
+def test_packer_accepts_the_bound_and_refuses_one_beyond(emul_bins, packer, name, poke, at, beyond):  # noqa: F811
     import pomcpp_amd as pa
     s = pa.make_boards(1, seed=5)
     s["agents"]["pad"] = 0
     poke(s, at)
     before = s.copy()
-    assert _pack_roundtrip(emul_bins, s) == 0, f"{name}={at} refused"
+    assert _pack_roundtrip(emul_bins, s, packer) == 0, f"{name}={at} refused"
     assert s.tobytes() == before.tobytes(), f"{name}={at} does not survive pack / unpack"
     poke(s, beyond)
     before = s.copy()
-    assert _pack_roundtrip(emul_bins, s) == 0xFFFFFFFF, f"{name}={beyond} accepted"
+    assert _pack_roundtrip(emul_bins, s, packer) == 0xFFFFFFFF, f"{name}={beyond} accepted"
     assert s.tobytes() == before.tobytes()
+
+
+# a bomb word (bboard.hpp:261-335: x:4 | y:4 | id:4 @8 | strength:4 @12 | time:4 @16) that fits its record dword like any other
+# but cannot be a bomb of a game: off the board, or of an agent that does not exist
+OFF_BOARD_BOMBS = [("x_11", 11 | (3 << 4) | (1 << 12) | (5 << 16)), ("y_11", 3 | (11 << 4) | (1 << 12) | (5 << 16)),
+                   ("agent_4", 3 | (3 << 4) | (4 << 8) | (1 << 12) | (5 << 16))]
+
+
+@pytest.mark.parametrize("name,word", OFF_BOARD_BOMBS, ids=[b[0] for b in OFF_BOARD_BOMBS])
+def test_live_bomb_rule_is_what_pom_steps_packer_refuses_beyond_pom_pack_state(emul_bins, name, word):  # noqa: F811
+    """The live-bomb rule (pom_pack_live_bomb_bad): a bomb in one of the bombs.count slots from bombs.index on must sit on the
+    board and belong to a real agent.  It is the ONE place where pom_step's packer (and upload to a batch) is stricter than
+    pom_pack_state, which keeps the bomb queue raw: the same word in a stale slot passes both, in a live slot only pom_pack_state."""
+    import pomcpp_amd as pa
+    s = pa.make_boards(1, seed=5)
+    s["agents"]["pad"] = 0
+    s["bombs_index"][0], s["bombs_count"][0] = 18, 3  # live: slots 18, 19, 0 (the queue wraps)
+    s["bombs_queue"][0, [18, 19, 0]] = 3 | (3 << 4) | (1 << 12) | (5 << 16)
+    for slot, live in ((1, False), (17, False), (18, True), (0, True)):
+        t = s.copy()
+        t["bombs_queue"][0, slot] = word
+        for packer in PACKERS:
+            before = t.copy()
+            refused = live and packer == "pom_step"
+            assert _pack_roundtrip(emul_bins, t, packer) == (0xFFFFFFFF if refused else 0), f"{packer}: {name} in slot {slot} (live: {live})"
+            assert t.tobytes() == before.tobytes(), f"{packer}: {name} in slot {slot} altered"
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU
