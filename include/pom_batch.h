@@ -292,7 +292,8 @@ int pom_batch_device_view(PomBatch* h, void** base, int64_t* n_pad, int32_t* rec
  *    0  board: the small numbers of the reference's Item enum (bboard.hpp:54-71) — 0 passage, 1 rigid, 2 wood (any flag), 3 bomb,
  *       4 flames, 5 fog, 6 extra-bomb, 7 incr-range, 8 kick, 9 agent dummy, 10..13 agents 0..3; 255 for anything else
  *    1 2 3  bomb strength, life, direction (planes 12, 13, 14 above)        4  flame life (plane 15 above)
- * per_agent must be 0 (agents are named by id; agent_attrs says who is where).
+ * per_agent must be 0 (agents are named by id; agent_attrs says who is where).  The agents' own FOGGED views of either form:
+ * PomViewSpec below.
  */
 enum { POM_OBS_U8 = 0, POM_OBS_F16 = 1, POM_OBS_F32 = 2, POM_OBS_CODES = 3 };
 enum { POM_OBS_PLANES = 16, POM_OBS_CODE_PLANES = 5, POM_OBS_AGENT_ATTRS = 8, POM_OBS_ENV_ATTRS = 4 };
@@ -319,6 +320,49 @@ int pom_batch_step_device_observe(PomBatch* h, const int32_t* moves_dev, void* p
  * Quad shape only (POM_E_ARG otherwise).  bench.py: other_configs.closed_loop_65536_envs. */
 int pom_batch_step_device_range(PomBatch* h, int64_t first, int64_t count, const int32_t* moves_dev, void* stream, void* planes_dev,
                                 int32_t dtype, int32_t per_agent, int32_t* agent_attrs_dev, int32_t* env_attrs_dev);
+/*
+ * PER-AGENT FOGGED VIEWS: the observation a Pommerman agent really gets — the board through a window around itself, fog elsewhere —
+ * for all four agents of every env, written by the export's kernels (no second pass over the planes).  The three calls below are
+ * pom_batch_observe, pom_batch_step_device_observe and pom_batch_step_device_range with a PomViewSpec in place of their output
+ * arguments; the calls above keep their signatures and behaviour.
+ * Viewer and window: view v of env e belongs to agent v, alive or dead (as per_agent = 1 writes dead agents' views too).  Its window is
+ *          the set of cells with |x - x_v| <= view_radius and |y - y_v| <= view_radius, x_v, y_v the agent's position as agent_attrs
+ *          reports it (a dead agent looks out from where it died), clipped by the board.  No other special cases.  view_radius 4 is
+ *          Pommerman's 9x9 window; 10 fogs nothing.
+ * planes:  POM_OBS_U8 / _F16 / _F32: [n][4][16][11][11].  Inside the window exactly what pom_batch_observe(per_agent = 1) writes for
+ *          that view (planes 8..11 rotated: 8 = the viewer); outside it all 16 planes are 0 — planes 0..11 are one-hot on every real
+ *          cell, so an all-zero cell is unambiguously fog.
+ *          POM_OBS_CODES: uint8 [n][4][5][11][11].  Inside the window the five bytes pom_batch_observe(POM_OBS_CODES) writes (agents keep
+ *          their absolute codes 10..13 in every view); outside it the board plane is 5 (Item::FOG) and planes 1..4 are 0.
+ *          Alignment as for per_agent = 1: 4 x the element size (an env's four views are 2,420 / 7,744 elements: every env starts on
+ *          that boundary).
+ * viewer_attrs (nullable): int32 [n][4][12], rows of 48 bytes, the pointer 16-byte aligned — what a Pommerman observation carries
+ *          beside the board, and nothing about the others that the board does not show:
+ *          0..7 agent v's own row of agent_attrs (x, y, alive, ammo, bombCount, maxBombCount, bombStrength, canKick), 8 9 10 the alive
+ *          flags of agents (v+1)%4, (v+2)%4, (v+3)%4, 11 timeStep.
+ * env_attrs (nullable): as pom_batch_observe — done, winner and the rest are public.
+ * POM_E_ARG (with a pom_last_error text): a null spec (pom_batch_step_device_range_view: NULL = no observation, the call is
+ *          pom_batch_step_device_range without planes), struct_size != sizeof(PomViewSpec) (POM_VIEW_SPEC_SIZE), view_radius outside
+ *          0..10, reserved_ != 0, an unknown dtype, a null or misaligned planes_dev, misaligned attribute pointers; nothing is written.
+ * Ordering and settling: stream order, the settling of chained launches and the two launches of the one-lane-per-env shapes exactly as
+ *          in the three calls above; with POM_RESET_AT_END an env that has just finished shows views of its next start state.  The fused
+ *          and the range call equal the step followed by pom_batch_observe_view, bit for bit.
+ */
+enum { POM_OBS_VIEWER_ATTRS = 12, POM_VIEW_RADIUS_MAX = 10, POM_VIEW_SPEC_SIZE = 40 };
+typedef struct PomViewSpec {
+    int32_t struct_size;       /* = sizeof(PomViewSpec) */
+    int32_t dtype;             /* POM_OBS_U8 / _F16 / _F32 / _CODES */
+    int32_t view_radius;       /* 0..10, Chebyshev */
+    int32_t reserved_;         /* must be 0 */
+    void* planes_dev;          /* [n][4][16][11][11] of dtype, or uint8 [n][4][5][11][11] for POM_OBS_CODES */
+    int32_t* viewer_attrs_dev; /* nullable: int32 [n][4][POM_OBS_VIEWER_ATTRS] */
+    int32_t* env_attrs_dev;    /* nullable: as pom_batch_observe */
+} PomViewSpec;
+int pom_batch_observe_view(PomBatch* h, const PomViewSpec* spec);
+int pom_batch_step_device_observe_view(PomBatch* h, const int32_t* moves_dev, const PomViewSpec* spec);
+int pom_batch_step_device_range_view(PomBatch* h, int64_t first, int64_t count, const int32_t* moves_dev, void* stream,
+                                     const PomViewSpec* spec);
+
 /* A stand-in for a learned policy in measurements and tests of the closed loop (NOT part of the stepper): one launch on `stream`
  * that writes Move[4] of the envs [first, first + count) into moves_dev (int32 [n][4]).  codes_dev != NULL: the POM_OBS_CODES
  * observation of the batch (uint8 [n][5][11][11]) — every byte of the range's observations is read and the moves depend on them;

@@ -50,6 +50,19 @@ class _Options(C.Structure):
     ]
 
 
+class _ViewSpec(C.Structure):
+    """PomViewSpec (include/pom_batch.h): where the fogged per-agent views go"""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("dtype", C.c_int32), ("view_radius", C.c_int32), ("reserved_", C.c_int32),
+        ("planes_dev", C.c_void_p), ("viewer_attrs_dev", C.c_void_p), ("env_attrs_dev", C.c_void_p),
+    ]
+
+
+def _view_spec(code: int, radius: int, planes, viewer_attrs=None, env_attrs=None) -> _ViewSpec:
+    ptr = lambda t: None if t is None else t.data_ptr() if hasattr(t, "data_ptr") else int(t)  # noqa: E731
+    return _ViewSpec(C.sizeof(_ViewSpec), code, int(radius), 0, ptr(planes), ptr(viewer_attrs), ptr(env_attrs))
+
+
 def library_path() -> str:
     return os.environ.get("POM_LIB") or os.path.join(_HERE, "libpom_batch.so")  # POM_LIB: experimental builds only
 
@@ -85,6 +98,10 @@ def load_library() -> C.CDLL:
     lib.pom_batch_observe.argtypes = [P, VP, I32, I32, VP, VP]
     if not os.environ.get("POM_LIB") or hasattr(lib, "pom_batch_step_device_observe"):
         lib.pom_batch_step_device_observe.argtypes = [P, VP, VP, I32, I32, VP, VP]
+    if not os.environ.get("POM_LIB") or hasattr(lib, "pom_batch_observe_view"):
+        lib.pom_batch_observe_view.argtypes = [P, C.POINTER(_ViewSpec)]
+        lib.pom_batch_step_device_observe_view.argtypes = [P, VP, C.POINTER(_ViewSpec)]
+        lib.pom_batch_step_device_range_view.argtypes = [P, I64, I64, VP, VP, C.POINTER(_ViewSpec)]
     if hasattr(lib, "pom_batch_step_device_range"):
         lib.pom_batch_step_device_range.argtypes = [P, I64, I64, VP, VP, VP, I32, I32, VP, VP]
         lib.pom_bench_policy.argtypes = [VP, VP, I64, I64, C.c_uint32, VP]
@@ -362,15 +379,35 @@ class BatchEnvironment:
             raise ValueError("a raw device address needs `ticks`")
         _check(self._lib, self._lib.pom_batch_step_device_many(self._h, int(moves), int(ticks)))
 
-    def step_device_range(self, first: int, count: int, moves, stream=None, codes=None, planes=None) -> None:
+    def step_device_range(self, first: int, count: int, moves, stream=None, codes=None, planes=None, view_radius: Optional[int] = None,
+                          viewer_attrs=None, env_attrs=None) -> None:
         """Closed-loop stepping (pom_batch_step_device_range): one tick for the envs [first, first + count) — whole tiles of 16 — as ONE
         launch on `stream` (a raw hipStream_t / torch stream; None: the handle's stream), Move[4] from `moves` (int32[n, 4] device tensor
         or address, indexed by env).  `codes` (uint8[n, 5, 11, 11]) or `planes` (uint8[n, 16, 11, 11]): the observation of those envs after
         the tick, written by the same launch.  Nothing is forked or joined: the stream orders the call; sync() the handle once before a loop
-        of these (and before capturing them into a graph)."""
+        of these (and before capturing them into a graph).  `view_radius`: the four agents' fogged views instead
+        (pom_batch_step_device_range_view) — `codes` uint8[n, 4, 5, 11, 11] or `planes` [n, 4, 16, 11, 11] of uint8 / float16 / float32, and
+        optionally `viewer_attrs` int32[n, 4, 12] and `env_attrs` int32[n, 4]."""
         st = getattr(stream, "cuda_stream", stream)
         mv = moves.data_ptr() if hasattr(moves, "data_ptr") else int(moves)
         out, code = (codes, 3) if codes is not None else (planes, 0)
+        if view_radius is None and (viewer_attrs is not None or env_attrs is not None):
+            raise ValueError("viewer_attrs / env_attrs are written with the fogged views only: pass view_radius")
+        if view_radius is not None:
+            if out is None:
+                raise ValueError("view_radius needs `codes` or `planes` to write the views to")
+            if not 0 <= int(view_radius) <= 10:
+                raise ValueError("view_radius must be 0..10")
+            if codes is None:
+                code = {"torch.uint8": 0, "torch.float16": 1, "torch.float32": 2}.get(str(getattr(planes, "dtype", "torch.uint8")))
+                if code is None:
+                    raise ValueError("planes must be uint8, float16 or float32")
+            for t, shape in ((out, (self.n, 4, 5 if codes is not None else 16, 11, 11)), (viewer_attrs, (self.n, 4, 12)), (env_attrs, (self.n, 4))):
+                if hasattr(t, "shape") and (tuple(t.shape) != shape or not t.is_contiguous()):
+                    raise ValueError(f"expected a contiguous tensor of shape {shape}, got {tuple(t.shape)}")
+            spec = _view_spec(code, view_radius, out, viewer_attrs, env_attrs)
+            _check(self._lib, self._lib.pom_batch_step_device_range_view(self._h, int(first), int(count), mv, st, C.byref(spec)))
+            return
         _check(self._lib, self._lib.pom_batch_step_device_range(self._h, int(first), int(count), mv, st, out.data_ptr() if out is not None else None,
                                                                 code, 0, None, None))
 
@@ -442,31 +479,45 @@ class BatchEnvironment:
         return self.status()["winner"]
 
     # ---- observation export ---------------------------------------------------------
-    def step_device_observe(self, moves, per_agent: bool = False, dtype: str = "uint8", attrs: bool = True, out=None):
-        """step_device(moves) and observe(...) as ONE launch (pom_batch_step_device_observe): returns what observe() would."""
-        return self.observe(per_agent=per_agent, dtype=dtype, attrs=attrs, out=out, _step_moves=moves)
+    def step_device_observe(self, moves, per_agent: Optional[bool] = None, dtype: str = "uint8", attrs: bool = True, out=None,
+                            view_radius: Optional[int] = None):
+        """step_device(moves) and observe(...) as ONE launch (pom_batch_step_device_observe / _view): returns what observe() would."""
+        return self.observe(per_agent=per_agent, dtype=dtype, attrs=attrs, out=out, view_radius=view_radius, _step_moves=moves)
 
-    def observe(self, per_agent: bool = False, dtype: str = "uint8", attrs: bool = True, out=None, _step_moves=None):
+    def observe(self, per_agent: Optional[bool] = None, dtype: str = "uint8", attrs: bool = True, out=None,
+                view_radius: Optional[int] = None, _step_moves=None):
         """Planes of every env as torch tensors on the handle's device, written by one kernel on the handle's stream
         (pom_batch_observe; plane list in include/pom_batch.h).  Returns (planes, agent_attrs, env_attrs): planes
         [n,16,11,11] or [n,4,16,11,11]; agent_attrs int32 [n,4,8]; env_attrs int32 [n,4] (None, None if attrs=False).
         dtype "codes": the compact form, uint8 [n,5,11,11] = board codes 0..13, bomb strength / life / direction, flame life
         (POM_OBS_CODES; no per-agent view).  `out` reuses a planes tensor from an earlier call.  torch is only the owner of the
-        device memory here."""
+        device memory here.
+        view_radius (0..10; 4 = Pommerman's 9x9 window): partial observability (pom_batch_observe_view) — every agent's view through
+        the window around itself, fog elsewhere.  Returns (planes, viewer_attrs, env_attrs): planes [n,4,16,11,11], all-zero cells
+        outside the window, or for "codes" [n,4,5,11,11] with board code 5 (fog) outside it; viewer_attrs int32 [n,4,12] = the
+        viewer's own agent_attrs row, the alive flags of the next three agents, the time step.  per_agent is implied."""
         import torch
+        if view_radius is not None and per_agent is not None and not per_agent:
+            raise ValueError("view_radius gives every agent its own view: per_agent=False contradicts it")
+        per_agent = bool(per_agent)
         kinds = {"uint8": (0, torch.uint8), "float16": (1, torch.float16), "float32": (2, torch.float32), "codes": (3, torch.uint8)}
         if dtype not in kinds:
             raise ValueError(f"dtype must be one of {sorted(kinds)}")
-        if dtype == "codes" and per_agent:
-            raise ValueError("the codes layout has no per-agent view")
+        if dtype == "codes" and per_agent and view_radius is None:
+            raise ValueError("the codes layout has no per-agent view (but for the fogged ones: view_radius)")
+        view = view_radius is not None
+        if view and not 0 <= int(view_radius) <= 10:
+            raise ValueError("view_radius must be 0..10")
         code, tdt = kinds[dtype]
         dev = torch.device("cuda", self.device)
-        shape = (self.n, 5, 11, 11) if dtype == "codes" else (self.n, 4, 16, 11, 11) if per_agent else (self.n, 16, 11, 11)
+        shape = (self.n, 5, 11, 11) if dtype == "codes" else (self.n, 4, 16, 11, 11) if per_agent or view else (self.n, 16, 11, 11)
+        if view:
+            shape = (self.n, 4) + shape[-3:]
         if out is None:
             out = torch.empty(shape, dtype=tdt, device=dev)
         elif tuple(out.shape) != shape or out.dtype != tdt or not out.is_contiguous() or out.device != dev:
             raise ValueError("out does not match the requested view")
-        a_attrs = torch.empty((self.n, 4, 8), dtype=torch.int32, device=dev) if attrs else None
+        a_attrs = torch.empty((self.n, 4, 12 if view else 8), dtype=torch.int32, device=dev) if attrs else None
         e_attrs = torch.empty((self.n, 4), dtype=torch.int32, device=dev) if attrs else None
         # the kernel runs on the handle's stream, the tensors live on torch's current stream: order the two with events
         mine, theirs = torch.cuda.ExternalStream(self.stream_handle(), device=dev), torch.cuda.current_stream(dev)
@@ -475,6 +526,13 @@ class BatchEnvironment:
         if _step_moves is not None:
             if tuple(_step_moves.shape) != (self.n, 4) or "int32" not in str(_step_moves.dtype) or not _step_moves.is_contiguous():
                 raise ValueError(f"moves must be a contiguous int32[{self.n}, 4] device tensor")
+        if view:
+            spec = _view_spec(code, view_radius, out, a_attrs, e_attrs)
+            if _step_moves is not None:
+                _check(self._lib, self._lib.pom_batch_step_device_observe_view(self._h, _step_moves.data_ptr(), C.byref(spec)))
+            else:
+                _check(self._lib, self._lib.pom_batch_observe_view(self._h, C.byref(spec)))
+        elif _step_moves is not None:
             _check(self._lib, self._lib.pom_batch_step_device_observe(self._h, _step_moves.data_ptr(), out.data_ptr(), code, int(per_agent),
                                                                       a_attrs.data_ptr() if attrs else None,
                                                                       e_attrs.data_ptr() if attrs else None))

@@ -716,15 +716,10 @@ static int observe_args(const char* who, const void* planes_dev, int32_t dtype, 
     return POM_OK;
 }
 
-int pom_batch_observe(PomBatch* h, void* planes_dev, int32_t dtype, int32_t per_agent, int32_t* agent_attrs_dev,
-                      int32_t* env_attrs_dev)
+/* the export kernels' arguments for the whole batch (viewer_attrs / view_radius: the fogged views only) */
+static ObserveParams observe_params(const PomBatch* h, void* planes_dev, int32_t dtype, int32_t per_agent, int32_t* agent_attrs_dev,
+                                    int32_t* env_attrs_dev, int32_t* viewer_attrs_dev = nullptr, int32_t view_radius = 0)
 {
-    if (!h) return POM_E_ARG;
-    if (int ar = observe_args("pom_batch_observe", planes_dev, dtype, per_agent, agent_attrs_dev, env_attrs_dev)) return ar;
-    HIPCHK(hipSetDevice(h->device));
-    /* quiesce, not only join: after chained launches a tile some visitor could not play is caught up first (chain_settle; free
-     * while no chained launch has been issued since the last check) — the planes always describe the state a download returns */
-    if (int jr = quiesce(h)) return jr;
     ObserveParams p;
     p.state = h->state;
     p.n = h->n;
@@ -735,6 +730,21 @@ int pom_batch_observe(PomBatch* h, void* planes_dev, int32_t dtype, int32_t per_
     p.env_attrs = env_attrs_dev;
     p.dtype = dtype;
     p.per_agent = per_agent ? 1 : 0;
+    p.viewer_attrs = viewer_attrs_dev;
+    p.view_radius = view_radius;
+    return p;
+}
+
+int pom_batch_observe(PomBatch* h, void* planes_dev, int32_t dtype, int32_t per_agent, int32_t* agent_attrs_dev,
+                      int32_t* env_attrs_dev)
+{
+    if (!h) return POM_E_ARG;
+    if (int ar = observe_args("pom_batch_observe", planes_dev, dtype, per_agent, agent_attrs_dev, env_attrs_dev)) return ar;
+    HIPCHK(hipSetDevice(h->device));
+    /* quiesce, not only join: after chained launches a tile some visitor could not play is caught up first (chain_settle; free
+     * while no chained launch has been issued since the last check) — the planes always describe the state a download returns */
+    if (int jr = quiesce(h)) return jr;
+    const ObserveParams p = observe_params(h, planes_dev, dtype, per_agent, agent_attrs_dev, env_attrs_dev);
     pom_observe_kernel<<<dim3((unsigned)((h->n + 15) / 16)), dim3(64), 0, h->stream>>>(p);
     HIPCHK(hipGetLastError());
     return POM_OK;
@@ -750,13 +760,12 @@ int pom_batch_step_device_observe(PomBatch* h, const int32_t* moves_dev, void* p
         if (int rc = pom_batch_step_device(h, moves_dev)) return rc;
         return pom_batch_observe(h, planes_dev, dtype, per_agent, agent_attrs_dev, env_attrs_dev);
     }
-    const PomObserveOut obs = {planes_dev, agent_attrs_dev, env_attrs_dev, dtype, per_agent ? 1 : 0};
+    const PomObserveOut obs = {planes_dev, agent_attrs_dev, env_attrs_dev, dtype, per_agent ? 1 : 0, 0, 0, nullptr};
     return launch_step(h, moves_dev, 0, 0, 1, false, true, &obs);
 }
 
 /* closed-loop stepping: one tick for a range of whole tiles, one launch on the caller's stream, nothing forked or joined */
-int pom_batch_step_device_range(PomBatch* h, int64_t first, int64_t count, const int32_t* moves_dev, void* stream, void* planes_dev,
-                                int32_t dtype, int32_t per_agent, int32_t* agent_attrs_dev, int32_t* env_attrs_dev)
+static int range_args(PomBatch* h, int64_t first, int64_t count, const int32_t* moves_dev)
 {
     int rc = check_range(h, first, count);
     if (rc || !moves_dev) return rc ? rc : POM_E_ARG;
@@ -765,21 +774,93 @@ int pom_batch_step_device_range(PomBatch* h, int64_t first, int64_t count, const
                  (long long)count);
         return POM_E_ARG;
     }
-    if (planes_dev)
-        if (int ar = observe_args("pom_batch_step_device_range", planes_dev, dtype, per_agent, agent_attrs_dev, env_attrs_dev)) return ar;
+    return POM_OK;
+}
+static int launch_range(PomBatch* h, int64_t first, int64_t count, const int32_t* moves_dev, void* stream, const PomObserveOut* obs)
+{
     if (count == 0) return POM_OK;
     HIPCHK(hipSetDevice(h->device));
     if (int qr = quiesce(h)) return qr; /* (free, and no runtime call at all, once the handle is settled: what a graph capture needs) */
     StepParams p;
-    const PomObserveOut obs = {planes_dev, agent_attrs_dev, env_attrs_dev, dtype, per_agent ? 1 : 0};
-    if (int fr = fill_params(h, p, moves_dev, 0, 0, 1, planes_dev ? &obs : nullptr)) return fr;
+    if (int fr = fill_params(h, p, moves_dev, 0, 0, 1, obs)) return fr;
     p.block0 = first / 16;
     p.block_end = (first + count + 15) / 16;
-    const void* kernel = reinterpret_cast<const void*>(step_kernel(h, false, 1, false, planes_dev != nullptr));
+    const void* kernel = reinterpret_cast<const void*>(step_kernel(h, false, 1, false, obs != nullptr, obs && obs->view));
     void* args[1] = {&p};
     HIPCHK(hipLaunchKernel(kernel, dim3((unsigned)((p.block_end - p.block0 + POM_WPB - 1) / POM_WPB)), dim3(64 * POM_WPB), args, 0,
                            stream ? (hipStream_t)stream : h->stream));
     return POM_OK;
+}
+int pom_batch_step_device_range(PomBatch* h, int64_t first, int64_t count, const int32_t* moves_dev, void* stream, void* planes_dev,
+                                int32_t dtype, int32_t per_agent, int32_t* agent_attrs_dev, int32_t* env_attrs_dev)
+{
+    if (int rc = range_args(h, first, count, moves_dev)) return rc;
+    if (planes_dev)
+        if (int ar = observe_args("pom_batch_step_device_range", planes_dev, dtype, per_agent, agent_attrs_dev, env_attrs_dev)) return ar;
+    const PomObserveOut obs = {planes_dev, agent_attrs_dev, env_attrs_dev, dtype, per_agent ? 1 : 0, 0, 0, nullptr};
+    return launch_range(h, first, count, moves_dev, stream, planes_dev ? &obs : nullptr);
+}
+
+/* ---- the fogged views (pom_batch.h PomViewSpec): the three observation calls with the four agents' windows ---- */
+static_assert(sizeof(PomViewSpec) == POM_VIEW_SPEC_SIZE, "pom_batch.h states the size");
+static int view_args(const char* who, const PomViewSpec* s)
+{
+    const char* what = nullptr;
+    if (!s) what = "the spec is NULL";
+    else if (s->struct_size != (int32_t)sizeof(PomViewSpec)) what = "struct_size is not sizeof(PomViewSpec)";
+    else if (s->dtype < POM_OBS_U8 || s->dtype > POM_OBS_CODES) what = "unknown dtype";
+    else if (s->view_radius < 0 || s->view_radius > POM_VIEW_RADIUS_MAX) what = "view_radius must be 0..10";
+    else if (s->reserved_ != 0) what = "reserved_ must be 0";
+    else if (!s->planes_dev) what = "planes_dev is NULL";
+    if (what) {
+        snprintf(g_err, sizeof g_err, "%s: %s", who, what);
+        return POM_E_ARG;
+    }
+    /* the alignment rule of per_agent = 1 (observe_args): 4 x the element size, an env's four views start on that boundary */
+    const uintptr_t esz = s->dtype == POM_OBS_F16 ? 2 : s->dtype == POM_OBS_F32 ? 4 : 1;
+    if (((uintptr_t)s->planes_dev & (4 * esz - 1)) || ((uintptr_t)s->viewer_attrs_dev & 15) || ((uintptr_t)s->env_attrs_dev & 15)) {
+        snprintf(g_err, sizeof g_err, "%s: planes_dev must be aligned to 4 elements, the attribute pointers to 16 bytes", who);
+        return POM_E_ARG;
+    }
+    return POM_OK;
+}
+static PomObserveOut view_out(const PomViewSpec* s)
+{
+    return PomObserveOut{s->planes_dev, nullptr, s->env_attrs_dev, s->dtype, 1, 1, s->view_radius, s->viewer_attrs_dev};
+}
+
+int pom_batch_observe_view(PomBatch* h, const PomViewSpec* spec)
+{
+    if (!h) return POM_E_ARG;
+    if (int ar = view_args("pom_batch_observe_view", spec)) return ar;
+    HIPCHK(hipSetDevice(h->device));
+    if (int jr = quiesce(h)) return jr; /* (as pom_batch_observe) */
+    const ObserveParams p = observe_params(h, spec->planes_dev, spec->dtype, 1, nullptr, spec->env_attrs_dev, spec->viewer_attrs_dev, spec->view_radius);
+    pom_observe_view_kernel<<<dim3((unsigned)((h->n + 15) / 16)), dim3(64), 0, h->stream>>>(p);
+    HIPCHK(hipGetLastError());
+    return POM_OK;
+}
+
+int pom_batch_step_device_observe_view(PomBatch* h, const int32_t* moves_dev, const PomViewSpec* spec)
+{
+    if (!h || !moves_dev) return POM_E_ARG;
+    if (int ar = view_args("pom_batch_step_device_observe_view", spec)) return ar;
+    HIPCHK(hipSetDevice(h->device));
+    if (!h->quad) { /* the one-lane-per-env shapes have no fused twin: the two launches */
+        if (int rc = pom_batch_step_device(h, moves_dev)) return rc;
+        return pom_batch_observe_view(h, spec);
+    }
+    const PomObserveOut obs = view_out(spec);
+    return launch_step(h, moves_dev, 0, 0, 1, false, true, &obs);
+}
+
+int pom_batch_step_device_range_view(PomBatch* h, int64_t first, int64_t count, const int32_t* moves_dev, void* stream, const PomViewSpec* spec)
+{
+    if (!spec) return pom_batch_step_device_range(h, first, count, moves_dev, stream, nullptr, 0, 0, nullptr, nullptr);
+    if (int rc = range_args(h, first, count, moves_dev)) return rc;
+    if (int ar = view_args("pom_batch_step_device_range_view", spec)) return ar;
+    const PomObserveOut obs = view_out(spec);
+    return launch_range(h, first, count, moves_dev, stream, &obs);
 }
 
 /* the stand-in policy of the closed-loop measurements (pom_batch.h): a workgroup takes 64 envs, reads their observations — 64 x 605

@@ -212,6 +212,10 @@ struct PomObserveOut { /* pom_batch_step_device_observe / _range: where the fuse
     int32_t* agent_attrs;
     int32_t* env_attrs;
     int32_t dtype, per_agent;
+    /* the fogged views (pom_batch_step_device_observe_view / _range_view): view = 1 picks the VIEW kernels (launch_parts, launch_range),
+     * which write viewer_attrs and ignore agent_attrs / per_agent; the other kernels ignore these */
+    int32_t view, view_radius;
+    int32_t* viewer_attrs;
 };
 static int fill_params(PomBatch* h, StepParams& p, const int32_t* moves_dev, uint64_t seed, int dist, int ticks,
                        const PomObserveOut* obs = nullptr)
@@ -251,6 +255,8 @@ static int fill_params(PomBatch* h, StepParams& p, const int32_t* moves_dev, uin
     p.obs_env_attrs = obs ? obs->env_attrs : nullptr;
     p.obs_dtype = obs ? obs->dtype : 0;
     p.obs_per_agent = obs ? obs->per_agent : 0;
+    p.obs_viewer_attrs = obs && obs->view ? obs->viewer_attrs : nullptr;
+    p.obs_view_radius = obs && obs->view ? obs->view_radius : 0;
 #if defined(POM_DIAG)
     if (!h->diag) {
         HIPCHK(hipMalloc((void**)&h->diag, (size_t)h->n_waves * POM_PH_N * 8));
@@ -263,7 +269,8 @@ static int fill_params(PomBatch* h, StepParams& p, const int32_t* moves_dev, uin
 
 /* Which instantiation of pom_step_kernel a launch runs: the one table of them.  Quad shape (the default): one instantiation per
  * combination of fresh boards / fused policy / reset at the end for launches of ONE tick — plain, chained (pom_chain.h; the plain
- * one with the same flags is its twin, what chain_settle replays a tick with) and, for explicit moves, with the fused observation —
+ * one with the same flags is its twin, what chain_settle replays a tick with) and, for explicit moves, with the fused observation or the
+ * fused fogged views —
  * and the plain replay kernel for launches of several ticks: the other several-tick combinations would need more than the 128 VGPRs
  * that keep four wavefronts on a SIMD (12-116 B of scratch each, round 2), so those modes always run one tick per launch
  * (max_ticks_per_launch).  The one-lane-per-env shapes: fresh boards or not.  Combinations without a kernel of their own are kept
@@ -275,7 +282,7 @@ static int max_ticks_per_launch(const PomBatch* h, bool policy)
 {
     return (!h->quad || (!policy && !runs_fresh(h) && !runs_at_end(h))) ? INT_MAX : 1;
 }
-static PomStepKernel step_kernel(const PomBatch* h, bool policy, int ticks_per_launch, bool chained, bool observe)
+static PomStepKernel step_kernel(const PomBatch* h, bool policy, int ticks_per_launch, bool chained, bool observe, bool view = false)
 {
     /* (listed in the order the kernels have always been emitted in: the order reaches the register allocation — 118 instead of
      * 119 VGPRs for the fresh-board kernel of 16 envs per wavefront, one lane each, when listed otherwise) */
@@ -285,6 +292,7 @@ static PomStepKernel step_kernel(const PomBatch* h, bool policy, int ticks_per_l
         PomStepKernel one_lane[3][2]; /* [64 / 32 / 16 envs per wavefront][fresh ? 0 : 1] */
         PomStepKernel observe[4];     /* [fresh * 2 + at_end] (explicit moves: no policy) */
         PomStepKernel chained[8];     /* as one_tick */
+        PomStepKernel view[4];        /* as observe: the fogged views (listed last: the kernels before it are emitted as they always were) */
     } k = {
         {pom_step_kernel<16, 4, false, false, false, true>, pom_step_kernel<16, 4, false, false, true, true>,
          pom_step_kernel<16, 4, false, true, false, true>, pom_step_kernel<16, 4, false, true, true, true>,
@@ -299,10 +307,12 @@ static PomStepKernel step_kernel(const PomBatch* h, bool policy, int ticks_per_l
         {pom_step_kernel<16, 4, false, false, false, true, true>, pom_step_kernel<16, 4, false, false, true, true, true>,
          pom_step_kernel<16, 4, false, true, false, true, true>, pom_step_kernel<16, 4, false, true, true, true, true>,
          pom_step_kernel<16, 4, true, false, false, true, true>, pom_step_kernel<16, 4, true, false, true, true, true>,
-         pom_step_kernel<16, 4, true, true, false, true, true>, pom_step_kernel<16, 4, true, true, true, true, true>}};
+         pom_step_kernel<16, 4, true, true, false, true, true>, pom_step_kernel<16, 4, true, true, true, true, true>},
+        {pom_step_kernel<16, 4, false, false, false, true, false, true, true>, pom_step_kernel<16, 4, false, false, true, true, false, true, true>,
+         pom_step_kernel<16, 4, true, false, false, true, false, true, true>, pom_step_kernel<16, 4, true, false, true, true, false, true, true>}};
     const int fresh = runs_fresh(h) ? 1 : 0, at_end = runs_at_end(h) ? 1 : 0;
     if (!h->quad) return k.one_lane[h->epw == 64 ? 0 : h->epw == 32 ? 1 : 2][1 - fresh];
-    if (observe) return k.observe[2 * fresh + at_end];
+    if (observe) return (view ? k.view : k.observe)[2 * fresh + at_end];
     if (ticks_per_launch != 1) return k.several_ticks;
     return (chained ? k.chained : k.one_tick)[4 * fresh + (policy ? 2 : 0) + at_end];
 }
@@ -476,11 +486,11 @@ static int issue_runs(PomBatch* h, const PomRun* runs, int n, bool helpers, hipE
  * whole batch in ONE launch on the caller's stream.  For steps that have to be joined with the caller's stream every tick (explicit
  * moves): forking into sub-streams and joining them again costs more than the overlap gains (65,536 envs, MI355X: 23.3 us per step
  * as one launch, 43.8 as two, 60.2 as three; profiles/r02a_explicit_streams.txt).  `threads`: with the helper threads (issue_runs) */
-static int launch_parts(PomBatch* h, const StepParams& p, int launches, bool policy, bool one_launch, bool threads)
+static int launch_parts(PomBatch* h, const StepParams& p, int launches, bool policy, bool one_launch, bool threads, bool view = false)
 {
     const int parts = one_launch ? 1 : h->parts;
     if (int rc = one_launch ? join_parts(h) : fork_parts(h)) return rc;
-    const PomStepKernel kernel = step_kernel(h, policy, p.ticks, false, p.obs_planes != nullptr);
+    const PomStepKernel kernel = step_kernel(h, policy, p.ticks, false, p.obs_planes != nullptr, view);
     PomRun runs[PomBatch::MAX_PARTS];
     int n = 0;
     for (int k = 0; k < parts; k++) {
@@ -512,7 +522,7 @@ static int launch_step(PomBatch* h, const int32_t* moves_dev, uint64_t seed, int
     StepParams p;
     if (int rc = chain_settle(h)) return rc; /* an ordinary launch after chained ones: every tile must stand on the tick the host thinks it does */
     if (int rc = fill_params(h, p, moves_dev, seed, dist, ticks, obs)) return rc;
-    return launch_parts(h, p, 1, policy, one_launch, false);
+    return launch_parts(h, p, 1, policy, one_launch, false, obs && obs->view);
 }
 
 #ifndef POM_GRAPH_TICKS
