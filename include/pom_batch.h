@@ -363,6 +363,48 @@ int pom_batch_step_device_observe_view(PomBatch* h, const int32_t* moves_dev, co
 int pom_batch_step_device_range_view(PomBatch* h, int64_t first, int64_t count, const int32_t* moves_dev, void* stream,
                                      const PomViewSpec* spec);
 
+/*
+ * FORECAST: where will the fire be, and when — flames and deaths K ticks ahead, without touching the batch.  The reference's own
+ * answer is strategy::IsInDanger (src/bboard/strategy.cpp:229-249), the smallest timer over the bombs whose cross covers a cell; its
+ * comment says "TODO: add consideration for chained bomb explosions", and it knows nothing of walls, wood or moving bombs either.
+ * Here the tick itself answers: one launch plays K ticks of bboard::Step (include/bboard.hpp:668, src/bboard/step.cpp:9-284) on a
+ * scratch copy of every env that is never stored, so chains, blocked rays, wood turning into flames, kicked bombs in flight and
+ * agents dying where they stand are all in it.  With moves_dev it answers "what happens if we do this": six calls, one per move
+ * of an agent, are that agent's action-safety mask.
+ * Semantics: for every env e < n, S_0 = a private copy of its current State and S_t = bboard::Step(S_{t-1}, m_t) for t = 1 .. K =
+ *          horizon, with m_1 = moves_dev[e] (all four entries, dead agents' included, as pom_batch_step_device reads them:
+ *          step_utility.cpp:138-170) or IDLE x 4 if moves_dev is NULL, and m_t = IDLE x 4 for t >= 2.  Bare Step as in
+ *          POM_MODE_RAW whatever the handle's mode: no timeStep++ (environment.cpp:148-150), no done / max_steps logic
+ *          (environment.cpp:125-128, 152-168), no restart; a finished env is forecast like any other.
+ * flame_tick[e][y][x] (required; uint8 [n][11][11], row-major [y][x]): the smallest t in 1 .. K with IS_FLAME(S_t.board[y][x])
+ *          (bboard.hpp:85), 0 if there is none.  A cell that burns now gets 1 only if it still burns after tick 1.
+ * agent_tick[e][a] (nullable; int32 [n][4]): -1 if agent a is dead in S_0 (AgentInfo::dead, bboard.hpp:239); otherwise the smallest
+ *          t with S_t.agents[a].dead; 0 if the agent is alive in S_K.
+ * ubflags[e] (nullable; uint32 [n]): the OR of the POM_UB_* flags (pom_state.h) the K ticks raised, with the stepper's documented
+ *          fallbacks as in a real tick.  The env's own flags (pom_batch_status) are neither included nor changed.
+ * Nothing else changes: after the call nothing this API can read differs from before — records, snapshots and terminal records,
+ *          status and the envs' own ubflags, POM_CNT_* (forecast ticks are not steps), episode counters, the handle's tick, agent
+ *          memory, chain statistics.
+ * Ordering: exactly as pom_batch_observe — chained launches are settled and the sub-streams joined first, then ONE launch on the
+ *          handle's stream; moves_dev is read and the outputs are written in stream order.  Every launch shape of the handle gives
+ *          the same outputs (the device buffers are 16-env tiles whatever the shape).
+ * POM_E_ARG (with a pom_last_error text; nothing is written): a null handle or spec, struct_size != sizeof(PomForecastSpec)
+ *          (POM_FORECAST_SPEC_SIZE), horizon outside 1 .. POM_FORECAST_MAX_TICKS, nonzero reserved_, a null flame_tick_dev,
+ *          flame_tick_dev or agent_tick_dev not 16-byte aligned, ubflags_dev or moves_dev not 4-byte aligned.
+ */
+enum { POM_FORECAST_MAX_TICKS = 32, POM_FORECAST_SPEC_SIZE = 48 };
+typedef struct PomForecastSpec {
+    int32_t struct_size;        /* = sizeof(PomForecastSpec) */
+    int32_t horizon;            /* K, 1..POM_FORECAST_MAX_TICKS */
+    int32_t reserved_[2];       /* must be 0 */
+    const int32_t* moves_dev;   /* nullable: int32 [n][4], the moves of forecast tick 1 (dead agents' entries included,
+                                   as pom_batch_step_device reads them); NULL = IDLE.  Ticks 2..K are always all-IDLE */
+    uint8_t* flame_tick_dev;    /* required: uint8 [n][11][11], row-major [y][x] */
+    int32_t* agent_tick_dev;    /* nullable: int32 [n][4] */
+    uint32_t* ubflags_dev;      /* nullable: uint32 [n] */
+} PomForecastSpec;
+int pom_batch_forecast(PomBatch* h, const PomForecastSpec* spec);
+
 /* A stand-in for a learned policy in measurements and tests of the closed loop (NOT part of the stepper): one launch on `stream`
  * that writes Move[4] of the envs [first, first + count) into moves_dev (int32 [n][4]).  codes_dev != NULL: the POM_OBS_CODES
  * observation of the batch (uint8 [n][5][11][11]) — every byte of the range's observations is read and the moves depend on them;

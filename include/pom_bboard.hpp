@@ -490,6 +490,9 @@ public:
     {
         pom_check(pom_batch_copy_envs_device(h_, srcDev, first, count, flags));
     }
+    // where will the fire be, and when: spec.horizon ticks of Step played ahead on a scratch copy of every game, the games themselves
+    // untouched; all pointers of the spec are DEVICE memory (pom_batch_forecast)
+    void Forecast(const PomForecastSpec& spec) { pom_check(pom_batch_forecast(h_, &spec)); }
     bool IsDone(int64_t e) { return Query(e, 0) != 0; }
     bool IsDraw(int64_t e) { return Query(e, 2) != 0; }
     int GetWinner(int64_t e) { return Query(e, 1); }

@@ -63,6 +63,20 @@ def _view_spec(code: int, radius: int, planes, viewer_attrs=None, env_attrs=None
     return _ViewSpec(C.sizeof(_ViewSpec), code, int(radius), 0, ptr(planes), ptr(viewer_attrs), ptr(env_attrs))
 
 
+class _ForecastSpec(C.Structure):
+    """PomForecastSpec (include/pom_batch.h): the forecast's horizon, first-tick moves and outputs"""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("horizon", C.c_int32), ("reserved_", C.c_int32 * 2),
+        ("moves_dev", C.c_void_p), ("flame_tick_dev", C.c_void_p), ("agent_tick_dev", C.c_void_p), ("ubflags_dev", C.c_void_p),
+    ]
+
+
+def _forecast_spec(horizon: int, moves, flame_tick, agent_tick=None, ubflags=None) -> _ForecastSpec:
+    ptr = lambda t: None if t is None else t.data_ptr() if hasattr(t, "data_ptr") else int(t)  # noqa: E731
+    return _ForecastSpec(C.sizeof(_ForecastSpec), int(horizon), (C.c_int32 * 2)(0, 0), ptr(moves), ptr(flame_tick), ptr(agent_tick),
+                         ptr(ubflags))
+
+
 def library_path() -> str:
     return os.environ.get("POM_LIB") or os.path.join(_HERE, "libpom_batch.so")  # POM_LIB: experimental builds only
 
@@ -102,6 +116,8 @@ def load_library() -> C.CDLL:
         lib.pom_batch_observe_view.argtypes = [P, C.POINTER(_ViewSpec)]
         lib.pom_batch_step_device_observe_view.argtypes = [P, VP, C.POINTER(_ViewSpec)]
         lib.pom_batch_step_device_range_view.argtypes = [P, I64, I64, VP, VP, C.POINTER(_ViewSpec)]
+    if not os.environ.get("POM_LIB") or hasattr(lib, "pom_batch_forecast"):
+        lib.pom_batch_forecast.argtypes = [P, C.POINTER(_ForecastSpec)]
     if hasattr(lib, "pom_batch_step_device_range"):
         lib.pom_batch_step_device_range.argtypes = [P, I64, I64, VP, VP, VP, I32, I32, VP, VP]
         lib.pom_bench_policy.argtypes = [VP, VP, I64, I64, C.c_uint32, VP]
@@ -543,6 +559,48 @@ class BatchEnvironment:
         if mine.cuda_stream != theirs.cuda_stream:
             theirs.wait_stream(mine)
         return out, a_attrs, e_attrs
+
+    # ---- forecast: flames and deaths K ticks ahead (pom_batch_forecast) ---------------------------------
+    def forecast(self, horizon: int, moves=None, out=None, agent_ticks: bool = True, ubflags: bool = False) -> dict:
+        """Where will the fire be, and when: `horizon` (1..32) ticks of bboard::Step played on a scratch copy of every env by one
+        kernel on the handle's stream; the batch itself is left exactly as it is (pom_batch_forecast, include/pom_batch.h).
+        `moves`: a device int32 tensor [n, 4], the moves of forecast tick 1 (None: IDLE); the later ticks are all-IDLE.
+        Returns a dict of torch tensors on the handle's device: `flame_tick` uint8 [n, 11, 11], per cell the first tick 1..horizon
+        that leaves it in flames (0: none); with agent_ticks `agent_tick` int32 [n, 4] (-1 dead already, t the tick the agent dies
+        in, 0 alive at the end); with ubflags `ubflags` (int32 [n] holding the header's uint32 bit mask of the POM_UB_* flags the
+        forecast ticks raised: test bits, do not compare signed values).  `out`: a dict
+        with tensors of an earlier call under the same names, written in place of new ones."""
+        import torch
+        if not 1 <= int(horizon) <= 32:
+            raise ValueError("horizon must be 1..32")
+        dev = torch.device("cuda", self.device)
+        want = {"flame_tick": ((self.n, 11, 11), torch.uint8)}
+        if agent_ticks:
+            want["agent_tick"] = ((self.n, 4), torch.int32)
+        if ubflags:
+            want["ubflags"] = ((self.n,), torch.int32)
+        res = {}
+        for name, (shape, tdt) in want.items():
+            t = None if out is None else out.get(name)
+            if t is None:
+                t = torch.empty(shape, dtype=tdt, device=dev)
+            elif tuple(t.shape) != shape or t.dtype != tdt or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"out[{name!r}] must be a contiguous {tdt} tensor of shape {shape} on {dev}")
+            res[name] = t
+        if moves is not None:
+            if tuple(getattr(moves, "shape", ())) != (self.n, 4) or "int32" not in str(getattr(moves, "dtype", "")) or not moves.is_contiguous():
+                raise ValueError(f"moves must be a contiguous int32[{self.n}, 4] device tensor")
+            if moves.device != dev:
+                raise ValueError(f"moves live on {moves.device}, the batch on {dev}")
+        # the kernel runs on the handle's stream, the tensors live on torch's current stream: order the two with events
+        mine, theirs = torch.cuda.ExternalStream(self.stream_handle(), device=dev), torch.cuda.current_stream(dev)
+        if mine.cuda_stream != theirs.cuda_stream:
+            mine.wait_stream(theirs)
+        spec = _forecast_spec(horizon, moves, res["flame_tick"], res.get("agent_tick"), res.get("ubflags"))
+        _check(self._lib, self._lib.pom_batch_forecast(self._h, C.byref(spec)))
+        if mine.cuda_stream != theirs.cuda_stream:
+            theirs.wait_stream(mine)
+        return res
 
     def moves_tensor(self):
         """The handle's device move buffer as a torch int32 tensor [n, 4] (zero-copy): what policy_simple() fills and

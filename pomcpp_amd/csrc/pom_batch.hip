@@ -1294,3 +1294,41 @@ int pom_env_step(void* state_1004, const int32_t moves[4], int32_t max_steps, in
 }
 
 } /* extern "C" */
+
+/* ---- the forecast (pom_batch.h PomForecastSpec): K ticks ahead on a scratch copy of every tile.  Its kernel comes after every
+ * other kernel of this file, so that those are emitted as they were without it ---- */
+#include "pom_forecast.h"
+
+static_assert(sizeof(PomForecastSpec) == POM_FORECAST_SPEC_SIZE, "pom_batch.h states the size");
+
+extern "C" int pom_batch_forecast(PomBatch* h, const PomForecastSpec* s)
+{
+    const char* what = nullptr;
+    if (!h) what = "the handle is NULL";
+    else if (!s) what = "the spec is NULL";
+    else if (s->struct_size != (int32_t)sizeof(PomForecastSpec)) what = "struct_size is not sizeof(PomForecastSpec)";
+    else if (s->horizon < 1 || s->horizon > POM_FORECAST_MAX_TICKS) what = "horizon must be 1..32";
+    else if (s->reserved_[0] != 0 || s->reserved_[1] != 0) what = "reserved_ must be 0";
+    else if (!s->flame_tick_dev) what = "flame_tick_dev is NULL";
+    else if (((uintptr_t)s->flame_tick_dev & 15) || ((uintptr_t)s->agent_tick_dev & 15)) what = "flame_tick_dev and agent_tick_dev must be 16-byte aligned";
+    else if (((uintptr_t)s->ubflags_dev & 3) || ((uintptr_t)s->moves_dev & 3)) what = "ubflags_dev and moves_dev must be 4-byte aligned";
+    if (what) {
+        snprintf(g_err, sizeof g_err, "pom_batch_forecast: %s", what);
+        return POM_E_ARG;
+    }
+    HIPCHK(hipSetDevice(h->device));
+    /* quiesce, not only join (as pom_batch_observe): after chained launches a tile left behind is caught up first — the forecast
+     * starts from the state a download returns */
+    if (int jr = quiesce(h)) return jr;
+    ForecastParams p;
+    p.state = h->state;
+    p.moves = s->moves_dev;
+    p.flame_tick = s->flame_tick_dev;
+    p.agent_tick = s->agent_tick_dev;
+    p.ubflags = s->ubflags_dev;
+    p.n = h->n;
+    p.horizon = s->horizon;
+    pom_forecast_kernel<<<dim3((unsigned)((h->n + 15) / 16)), dim3(64), 0, h->stream>>>(p);
+    HIPCHK(hipGetLastError());
+    return POM_OK;
+}

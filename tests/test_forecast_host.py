@@ -1,0 +1,139 @@
+"""pom_batch_forecast (include/pom_batch.h PomForecastSpec) without a GPU: the checker (tests/forecast_oracle.py, K x Oracle.step on
+a copy) equals the compiled reference's answers (tests/golden/forecast.npz, tests/golden/gen_forecast.py) on every case, the
+hand-made cases give the planes written out by hand below, and the header's spec compiles as C and C++ at the size it states."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from pomcpp_amd.state import STATE_DTYPE
+from tests import forecast_cases as FC
+from tests.forecast_oracle import forecast
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "forecast.npz")
+
+
+def plane(cells):
+    """{tick: [(x, y), ...]} -> uint8 [11, 11], row-major [y][x]"""
+    p = np.zeros((11, 11), dtype=np.uint8)
+    for t, where in cells.items():
+        for x, y in where:
+            assert p[y, x] == 0
+            p[y, x] = t
+    return p
+
+
+def cross(x, y, reach):
+    """the cells of an unobstructed cross: reach = (right, left, down, up) cells along +x, -x, +y, -y"""
+    r, l, d, u = reach
+    return ([(x, y)] + [(x + i, y) for i in range(1, r + 1)] + [(x - i, y) for i in range(1, l + 1)] +
+            [(x, y + i) for i in range(1, d + 1)] + [(x, y - i) for i in range(1, u + 1)])
+
+
+# What each hand-made case of tests/forecast_cases.py must give, reasoned from the reference's rules: a bomb planted with life L goes
+# off in tick L (TickBombs, step_utility.cpp:224-245), its cross reaches `strength` cells (State::SpawnFlame, bboard.cpp:198-263),
+# rigid stops a ray before the cell, wood burns and stops it behind (SpawnFlameItem, bboard.cpp:24-57), a bomb inside a cross goes
+# off with it, a flame goes out when its timeLeft reaches 0 at the START of a tick (TickFlames, step_utility.cpp:208-222).
+HAND = {
+    # bomb (5, 5) strength 2 goes off in tick 2 and takes the bomb on (7, 5) (life 8, strength 2) along: its cross burns in tick 2 too
+    "early_chain": (plane({2: sorted(set(cross(5, 5, (2, 2, 2, 2)) + cross(7, 5, (2, 2, 2, 2))))}), [0, 0, 0, 0]),
+    # strength 3 from (5, 5): +x stops before the rigid cell (7, 5); +y burns the wood on (5, 7) and stops; -x, -y run their three cells
+    "blocked_rays": (plane({3: cross(5, 5, (1, 3, 2, 3))}), [0, 0, 0, 0]),
+    # the bomb rolls from (2, 5) to (5, 5) in three ticks and goes off there; nothing burns where it started or passed, but for (4, 5)
+    "moving_bomb": (plane({3: cross(5, 5, (1, 1, 1, 1))}), [0, 0, 0, 0]),
+    # the flame around (3, 3) goes out in tick 1: 0, except (3, 4), lit again by the bomb on (3, 5) in that tick; the flame around (8, 8) stays
+    "expiring_flames": (plane({1: cross(3, 5, (1, 1, 1, 1)) + cross(8, 8, (1, 1, 1, 1))}), [0, 0, 0, 0]),
+    # agent 1 stands on (5, 6), in the cross of the bomb that goes off in tick 4; agent 3 was dead before
+    "agent_deaths": (plane({4: cross(5, 5, (1, 1, 1, 1))}), [0, 4, 0, -1]),
+    "finished_game": (plane({2: cross(5, 5, (1, 1, 1, 1))}), [0, -1, -1, -1]),
+    # agent 0 plants in the corner (0, 0) and stays: tick 11, strength 1, and it dies on it
+    "move_bomb": (plane({11: cross(0, 0, (1, 0, 1, 0))}), [11, 0, 0, 0]),
+    "move_bomb_horizon32": (plane({11: cross(0, 0, (1, 0, 1, 0))}), [11, 0, 0, 0]),
+    # the bomb on (3, 5), strength 2, goes off in tick 1: (5, 5) is its last cell.  Agent 0 steps down to (5, 6) and lives ...
+    "step_out": (plane({1: cross(3, 5, (2, 2, 2, 2))}), [0, 0, 0, 0]),
+    "stay_in": (plane({1: cross(3, 5, (2, 2, 2, 2))}), [1, 0, 0, 0]),   # ... idle it dies
+    # agent 0 walks from (7, 5) into the flame cell (6, 5): dead in tick 1 (step.cpp:84-98); the flame (timeLeft 3) still burns after it
+    "step_into_flames": (plane({1: cross(5, 5, (1, 1, 1, 1))}), [1, 0, 0, 0]),
+}
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return np.load(GOLDEN)
+
+
+def test_fixture_holds_the_cases_as_they_are_built(oracle, golden):
+    cases = FC.all_cases(oracle)
+    assert [c.name for c in cases] == list(golden["names"]), "the cases changed: regenerate tests/golden/forecast.npz"
+    assert os.path.getsize(GOLDEN) < 256 * 1024
+    for i, c in enumerate(cases):
+        assert c.start.tobytes() == golden["start"][i].tobytes(), c.name
+        assert bool(golden["has_moves"][i]) == (c.moves is not None) and int(golden["horizon"][i]) == c.horizon, c.name
+        assert golden["moves"][i].tolist() == (list(c.moves) if c.moves is not None else [0, 0, 0, 0]), c.name
+    assert {1, 32} <= set(golden["horizon"].tolist())
+    assert set(HAND) == {c.name for c in FC.hand_made()}
+
+
+def test_checker_equals_the_reference_on_every_entry(oracle, golden):
+    """K x Oracle.step against K x the compiled bboard::Step; and no tick of any entry raises a flag"""
+    n = len(golden["names"])
+    deaths = cells = 0
+    for i in range(n):
+        s = golden["start"][i].copy().view(STATE_DTYPE)
+        mv = golden["moves"][i:i + 1] if golden["has_moves"][i] else None
+        flame, agent, ub = forecast(oracle, s, int(golden["horizon"][i]), mv)
+        assert np.array_equal(flame[0], golden["flame_tick"][i]), golden["names"][i]
+        assert np.array_equal(agent[0], golden["agent_tick"][i]), golden["names"][i]
+        assert ub[0] == 0, golden["names"][i]
+        deaths += int((agent > 0).sum())
+        cells += int((flame > 0).sum())
+    assert deaths >= 10 and cells >= 500   # the played entries are not quiet
+
+
+def test_hand_written_planes_equal_the_fixture(golden):
+    names = list(golden["names"])
+    for name, (flame, agent) in HAND.items():
+        i = names.index(name)
+        got = golden["flame_tick"][i]
+        assert np.array_equal(got, flame), f"{name}: cells {np.argwhere(got != flame).tolist()} (y, x) differ"
+        assert golden["agent_tick"][i].tolist() == agent, name
+    # what strategy::IsInDanger (strategy.cpp:229-249) would say of (9, 5) in early_chain: 8, the long fuse; the forecast says 2
+    assert HAND["early_chain"][0][5, 9] == 2
+    # the cells behind the blocked rays, and the rigid cell itself
+    assert HAND["blocked_rays"][0][5, 7] == 0 and HAND["blocked_rays"][0][5, 8] == 0 and HAND["blocked_rays"][0][8, 5] == 0
+    assert HAND["blocked_rays"][0][7, 5] == 3
+    assert HAND["expiring_flames"][0][3, 3] == 0 and HAND["expiring_flames"][0][4, 3] == 1
+
+
+SPEC_PROGRAM = """
+#include <stddef.h>
+#include "pom_batch.h"
+typedef char size_is_stated[sizeof(PomForecastSpec) == POM_FORECAST_SPEC_SIZE ? 1 : -1];
+typedef char ticks_are_32[POM_FORECAST_MAX_TICKS == 32 ? 1 : -1];
+typedef char moves_at_16[offsetof(PomForecastSpec, moves_dev) == 16 && offsetof(PomForecastSpec, ubflags_dev) == 40 ? 1 : -1];
+int use(PomBatch* h)
+{
+    PomForecastSpec s = {sizeof(PomForecastSpec), 12, {0, 0}, 0, 0, 0, 0};
+    return pom_batch_forecast(h, &s);
+}
+"""
+
+
+@pytest.mark.parametrize("compiler,std", [("gcc", "-std=c99"), ("g++", "-std=c++17")])
+def test_header_compiles_with_the_spec(tmp_path, compiler, std):
+    src = tmp_path / ("spec.c" if compiler == "gcc" else "spec.cpp")
+    src.write_text(SPEC_PROGRAM)
+    subprocess.run([compiler, std, "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), str(src)], check=True)
+    header = open(os.path.join(ROOT, "include", "pom_batch.h")).read()
+    assert int(re.search(r"POM_FORECAST_SPEC_SIZE = (\d+)", header).group(1)) == 48
+
+
+def test_wrapper_structure_is_the_headers():
+    import ctypes as C
+    from pomcpp_amd.batch import _ForecastSpec
+    assert C.sizeof(_ForecastSpec) == 48
+    assert (_ForecastSpec.moves_dev.offset, _ForecastSpec.flame_tick_dev.offset, _ForecastSpec.agent_tick_dev.offset,
+            _ForecastSpec.ubflags_dev.offset) == (16, 24, 32, 40)
