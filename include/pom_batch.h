@@ -405,6 +405,70 @@ typedef struct PomForecastSpec {
 } PomForecastSpec;
 int pom_batch_forecast(PomBatch* h, const PomForecastSpec* spec);
 
+/*
+ * ROLLOUT: how does the game end — R random playouts of every env to a finished game or a horizon of K ticks, without touching
+ * the batch.  What Monte-Carlo leaf evaluation, a roll-out baseline for a value head and "which of my six moves survives most
+ * often" need.  The reference plays a game out with Environment::StartGame (src/bboard/environment.cpp:68-88:
+ * Step until IsDone or the step bound) over RandomAgents (src/agents/basic_agents.cpp:12-22); here ONE launch plays all R x n
+ * playouts, each on a scratch copy of its env's 16-env tile that is never stored.
+ * Semantics: for every env e < n and sample r < R = samples: S_0 = a private copy of the env's current State and status, and
+ *          seed_r = pom_splitmix64(seed + r) (pom_rng.h).  For t = 1 .. K = horizon: stop if the game is finished
+ *          (Environment::Step returns early, environment.cpp:125-128); otherwise m_t = moves_dev[e] if t == 1 and moves_dev is
+ *          not NULL (all four entries, dead agents' included: step_utility.cpp:138-170), else
+ *          m_t = pom_rng_moves(seed_r, env_offset + e, t - 1, dist); S_t = bboard::Step(S_{t-1}, m_t) (include/bboard.hpp:668,
+ *          src/bboard/step.cpp:9-284).  After each tick the bookkeeping of Environment::Step (environment.cpp:148-168) whatever
+ *          the handle's mode: timeStep++ on the private copy (:150); finished with a winner when aliveAgents == 1 (:152-163,
+ *          the last alive index), finished as a draw when aliveAgents == 0 (:164-168), finished and timed out when the handle's
+ *          max_steps > 0 and timeStep >= max_steps (StartGame's bound, environment.cpp:71).
+ *          "Finished at S_0" is the record's own done bit (pom_batch_status), which is never set on a POM_MODE_RAW handle: such
+ *          an env gets length 0 and its recorded outcome in every sample.  No restart is ever played and no fresh board drawn,
+ *          whatever auto_reset says.
+ * Equivalence: sample r without moves_dev is exactly what a POM_MODE_ENV handle with auto_reset = 0, the same max_steps and the
+ *          same env_offset leaves in its statuses after pom_batch_upload(states), pom_batch_set_tick(0),
+ *          pom_batch_step_random(seed_r, dist, K, 1); with moves_dev after pom_batch_step_device(moves), pom_batch_set_tick(1),
+ *          pom_batch_step_random(seed_r, dist, K - 1, 1).
+ * result[r][e] (required; uint32 [R][n], sample-major): POM_RO_ALIVE bit a = agent a is alive in the last state played
+ *          (!AgentInfo::dead, bboard.hpp:239); POM_RO_DONE, POM_RO_DRAW (Environment::IsDone / IsDraw, environment.cpp:195-203),
+ *          POM_RO_TIMEOUT; POM_RO_UB = some played tick raised a POM_UB_* flag (pom_state.h; the documented fallbacks apply as in
+ *          a real tick; the env's own flags are neither read into this bit nor changed); bits POM_RO_WINNER_SHIFT .. + 2 =
+ *          Environment::GetWinner() + 1 (environment.cpp:205-208), 0 for none; bits POM_RO_LENGTH_SHIFT .. 31 = ticks played.
+ *          Every other bit is 0.
+ * Nothing else changes: after the call nothing this API can read differs from before — records, snapshots and terminal records,
+ *          status and the envs' ubflags, POM_CNT_* (rollout ticks are not steps), episode counters, the handle's tick, agent
+ *          memory, chain statistics.
+ * Ordering: exactly as pom_batch_forecast — chained launches are settled and the sub-streams joined first, then ONE launch on the
+ *          handle's stream; moves_dev is read and result_dev written in stream order.  Every launch shape of the handle gives the
+ *          same words.
+ * POM_E_ARG (with a pom_last_error text; nothing is written): a null handle or spec, struct_size != sizeof(PomRolloutSpec)
+ *          (POM_ROLLOUT_SPEC_SIZE), horizon outside 1 .. POM_ROLLOUT_MAX_TICKS, samples outside 1 .. POM_ROLLOUT_MAX_SAMPLES, dist
+ *          no POM_DIST_*, nonzero reserved_, a null result_dev, result_dev not 16-byte aligned, moves_dev not 4-byte aligned; and a
+ *          batch so large that samples x tiles does not fit one grid (more than 2^31 workgroups: call with fewer samples).
+ * Not here: SimpleAgent playouts (the agents' memory would have to be copied per sample), reductions over the samples (torch does
+ *          them on the words), rollouts of a range of envs.
+ */
+enum { POM_ROLLOUT_MAX_TICKS = 1024, POM_ROLLOUT_MAX_SAMPLES = 256, POM_ROLLOUT_SPEC_SIZE = 48 };
+enum { /* the result word */
+    POM_RO_ALIVE = 0xF,        /* bit a: agent a alive in the last state played */
+    POM_RO_DONE = 0x10,
+    POM_RO_DRAW = 0x20,
+    POM_RO_TIMEOUT = 0x40,
+    POM_RO_UB = 0x80,          /* a played tick raised a POM_UB_* flag */
+    POM_RO_WINNER_SHIFT = 8,   /* 3 bits: winner + 1, 0 = nobody */
+    POM_RO_WINNER_MASK = 0x700,
+    POM_RO_LENGTH_SHIFT = 16   /* 16 bits: ticks played, 0 .. horizon */
+};
+typedef struct PomRolloutSpec {
+    int32_t struct_size;       /* = sizeof(PomRolloutSpec) */
+    int32_t horizon;           /* K, 1..POM_ROLLOUT_MAX_TICKS */
+    int32_t samples;           /* R, 1..POM_ROLLOUT_MAX_SAMPLES */
+    int32_t dist;              /* POM_DIST_HARMLESS / _RANDOM / _STRESS (pom_rng.h) */
+    uint64_t seed;
+    const int32_t* moves_dev;  /* nullable: int32 [n][4], the moves of tick 1 of EVERY sample (dead agents' entries included) */
+    uint32_t* result_dev;      /* required: uint32 [R][n], sample-major, 16-byte aligned */
+    int64_t reserved_;         /* must be 0 */
+} PomRolloutSpec;
+int pom_batch_rollout(PomBatch* h, const PomRolloutSpec* spec);
+
 /* A stand-in for a learned policy in measurements and tests of the closed loop (NOT part of the stepper): one launch on `stream`
  * that writes Move[4] of the envs [first, first + count) into moves_dev (int32 [n][4]).  codes_dev != NULL: the POM_OBS_CODES
  * observation of the batch (uint8 [n][5][11][11]) — every byte of the range's observations is read and the moves depend on them;

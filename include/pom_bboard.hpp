@@ -493,6 +493,9 @@ public:
     // where will the fire be, and when: spec.horizon ticks of Step played ahead on a scratch copy of every game, the games themselves
     // untouched; all pointers of the spec are DEVICE memory (pom_batch_forecast)
     void Forecast(const PomForecastSpec& spec) { pom_check(pom_batch_forecast(h_, &spec)); }
+    // how does the game end: spec.samples random playouts of every game to a finished game or spec.horizon ticks, the games themselves
+    // untouched; one result word (POM_RO_*) per sample and game; all pointers of the spec are DEVICE memory (pom_batch_rollout)
+    void Rollout(const PomRolloutSpec& spec) { pom_check(pom_batch_rollout(h_, &spec)); }
     bool IsDone(int64_t e) { return Query(e, 0) != 0; }
     bool IsDraw(int64_t e) { return Query(e, 2) != 0; }
     int GetWinner(int64_t e) { return Query(e, 1); }

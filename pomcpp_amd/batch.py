@@ -77,6 +77,34 @@ def _forecast_spec(horizon: int, moves, flame_tick, agent_tick=None, ubflags=Non
                          ptr(ubflags))
 
 
+class _RolloutSpec(C.Structure):
+    """PomRolloutSpec (include/pom_batch.h): the rollout's horizon, samples, move stream, first-tick moves and result"""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("horizon", C.c_int32), ("samples", C.c_int32), ("dist", C.c_int32), ("seed", C.c_uint64),
+        ("moves_dev", C.c_void_p), ("result_dev", C.c_void_p), ("reserved_", C.c_int64),
+    ]
+
+
+# the result word of a rollout (the header's POM_RO_*)
+RO_ALIVE, RO_DONE, RO_DRAW, RO_TIMEOUT, RO_UB, RO_WINNER_SHIFT, RO_WINNER_MASK, RO_LENGTH_SHIFT = 0xF, 0x10, 0x20, 0x40, 0x80, 8, 0x700, 16
+
+
+def decode_rollout(result) -> dict:
+    """The fields of rollout()'s result words (torch tensor or numpy array of any shape [...], int32 or uint32): `alive` bool
+    [..., 4], `done`, `draw`, `timeout`, `ub` bool [...], `winner` (-1: nobody) and `length` (ticks played) int32 [...]; the same kind of
+    array as the input, on its device.  Reductions are the caller's: decode_rollout(r)["alive"].float().mean(0) is the survival rate."""
+    w = result
+    if isinstance(w, np.ndarray):
+        w = w.astype(np.int64) & 0xFFFFFFFF
+        bits, i32 = w[..., None] >> np.arange(4) & 1, lambda a: a.astype(np.int32)  # noqa: E731
+    else:
+        import torch
+        w = w.to(torch.int64) & 0xFFFFFFFF
+        bits, i32 = w[..., None] >> torch.arange(4, device=w.device) & 1, lambda a: a.to(torch.int32)  # noqa: E731
+    return {"alive": bits != 0, "done": (w & RO_DONE) != 0, "draw": (w & RO_DRAW) != 0, "timeout": (w & RO_TIMEOUT) != 0,
+            "ub": (w & RO_UB) != 0, "winner": i32(((w & RO_WINNER_MASK) >> RO_WINNER_SHIFT) - 1), "length": i32(w >> RO_LENGTH_SHIFT)}
+
+
 def library_path() -> str:
     return os.environ.get("POM_LIB") or os.path.join(_HERE, "libpom_batch.so")  # POM_LIB: experimental builds only
 
@@ -118,6 +146,8 @@ def load_library() -> C.CDLL:
         lib.pom_batch_step_device_range_view.argtypes = [P, I64, I64, VP, VP, C.POINTER(_ViewSpec)]
     if not os.environ.get("POM_LIB") or hasattr(lib, "pom_batch_forecast"):
         lib.pom_batch_forecast.argtypes = [P, C.POINTER(_ForecastSpec)]
+    if not os.environ.get("POM_LIB") or hasattr(lib, "pom_batch_rollout"):
+        lib.pom_batch_rollout.argtypes = [P, C.POINTER(_RolloutSpec)]
     if hasattr(lib, "pom_batch_step_device_range"):
         lib.pom_batch_step_device_range.argtypes = [P, I64, I64, VP, VP, VP, I32, I32, VP, VP]
         lib.pom_bench_policy.argtypes = [VP, VP, I64, I64, C.c_uint32, VP]
@@ -601,6 +631,43 @@ class BatchEnvironment:
         if mine.cuda_stream != theirs.cuda_stream:
             theirs.wait_stream(mine)
         return res
+
+    # ---- rollout: R random playouts of every env (pom_batch_rollout) ---------------------------------------
+    def rollout(self, horizon: int, samples: int, seed: int, dist: int = DIST_RANDOM, moves=None, out=None):
+        """How does the game end: `samples` (1..256) random playouts of every env under the move stream `dist`, each to a finished game
+        or `horizon` (1..1024) ticks, by one kernel on the handle's stream; the batch itself is left exactly as it is
+        (pom_batch_rollout, include/pom_batch.h).  Sample r is seeded pom_splitmix64(seed + r).  `moves`: a device int32 tensor
+        [n, 4], the moves of tick 1 of every sample (None: drawn like the others).  Returns the result words, an int32 tensor
+        [samples, n] on the handle's device holding the header's uint32 words (decode_rollout names the fields: test bits, do not
+        compare signed values).  `out`: such a tensor of an earlier call, written in place of a new one."""
+        import torch
+        if not 1 <= int(horizon) <= 1024:
+            raise ValueError("horizon must be 1..1024")
+        if not 1 <= int(samples) <= 256:
+            raise ValueError("samples must be 1..256")
+        if dist not in (DIST_HARMLESS, DIST_RANDOM, DIST_STRESS):
+            raise ValueError("dist must be DIST_HARMLESS, DIST_RANDOM or DIST_STRESS")
+        dev = torch.device("cuda", self.device)
+        shape = (int(samples), self.n)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int32, device=dev)
+        elif tuple(out.shape) != shape or out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"out must be a contiguous int32 tensor of shape {shape} on {dev}")
+        if moves is not None:
+            if tuple(getattr(moves, "shape", ())) != (self.n, 4) or "int32" not in str(getattr(moves, "dtype", "")) or not moves.is_contiguous():
+                raise ValueError(f"moves must be a contiguous int32[{self.n}, 4] device tensor")
+            if moves.device != dev:
+                raise ValueError(f"moves live on {moves.device}, the batch on {dev}")
+        # the kernel runs on the handle's stream, the tensors live on torch's current stream: order the two with events
+        mine, theirs = torch.cuda.ExternalStream(self.stream_handle(), device=dev), torch.cuda.current_stream(dev)
+        if mine.cuda_stream != theirs.cuda_stream:
+            mine.wait_stream(theirs)
+        spec = _RolloutSpec(C.sizeof(_RolloutSpec), int(horizon), int(samples), int(dist), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                            None if moves is None else moves.data_ptr(), out.data_ptr(), 0)
+        _check(self._lib, self._lib.pom_batch_rollout(self._h, C.byref(spec)))
+        if mine.cuda_stream != theirs.cuda_stream:
+            theirs.wait_stream(mine)
+        return out
 
     def moves_tensor(self):
         """The handle's device move buffer as a torch int32 tensor [n, 4] (zero-copy): what policy_simple() fills and

@@ -1332,3 +1332,50 @@ extern "C" int pom_batch_forecast(PomBatch* h, const PomForecastSpec* s)
     HIPCHK(hipGetLastError());
     return POM_OK;
 }
+
+/* ---- the rollout (pom_batch.h PomRolloutSpec): R random playouts of every env on scratch copies of its tile.  Its kernel comes
+ * after the forecast's, so that every kernel before it is emitted as it was without it ---- */
+#include "pom_rollout.h"
+
+static_assert(sizeof(PomRolloutSpec) == POM_ROLLOUT_SPEC_SIZE, "pom_batch.h states the size");
+
+extern "C" int pom_batch_rollout(PomBatch* h, const PomRolloutSpec* s)
+{
+    const char* what = nullptr;
+    const int64_t tiles = h ? (h->n + 15) / 16 : 0, tiles8 = (tiles + 7) / 8 * 8;
+    if (!h) what = "the handle is NULL";
+    else if (!s) what = "the spec is NULL";
+    else if (s->struct_size != (int32_t)sizeof(PomRolloutSpec)) what = "struct_size is not sizeof(PomRolloutSpec)";
+    else if (s->horizon < 1 || s->horizon > POM_ROLLOUT_MAX_TICKS) what = "horizon must be 1..1024";
+    else if (s->samples < 1 || s->samples > POM_ROLLOUT_MAX_SAMPLES) what = "samples must be 1..256";
+    else if (s->dist < POM_DIST_HARMLESS || s->dist > POM_DIST_STRESS) what = "dist must be POM_DIST_HARMLESS, _RANDOM or _STRESS";
+    else if (s->reserved_ != 0) what = "reserved_ must be 0";
+    else if (!s->result_dev) what = "result_dev is NULL";
+    else if ((uintptr_t)s->result_dev & 15) what = "result_dev must be 16-byte aligned";
+    else if ((uintptr_t)s->moves_dev & 3) what = "moves_dev must be 4-byte aligned";
+    else if (tiles8 * s->samples > (int64_t)INT_MAX) what = "samples x tiles of 16 envs exceed one grid: call with fewer samples";
+    if (what) {
+        snprintf(g_err, sizeof g_err, "pom_batch_rollout: %s", what);
+        return POM_E_ARG;
+    }
+    HIPCHK(hipSetDevice(h->device));
+    /* quiesce, not only join (as pom_batch_forecast): after chained launches a tile left behind is caught up first — the rollout
+     * starts from the state a download returns */
+    if (int jr = quiesce(h)) return jr;
+    if (tiles == 0) return POM_OK;
+    RolloutParams p;
+    p.state = h->state;
+    p.moves = s->moves_dev;
+    p.result = s->result_dev;
+    p.n = h->n;
+    p.env_offset = h->env_offset;
+    p.seed = s->seed;
+    p.horizon = s->horizon;
+    p.dist = s->dist;
+    p.max_steps = h->max_steps;
+    p.tiles = (uint32_t)tiles;
+    p.tiles8 = (uint32_t)tiles8;
+    pom_rollout_kernel<<<dim3((unsigned)(tiles8 * s->samples)), dim3(64), 0, h->stream>>>(p);
+    HIPCHK(hipGetLastError());
+    return POM_OK;
+}
