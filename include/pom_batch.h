@@ -443,8 +443,8 @@ int pom_batch_forecast(PomBatch* h, const PomForecastSpec* spec);
  *          (POM_ROLLOUT_SPEC_SIZE), horizon outside 1 .. POM_ROLLOUT_MAX_TICKS, samples outside 1 .. POM_ROLLOUT_MAX_SAMPLES, dist
  *          no POM_DIST_*, nonzero reserved_, a null result_dev, result_dev not 16-byte aligned, moves_dev not 4-byte aligned; and a
  *          batch so large that samples x tiles does not fit one grid (more than 2^31 workgroups: call with fewer samples).
- * Not here: SimpleAgent playouts (the agents' memory would have to be copied per sample), reductions over the samples (torch does
- *          them on the words), rollouts of a range of envs.
+ * Not here: SimpleAgent playouts (pom_batch_rollout_policy below), reductions over the samples (torch does them on the words),
+ *          rollouts of a range of envs.
  */
 enum { POM_ROLLOUT_MAX_TICKS = 1024, POM_ROLLOUT_MAX_SAMPLES = 256, POM_ROLLOUT_SPEC_SIZE = 48 };
 enum { /* the result word */
@@ -468,6 +468,63 @@ typedef struct PomRolloutSpec {
     int64_t reserved_;         /* must be 0 */
 } PomRolloutSpec;
 int pom_batch_rollout(PomBatch* h, const PomRolloutSpec* spec);
+
+/*
+ * ROLLOUT WITH A POLICY: the rollout above with agents::SimpleAgent (include/agents.hpp:55-76, src/agents/simple_agent.cpp) for the
+ * agents of simple_mask, the pom_rng.h stream for the others, and a first tick that may be fixed agent by agent: "my move fixed, the
+ * others play a sensible policy" — what a search's leaf evaluation and a roll-out baseline need; random agents
+ * blow themselves up within a few dozen ticks and say little about the game the caller is in.  ONE launch plays all R x n playouts;
+ * the agents' memory (two dwords per agent) is copied per sample into registers and never stored.
+ * Semantics: for every env e < n and sample r < R = samples: seed_r = pom_splitmix64(seed + r); S_0 = a private copy of the env's
+ *          current State and status; M_0 = a private copy of the env's four SimpleAgent memories as pom_batch_policy_memory reports
+ *          them — all-zero (`new SimpleAgent()` with empty queues) if the handle never ran the policy or POM_ROLLOUT_FRESH_AGENTS is
+ *          set.  For t = 1 .. K = horizon: stop if the game is finished (environment.cpp:125-128); otherwise
+ *          1. every live agent a of simple_mask is asked for a move exactly as pom_batch_policy_simple(seed_r) asks it at handle tick
+ *             t - 1: SimpleAgent::act on S_{t-1} (environment.cpp:139-146), its one draw = (agent a's 16 bits of
+ *             pom_rng_draw(seed_r, env_offset + e, t - 1)) * 5 >> 16, its memory in M updated; a dead agent of the mask gives IDLE
+ *             (environment.cpp:139-146);
+ *          2. every agent not in simple_mask gets entry a of pom_rng_moves(seed_r, env_offset + e, t - 1, dist), dead agents too, as
+ *             in pom_batch_rollout;
+ *          3. at t == 1 every agent of first_mask gets moves_dev[e][a] instead (dead agents' entries are read as
+ *             pom_batch_step_device reads them: step_utility.cpp:138-170).  A SimpleAgent overridden this way has still been asked
+ *             and its memory has moved on: the "overwrite entries of the move buffer between pom_batch_policy_simple and
+ *             pom_batch_step_policy" pattern of pom_batch_moves_device;
+ *          4. S_t = bboard::Step(S_{t-1}, m_t) (include/bboard.hpp:668, src/bboard/step.cpp:9-284), then the bookkeeping of
+ *             Environment::Step (environment.cpp:148-168: timeStep++, winner / draw; the handle's max_steps as StartGame's bound,
+ *             environment.cpp:71) exactly as pom_batch_rollout does it, whatever the handle's mode.
+ *          An env finished at S_0 (the record's own done bit) gets length 0 and its recorded outcome in every sample.
+ * result[r][e]: pom_batch_rollout's word, bit for bit (POM_RO_*).
+ * Equivalences: simple_mask == 0 with first_mask == 0 (no moves_dev needed), or with first_mask == 0xF and moves_dev, gives exactly
+ *          pom_batch_rollout's words without / with moves_dev.  simple_mask == 0xF, first_mask == 0, POM_ROLLOUT_FRESH_AGENTS: sample r
+ *          is what a POM_MODE_ENV handle with auto_reset = 0, the same max_steps and the same env_offset leaves in its statuses after
+ *          pom_batch_upload(states), pom_batch_set_tick(0), pom_batch_step_simple(seed_r, K).  Without POM_ROLLOUT_FRESH_AGENTS sample r
+ *          is what the handle itself would reach by pom_batch_set_tick(0), pom_batch_step_simple(seed_r, K) from where it stands
+ *          (no restart is played: an env that finishes stays finished).
+ * Nothing else changes: as pom_batch_rollout — records, snapshots and terminal records, status and ubflags, POM_CNT_*, episode
+ *          counters, the handle's tick, agent memory, chain statistics are as before the call.
+ * Ordering: exactly as pom_batch_rollout — chained launches are settled and the sub-streams joined first, then ONE launch on the
+ *          handle's stream; moves_dev and the agents' memory are read and result_dev is written in stream order.
+ * POM_E_ARG (with a pom_last_error text naming pom_batch_rollout_policy; nothing is written): everything pom_batch_rollout refuses
+ *          (struct_size != sizeof(PomRolloutPolicySpec) = POM_ROLLOUT_POLICY_SPEC_SIZE), simple_mask or first_mask outside 0 .. 15,
+ *          first_mask != 0 with a null moves_dev, flags other than 0 or POM_ROLLOUT_FRESH_AGENTS, nonzero reserved_.  A non-null
+ *          moves_dev with first_mask == 0 is accepted and not read.
+ */
+enum { POM_ROLLOUT_FRESH_AGENTS = 1 };            /* flags */
+enum { POM_ROLLOUT_POLICY_SPEC_SIZE = 56 };
+typedef struct PomRolloutPolicySpec {
+    int32_t struct_size;       /* = sizeof(PomRolloutPolicySpec) */
+    int32_t horizon;           /* K, 1..POM_ROLLOUT_MAX_TICKS */
+    int32_t samples;           /* R, 1..POM_ROLLOUT_MAX_SAMPLES */
+    int32_t dist;              /* POM_DIST_*: the stream of the agents NOT in simple_mask */
+    uint64_t seed;
+    const int32_t* moves_dev;  /* nullable: int32 [n][4], tick-1 moves of the agents in first_mask */
+    uint32_t* result_dev;      /* required: uint32 [R][n], sample-major, 16-byte aligned */
+    int32_t simple_mask;       /* bit a: agent a plays SimpleAgent; else the pom_rng.h stream under dist */
+    int32_t first_mask;        /* bit a: agent a's move of tick 1 is moves_dev[e][a] */
+    int32_t flags;             /* 0 or POM_ROLLOUT_FRESH_AGENTS */
+    int32_t reserved_;         /* must be 0 */
+} PomRolloutPolicySpec;
+int pom_batch_rollout_policy(PomBatch* h, const PomRolloutPolicySpec* spec);
 
 /* A stand-in for a learned policy in measurements and tests of the closed loop (NOT part of the stepper): one launch on `stream`
  * that writes Move[4] of the envs [first, first + count) into moves_dev (int32 [n][4]).  codes_dev != NULL: the POM_OBS_CODES

@@ -85,6 +85,34 @@ class _RolloutSpec(C.Structure):
     ]
 
 
+class _RolloutPolicySpec(C.Structure):
+    """PomRolloutPolicySpec (include/pom_batch.h): the rollout's spec plus who plays SimpleAgent, whose first move is fixed, and flags"""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("horizon", C.c_int32), ("samples", C.c_int32), ("dist", C.c_int32), ("seed", C.c_uint64),
+        ("moves_dev", C.c_void_p), ("result_dev", C.c_void_p), ("simple_mask", C.c_int32), ("first_mask", C.c_int32),
+        ("flags", C.c_int32), ("reserved_", C.c_int32),
+    ]
+
+
+ROLLOUT_FRESH_AGENTS = 1  # POM_ROLLOUT_FRESH_AGENTS
+
+
+def _agent_mask(v, name: str) -> int:
+    """a mask int 0..15, or an iterable of agent ids 0..3"""
+    if isinstance(v, (int, np.integer)) and not isinstance(v, bool):
+        m = int(v)
+        if not 0 <= m <= 15:
+            raise ValueError(f"{name} must be a mask 0..15 or an iterable of agent ids 0..3")
+        return m
+    try:
+        ids = [int(a) for a in v]
+    except TypeError:
+        raise ValueError(f"{name} must be a mask 0..15 or an iterable of agent ids 0..3") from None
+    if any(not 0 <= a <= 3 for a in ids):
+        raise ValueError(f"{name} must be a mask 0..15 or an iterable of agent ids 0..3")
+    return sum(1 << a for a in set(ids))
+
+
 # the result word of a rollout (the header's POM_RO_*)
 RO_ALIVE, RO_DONE, RO_DRAW, RO_TIMEOUT, RO_UB, RO_WINNER_SHIFT, RO_WINNER_MASK, RO_LENGTH_SHIFT = 0xF, 0x10, 0x20, 0x40, 0x80, 8, 0x700, 16
 
@@ -148,6 +176,8 @@ def load_library() -> C.CDLL:
         lib.pom_batch_forecast.argtypes = [P, C.POINTER(_ForecastSpec)]
     if not os.environ.get("POM_LIB") or hasattr(lib, "pom_batch_rollout"):
         lib.pom_batch_rollout.argtypes = [P, C.POINTER(_RolloutSpec)]
+    if not os.environ.get("POM_LIB") or hasattr(lib, "pom_batch_rollout_policy"):
+        lib.pom_batch_rollout_policy.argtypes = [P, C.POINTER(_RolloutPolicySpec)]
     if hasattr(lib, "pom_batch_step_device_range"):
         lib.pom_batch_step_device_range.argtypes = [P, I64, I64, VP, VP, VP, I32, I32, VP, VP]
         lib.pom_bench_policy.argtypes = [VP, VP, I64, I64, C.c_uint32, VP]
@@ -633,13 +663,19 @@ class BatchEnvironment:
         return res
 
     # ---- rollout: R random playouts of every env (pom_batch_rollout) ---------------------------------------
-    def rollout(self, horizon: int, samples: int, seed: int, dist: int = DIST_RANDOM, moves=None, out=None):
+    def rollout(self, horizon: int, samples: int, seed: int, dist: int = DIST_RANDOM, moves=None, out=None, *, simple=None, first=None,
+                fresh_agents: bool = False):
         """How does the game end: `samples` (1..256) random playouts of every env under the move stream `dist`, each to a finished game
         or `horizon` (1..1024) ticks, by one kernel on the handle's stream; the batch itself is left exactly as it is
         (pom_batch_rollout, include/pom_batch.h).  Sample r is seeded pom_splitmix64(seed + r).  `moves`: a device int32 tensor
         [n, 4], the moves of tick 1 of every sample (None: drawn like the others).  Returns the result words, an int32 tensor
         [samples, n] on the handle's device holding the header's uint32 words (decode_rollout names the fields: test bits, do not
-        compare signed values).  `out`: such a tensor of an earlier call, written in place of a new one."""
+        compare signed values).  `out`: such a tensor of an earlier call, written in place of a new one.
+
+        With `simple`, `first` or `fresh_agents` given the playouts are pom_batch_rollout_policy's: `simple` (a mask int 0..15 or an
+        iterable of agent ids) names the agents that play SimpleAgent, starting from a copy per sample of the memory policy_memory()
+        reports (`fresh_agents`: from new agents); the others draw from `dist`.  `first` (likewise) names the agents whose move of
+        tick 1 is `moves[e][a]`; with `moves` given and `first` not, all four are."""
         import torch
         if not 1 <= int(horizon) <= 1024:
             raise ValueError("horizon must be 1..1024")
@@ -647,6 +683,13 @@ class BatchEnvironment:
             raise ValueError("samples must be 1..256")
         if dist not in (DIST_HARMLESS, DIST_RANDOM, DIST_STRESS):
             raise ValueError("dist must be DIST_HARMLESS, DIST_RANDOM or DIST_STRESS")
+        with_policy = simple is not None or first is not None or bool(fresh_agents)
+        simple_mask = first_mask = 0
+        if with_policy:
+            simple_mask = 0 if simple is None else _agent_mask(simple, "simple")
+            first_mask = (0 if moves is None else 0xF) if first is None else _agent_mask(first, "first")
+            if first_mask and moves is None:
+                raise ValueError("first names agents but moves is None")
         dev = torch.device("cuda", self.device)
         shape = (int(samples), self.n)
         if out is None:
@@ -662,9 +705,15 @@ class BatchEnvironment:
         mine, theirs = torch.cuda.ExternalStream(self.stream_handle(), device=dev), torch.cuda.current_stream(dev)
         if mine.cuda_stream != theirs.cuda_stream:
             mine.wait_stream(theirs)
-        spec = _RolloutSpec(C.sizeof(_RolloutSpec), int(horizon), int(samples), int(dist), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                            None if moves is None else moves.data_ptr(), out.data_ptr(), 0)
-        _check(self._lib, self._lib.pom_batch_rollout(self._h, C.byref(spec)))
+        if with_policy:
+            spec = _RolloutPolicySpec(C.sizeof(_RolloutPolicySpec), int(horizon), int(samples), int(dist), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                      None if moves is None else moves.data_ptr(), out.data_ptr(), simple_mask, first_mask,
+                                      ROLLOUT_FRESH_AGENTS if fresh_agents else 0, 0)
+            _check(self._lib, self._lib.pom_batch_rollout_policy(self._h, C.byref(spec)))
+        else:
+            spec = _RolloutSpec(C.sizeof(_RolloutSpec), int(horizon), int(samples), int(dist), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                None if moves is None else moves.data_ptr(), out.data_ptr(), 0)
+            _check(self._lib, self._lib.pom_batch_rollout(self._h, C.byref(spec)))
         if mine.cuda_stream != theirs.cuda_stream:
             theirs.wait_stream(mine)
         return out

@@ -1379,3 +1379,59 @@ extern "C" int pom_batch_rollout(PomBatch* h, const PomRolloutSpec* s)
     HIPCHK(hipGetLastError());
     return POM_OK;
 }
+
+/* ---- the policy rollout (pom_batch.h PomRolloutPolicySpec): the rollout with SimpleAgent for the agents of simple_mask and a
+ * per-agent first tick.  Its kernel comes after the rollout's, so that every kernel before it is emitted as it was without it ---- */
+#include "pom_rollout_policy.h"
+
+static_assert(sizeof(PomRolloutPolicySpec) == POM_ROLLOUT_POLICY_SPEC_SIZE, "pom_batch.h states the size");
+
+extern "C" int pom_batch_rollout_policy(PomBatch* h, const PomRolloutPolicySpec* s)
+{
+    const char* what = nullptr;
+    const int64_t tiles = h ? (h->n + 15) / 16 : 0, tiles8 = (tiles + 7) / 8 * 8;
+    if (!h) what = "the handle is NULL";
+    else if (!s) what = "the spec is NULL";
+    else if (s->struct_size != (int32_t)sizeof(PomRolloutPolicySpec)) what = "struct_size is not sizeof(PomRolloutPolicySpec)";
+    else if (s->horizon < 1 || s->horizon > POM_ROLLOUT_MAX_TICKS) what = "horizon must be 1..1024";
+    else if (s->samples < 1 || s->samples > POM_ROLLOUT_MAX_SAMPLES) what = "samples must be 1..256";
+    else if (s->dist < POM_DIST_HARMLESS || s->dist > POM_DIST_STRESS) what = "dist must be POM_DIST_HARMLESS, _RANDOM or _STRESS";
+    else if (s->simple_mask < 0 || s->simple_mask > 15) what = "simple_mask must be 0..15";
+    else if (s->first_mask < 0 || s->first_mask > 15) what = "first_mask must be 0..15";
+    else if (s->flags & ~(int32_t)POM_ROLLOUT_FRESH_AGENTS) what = "flags must be 0 or POM_ROLLOUT_FRESH_AGENTS";
+    else if (s->reserved_ != 0) what = "reserved_ must be 0";
+    else if (s->first_mask != 0 && !s->moves_dev) what = "first_mask names agents but moves_dev is NULL";
+    else if (!s->result_dev) what = "result_dev is NULL";
+    else if ((uintptr_t)s->result_dev & 15) what = "result_dev must be 16-byte aligned";
+    else if ((uintptr_t)s->moves_dev & 3) what = "moves_dev must be 4-byte aligned";
+    else if (tiles8 * s->samples > (int64_t)INT_MAX) what = "samples x tiles of 16 envs exceed one grid: call with fewer samples";
+    if (what) {
+        snprintf(g_err, sizeof g_err, "pom_batch_rollout_policy: %s", what);
+        return POM_E_ARG;
+    }
+    HIPCHK(hipSetDevice(h->device));
+    /* quiesce, not only join (as pom_batch_rollout): the playouts start from the state a download returns */
+    if (int jr = quiesce(h)) return jr;
+    if (tiles == 0) return POM_OK;
+    RolloutPolicyParams p;
+    p.state = h->state;
+    p.moves = s->first_mask ? s->moves_dev : nullptr; /* not read when no agent's first move is fixed */
+    p.agent_mem = (s->flags & POM_ROLLOUT_FRESH_AGENTS) ? nullptr : h->agent_mem; /* a handle that never ran the policy has none: fresh agents */
+    p.result = s->result_dev;
+    p.n = h->n;
+    p.n_pad = h->n_pad;
+    p.env_offset = h->env_offset;
+    p.seed = s->seed;
+    p.horizon = s->horizon;
+    p.dist = s->dist;
+    p.max_steps = h->max_steps;
+    p.simple_mask = s->simple_mask;
+    p.first_mask = s->first_mask;
+    p.tiles = (uint32_t)tiles;
+    p.tiles8 = (uint32_t)tiles8;
+    const dim3 grid((unsigned)(tiles8 * s->samples));
+    if (s->simple_mask) pom_rollout_policy_kernel<true><<<grid, dim3(64), 0, h->stream>>>(p);
+    else pom_rollout_policy_kernel<false><<<grid, dim3(64), 0, h->stream>>>(p);
+    HIPCHK(hipGetLastError());
+    return POM_OK;
+}

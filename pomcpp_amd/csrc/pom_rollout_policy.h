@@ -1,0 +1,174 @@
+/*
+ * pom_rollout_policy.h — pom_batch_rollout_policy's kernel (include/pom_batch.h PomRolloutPolicySpec): R playouts of every env in
+ * which the agents of simple_mask play agents::SimpleAgent, the others the pom_rng.h move stream, and tick 1 may be fixed per agent;
+ * the batch untouched.
+ *
+ * It joins pom_rollout_kernel (pom_rollout.h: the K-tick loop on a tile that never leaves LDS, the ballot exit, Environment::Step's
+ * bookkeeping, the result word) with the policy of pom_step_kernel<POLICY> (pom_kernels.h: pom_policy_prepare_*, pom_policy_wave, the
+ * danger map and the cell sets laid over the tick's scratch rows).  One wavefront per (tile of 16 envs, sample); lane m of an env's
+ * quad is agent m.  The agents' memory is two dwords per lane, loaded once and never stored to global memory: every sample plays on
+ * with its own copy.
+ *
+ * The wavefront's floods run cooperatively (pom_coop_forward / pom_coop_backward deal the jobs to all 16 quads), so EVERY lane enters
+ * pom_policy_wave on every tick the wavefront plays — with actor = false for finished envs, lanes past the batch's end, dead agents
+ * and agents outside simple_mask.  Only the wave-uniform ballot exit skips it.
+ *
+ * POLICY = false (simple_mask == 0): an instantiation without any of the policy — pom_rollout_kernel with a per-agent first tick.
+ *
+ * Included after pom_rollout.h, so that every kernel before it is emitted as it was.
+ *
+ * LDS: max(LDS_ROWS, POM_REC_DWORDS + 44) rows: the danger map (32 rows of bytes) and the cell sets (12 rows) lie where the tick keeps
+ * its bomb destinations and explosion frames — the policy of a tick is over before its tick begins.  Behind them 12 rows, three
+ * dwords per lane: the agent's memory and its move of tick 1 wait there through the tick (in registers they cost 12 spilled VGPRs
+ * at 4 wavefronts per SIMD).  8,704 B per wavefront: the 16 wavefronts of a CU fit.  128 VGPRs, no scratch.
+ *
+ * Grid: as pom_rollout_kernel — workgroup b = r * tiles8 + slot, all samples of a tile on one XCD; slots >= tiles exit.
+ */
+#ifndef POM_ROLLOUT_POLICY_H_
+#define POM_ROLLOUT_POLICY_H_
+
+#include "pom_rollout.h"
+
+struct RolloutPolicyParams {
+    const uint32_t* state;
+    const int32_t* moves;      /* device int32[n][4]: tick 1 of the agents in first_mask; nullptr when first_mask == 0 */
+    const uint32_t* agent_mem; /* [2][4 * n_pad], or nullptr: fresh agents (no memory allocated, or POM_ROLLOUT_FRESH_AGENTS) */
+    uint32_t* result;          /* uint32 [samples][n] */
+    int64_t n, n_pad, env_offset;
+    uint64_t seed;
+    int32_t horizon;           /* 1 .. POM_ROLLOUT_MAX_TICKS */
+    int32_t dist, max_steps;
+    int32_t simple_mask, first_mask;
+    uint32_t tiles, tiles8;    /* tiles of 16 envs; the same rounded up to a multiple of 8: the grid is samples * tiles8 */
+};
+
+enum { RP_ROWS = POM_REC_DWORDS + 44 > LDS_ROWS ? POM_REC_DWORDS + 44 : LDS_ROWS, RP_PARK_ROWS = 3 * 4 };
+
+template <bool POLICY>
+__global__ __launch_bounds__(64, 4) void pom_rollout_policy_kernel(RolloutPolicyParams p)
+{
+    /* POLICY: behind the tile three dwords per lane that are parked through the tick: the agent's memory and its move of tick 1 */
+    __shared__ __attribute__((aligned(16))) uint32_t tile[(POLICY ? RP_ROWS + RP_PARK_ROWS : LDS_ROWS) * 16];
+    const int lane = threadIdx.x;
+    const uint32_t sample = blockIdx.x / p.tiles8, slot = blockIdx.x - sample * p.tiles8;
+    if (slot >= p.tiles) return; /* a workgroup of the padding */
+    const int64_t tile_id = pom_xcd_tile_order(slot, p.tiles);
+    load_tile16_x4(p.state + tile_id * POM_TILE_DWORDS, POM_TILE_ENVS, tile, lane);
+    /* lane -> (env lane / 4, agent lane % 4) */
+    const int ec = lane >> 2, member = lane & 3;
+    const int64_t e = tile_id * 16 + ec;
+    const bool valid = e < p.n;
+    const uint32_t key0 = (uint32_t)(p.env_offset + tile_id * 16); /* + ec: the env's number in the whole job, what its draws are keyed by */
+    const uint64_t seed_r = pom_splitmix64(p.seed + sample); /* uniform: scalar code */
+    /* neither tick 1's moves nor the agents' memory depend on the record: fetch them while it is on its way */
+    int first = POM_MOVE_IDLE;
+    if (((p.first_mask >> member) & 1) && valid) first = p.moves[e * 4 + member]; /* (dead agents' entries included) */
+    if (POLICY) {
+        /* this lane's agent's memory: this sample's own copy, never stored to global memory (the buffers hold n_pad columns) */
+        uint32_t m0 = 0, m1 = 0;
+        if (p.agent_mem) {
+            m0 = p.agent_mem[tile_id * 64 + lane];
+            m1 = p.agent_mem[4 * p.n_pad + tile_id * 64 + lane];
+        }
+        uint32_t* park = tile + RP_ROWS * 16 + lane; /* (rows no DMA touches) */
+        park[0] = m0;
+        park[64] = m1;
+        park[128] = (uint32_t)first;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); /* the DMA rows have landed (one wavefront per workgroup: no barrier) */
+    PomLane L;
+    /* the playout's state beside the tile and L, one register: the status byte, bit 8 = a played tick raised a flag, bits 16.. = ticks played */
+    uint32_t run = 0;
+    {
+        int time_step = 0; /* lives in the tile: the owner lane counts it there */
+        lane_from_tile(L, time_step, run, tile + ec, 16);
+        run &= 0xFFu & ~(uint32_t)POM_ST_RESTARTED;
+        if (!valid) run |= POM_ST_DONE; /* the lanes of an env past the batch's end count as done from the start; they write nothing */
+    }
+#if defined(POM_DIAG)
+    for (int k = 0; k < POM_PH_N; k++) L.t_acc[k] = 0;
+    L.t_last = 0;
+#endif
+#if defined(POM_TRUNC)
+    L.trunc = 990; /* no cut: the diagnostic truncation is the step kernels' business */
+#endif
+
+    const int K = p.horizon;
+    POM_NOUNROLL
+    for (int tk = 1; tk <= K; tk++) {
+        if (__ballot(!(run & POM_ST_DONE)) == 0) break; /* wave-uniform: the one exit that may skip the policy */
+        /* a lane id and a view of the tile that the compiler cannot see through, made anew for the policy and for the tick: what is
+         * derived from them is worked out where it is used, not before the loop and carried through every tick (the fresh-view trick of
+         * pom_step_kernel<POLICY>) */
+        int ln = lane;
+        uint32_t* tp = tile;
+        if (POLICY) asm volatile("" : "+v"(ln), "+v"(tp));
+        const int ec_p = ln >> 2, member_p = ln & 3;
+        const bool done = (run & POM_ST_DONE) != 0;
+        const bool simple = POLICY && ((p.simple_mask >> member_p) & 1);        /* this lane's agent plays SimpleAgent */
+        const bool fixed = tk == 1 && ((p.first_mask >> member_p) & 1);         /* ... and this tick's move is the caller's */
+        /* agent m's 16 bits of the tick's draw: SimpleAgent's one random choice, or the stream's move */
+        const uint32_t r = pom_rng_draw_half(seed_r, key0 + (uint32_t)ec_p, (uint32_t)(tk - 1), member_p >> 1);
+        const uint32_t r16 = (r >> (16 * (member_p & 1))) & 0xFFFFu;
+        int mine = first;
+        if (POLICY) {
+            uint8_t* const danger = reinterpret_cast<uint8_t*>(tp + POM_REC_DWORDS * 16);
+            uint32_t* const sets = tp + (POM_REC_DWORDS + 32) * 16;
+            LdsEnv<16, 4> accp(tp, ec_p, member_p);
+            uint32_t* const park = tp + RP_ROWS * 16 + ln;
+            uint32_t m0 = park[0], m1 = park[64]; /* the memory does not stay in registers through the tick */
+            PolicyStore st{tp, tp + ec_p, danger + ec_p, sets + ec_p, member_p};
+            const PomPolicyEnv E{{L.a0[0], L.a0[1], L.a0[2], L.a0[3]}, {accp.ag1(0), accp.ag1(1), accp.ag1(2), accp.ag1(3)}, L.bIdx, L.bCnt};
+            if (!done) { /* all four lanes of the env, dead agents' lanes included */
+                pom_policy_prepare_clear(st);
+                pom_policy_prepare_fill(st, E);
+                pom_policy_prepare_safe(st);
+            }
+            /* act() is only asked of live agents (environment.cpp:139-146); the wavefront's searches run together: EVERY lane goes in */
+            const bool actor = !done && simple && !ag_dead(sel4(member_p, L.a0));
+#if defined(POM_DIAG)
+            long long pt_last = 0, pt_acc[POM_PP_N];
+            mine = pom_policy_wave(st, E, member_p, m0, m1, actor, (int)((r16 * 5u) >> 16), sets, ln, pt_last, pt_acc);
+#else
+            mine = pom_policy_wave(st, E, member_p, m0, m1, actor, (int)((r16 * 5u) >> 16), sets, ln);
+#endif
+            park[0] = m0;
+            park[64] = m1;
+            /* the caller's move of tick 1: a SimpleAgent overridden here has been asked all the same, its memory has moved on */
+            if (fixed) mine = (int)park[128];
+        }
+        if (!done) { /* the quad's four lanes agree */
+            if (!fixed && !simple) mine = pom_rng_pick(r16, p.dist); /* the stream's move (dead agents get theirs too) */
+            int ln2 = lane;
+            uint32_t* t2 = tile;
+            if (POLICY) asm volatile("" : "+v"(ln2), "+v"(t2));
+            const int ec2 = ln2 >> 2, member2 = ln2 & 3;
+            LdsEnv<16, 4> acc2(t2, ec2, member2);
+            PomStepper<LdsEnv<16, 4>> stepper2(acc2, L);
+            const uint32_t mvp = stepper2.pack_moves_quad(mine);
+            L.ub = 0;
+            stepper2.step_packed(mvp);
+            /* Environment::Step's bookkeeping whatever the handle's mode (environment.cpp:148-168); timeStep is looked at here only: read
+             * back from the tile instead of living in a register through the tick */
+            uint32_t* const ts = t2 + ec2 + POM_REC_TIMESTEP * 16;
+            const int time_step = (int)*ts + 1;
+            if (member2 == 0) *ts = (uint32_t)time_step;
+            const uint32_t status = pom_env_epilogue(L, time_step, p.max_steps, run & 0xFFu);
+            run = status | (run & 0x100u) | (L.ub ? 0x100u : 0u) | ((uint32_t)tk << 16);
+        }
+    }
+
+    /* out: pom_rollout_kernel's word, one dword per env from its owner lane */
+    if (valid && member == 0) {
+        uint32_t alive = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) alive |= (uint32_t)(ag_dead(L.a0[i]) ^ 1) << i;
+        const uint32_t status = run & 0xFFu;
+        const uint32_t word = alive | ((status & (POM_ST_DONE | POM_ST_DRAW)) << 4) | ((status & POM_ST_TIMEOUT) << 1) |
+                              ((run & 0x100u) ? (uint32_t)POM_RO_UB : 0u) | (((status >> POM_ST_WINNER_SHIFT) & 7u) << POM_RO_WINNER_SHIFT) |
+                              ((run >> 16) << POM_RO_LENGTH_SHIFT);
+        p.result[(int64_t)sample * p.n + e] = word;
+    }
+}
+
+#endif /* POM_ROLLOUT_POLICY_H_ */
