@@ -1336,33 +1336,57 @@ extern "C" int pom_batch_forecast(PomBatch* h, const PomForecastSpec* s)
 /* ---- the rollout (pom_batch.h PomRolloutSpec): R random playouts of every env on scratch copies of its tile.  Its kernel comes
  * after the forecast's, so that every kernel before it is emitted as it was without it ---- */
 #include "pom_rollout.h"
+/* ---- the policy rollout (pom_batch.h PomRolloutPolicySpec): the rollout with SimpleAgent for the agents of simple_mask and a
+ * per-agent first tick.  Its kernel comes after the rollout's, so that every kernel before it is emitted as it was without it ---- */
+#include "pom_rollout_policy.h"
 
 static_assert(sizeof(PomRolloutSpec) == POM_ROLLOUT_SPEC_SIZE, "pom_batch.h states the size");
+static_assert(sizeof(PomRolloutPolicySpec) == POM_ROLLOUT_POLICY_SPEC_SIZE, "pom_batch.h states the size");
+
+static int rollout_bad_arg(const char* who, const char* what)
+{
+    snprintf(g_err, sizeof g_err, "%s: %s", who, what);
+    return POM_E_ARG;
+}
+
+/* What the two entry points share, up to the launch: the checks on the handle and on the fields both specs have (the callers have
+ * checked what is their own), the device, the settling, and the grid — tiles of 16 envs, and the same rounded up to a multiple of
+ * 8 (the grid is samples * tiles8).  *tiles == 0 on return: nothing to launch (an error, or an empty batch) */
+static int rollout_begin(PomBatch* h, const char* who, int32_t horizon, int32_t samples, int32_t dist, const int32_t* moves_dev,
+                         const uint32_t* result_dev, int64_t* tiles, int64_t* tiles8)
+{
+    const char* what = nullptr;
+    const int64_t t = h ? (h->n + 15) / 16 : 0, t8 = (t + 7) / 8 * 8;
+    *tiles = *tiles8 = 0;
+    if (!h) what = "the handle is NULL";
+    else if (horizon < 1 || horizon > POM_ROLLOUT_MAX_TICKS) what = "horizon must be 1..1024";
+    else if (samples < 1 || samples > POM_ROLLOUT_MAX_SAMPLES) what = "samples must be 1..256";
+    else if (dist < POM_DIST_HARMLESS || dist > POM_DIST_STRESS) what = "dist must be POM_DIST_HARMLESS, _RANDOM or _STRESS";
+    else if (!result_dev) what = "result_dev is NULL";
+    else if ((uintptr_t)result_dev & 15) what = "result_dev must be 16-byte aligned";
+    else if ((uintptr_t)moves_dev & 3) what = "moves_dev must be 4-byte aligned";
+    else if (t8 * samples > (int64_t)INT_MAX) what = "samples x tiles of 16 envs exceed one grid: call with fewer samples";
+    if (what) return rollout_bad_arg(who, what);
+    HIPCHK(hipSetDevice(h->device));
+    /* quiesce, not only join (as pom_batch_forecast): after chained launches a tile left behind is caught up first — the playouts
+     * start from the state a download returns */
+    if (int jr = quiesce(h)) return jr;
+    *tiles = t;
+    *tiles8 = t8;
+    return POM_OK;
+}
 
 extern "C" int pom_batch_rollout(PomBatch* h, const PomRolloutSpec* s)
 {
+    static const char who[] = "pom_batch_rollout";
     const char* what = nullptr;
-    const int64_t tiles = h ? (h->n + 15) / 16 : 0, tiles8 = (tiles + 7) / 8 * 8;
-    if (!h) what = "the handle is NULL";
-    else if (!s) what = "the spec is NULL";
+    if (!s) what = "the spec is NULL";
     else if (s->struct_size != (int32_t)sizeof(PomRolloutSpec)) what = "struct_size is not sizeof(PomRolloutSpec)";
-    else if (s->horizon < 1 || s->horizon > POM_ROLLOUT_MAX_TICKS) what = "horizon must be 1..1024";
-    else if (s->samples < 1 || s->samples > POM_ROLLOUT_MAX_SAMPLES) what = "samples must be 1..256";
-    else if (s->dist < POM_DIST_HARMLESS || s->dist > POM_DIST_STRESS) what = "dist must be POM_DIST_HARMLESS, _RANDOM or _STRESS";
     else if (s->reserved_ != 0) what = "reserved_ must be 0";
-    else if (!s->result_dev) what = "result_dev is NULL";
-    else if ((uintptr_t)s->result_dev & 15) what = "result_dev must be 16-byte aligned";
-    else if ((uintptr_t)s->moves_dev & 3) what = "moves_dev must be 4-byte aligned";
-    else if (tiles8 * s->samples > (int64_t)INT_MAX) what = "samples x tiles of 16 envs exceed one grid: call with fewer samples";
-    if (what) {
-        snprintf(g_err, sizeof g_err, "pom_batch_rollout: %s", what);
-        return POM_E_ARG;
-    }
-    HIPCHK(hipSetDevice(h->device));
-    /* quiesce, not only join (as pom_batch_forecast): after chained launches a tile left behind is caught up first — the rollout
-     * starts from the state a download returns */
-    if (int jr = quiesce(h)) return jr;
-    if (tiles == 0) return POM_OK;
+    if (what) return rollout_bad_arg(who, what);
+    int64_t tiles, tiles8;
+    const int rc = rollout_begin(h, who, s->horizon, s->samples, s->dist, s->moves_dev, s->result_dev, &tiles, &tiles8);
+    if (rc || tiles == 0) return rc;
     RolloutParams p;
     p.state = h->state;
     p.moves = s->moves_dev;
@@ -1380,39 +1404,21 @@ extern "C" int pom_batch_rollout(PomBatch* h, const PomRolloutSpec* s)
     return POM_OK;
 }
 
-/* ---- the policy rollout (pom_batch.h PomRolloutPolicySpec): the rollout with SimpleAgent for the agents of simple_mask and a
- * per-agent first tick.  Its kernel comes after the rollout's, so that every kernel before it is emitted as it was without it ---- */
-#include "pom_rollout_policy.h"
-
-static_assert(sizeof(PomRolloutPolicySpec) == POM_ROLLOUT_POLICY_SPEC_SIZE, "pom_batch.h states the size");
-
 extern "C" int pom_batch_rollout_policy(PomBatch* h, const PomRolloutPolicySpec* s)
 {
+    static const char who[] = "pom_batch_rollout_policy";
     const char* what = nullptr;
-    const int64_t tiles = h ? (h->n + 15) / 16 : 0, tiles8 = (tiles + 7) / 8 * 8;
-    if (!h) what = "the handle is NULL";
-    else if (!s) what = "the spec is NULL";
+    if (!s) what = "the spec is NULL";
     else if (s->struct_size != (int32_t)sizeof(PomRolloutPolicySpec)) what = "struct_size is not sizeof(PomRolloutPolicySpec)";
-    else if (s->horizon < 1 || s->horizon > POM_ROLLOUT_MAX_TICKS) what = "horizon must be 1..1024";
-    else if (s->samples < 1 || s->samples > POM_ROLLOUT_MAX_SAMPLES) what = "samples must be 1..256";
-    else if (s->dist < POM_DIST_HARMLESS || s->dist > POM_DIST_STRESS) what = "dist must be POM_DIST_HARMLESS, _RANDOM or _STRESS";
     else if (s->simple_mask < 0 || s->simple_mask > 15) what = "simple_mask must be 0..15";
     else if (s->first_mask < 0 || s->first_mask > 15) what = "first_mask must be 0..15";
     else if (s->flags & ~(int32_t)POM_ROLLOUT_FRESH_AGENTS) what = "flags must be 0 or POM_ROLLOUT_FRESH_AGENTS";
     else if (s->reserved_ != 0) what = "reserved_ must be 0";
     else if (s->first_mask != 0 && !s->moves_dev) what = "first_mask names agents but moves_dev is NULL";
-    else if (!s->result_dev) what = "result_dev is NULL";
-    else if ((uintptr_t)s->result_dev & 15) what = "result_dev must be 16-byte aligned";
-    else if ((uintptr_t)s->moves_dev & 3) what = "moves_dev must be 4-byte aligned";
-    else if (tiles8 * s->samples > (int64_t)INT_MAX) what = "samples x tiles of 16 envs exceed one grid: call with fewer samples";
-    if (what) {
-        snprintf(g_err, sizeof g_err, "pom_batch_rollout_policy: %s", what);
-        return POM_E_ARG;
-    }
-    HIPCHK(hipSetDevice(h->device));
-    /* quiesce, not only join (as pom_batch_rollout): the playouts start from the state a download returns */
-    if (int jr = quiesce(h)) return jr;
-    if (tiles == 0) return POM_OK;
+    if (what) return rollout_bad_arg(who, what);
+    int64_t tiles, tiles8;
+    const int rc = rollout_begin(h, who, s->horizon, s->samples, s->dist, s->moves_dev, s->result_dev, &tiles, &tiles8);
+    if (rc || tiles == 0) return rc;
     RolloutPolicyParams p;
     p.state = h->state;
     p.moves = s->first_mask ? s->moves_dev : nullptr; /* not read when no agent's first move is fixed */

@@ -370,6 +370,20 @@ __device__ __forceinline__ void lane_from_tile(PomLane& L, int& time_step, uint3
     time_step = (int)t[POM_REC_TIMESTEP * epw];
 }
 
+/* the diagnostic builds' fields of a lane, for a kernel that takes no part in them: the phase clocks at zero, and no cut (990 lies
+ * beyond every POM_CUT number of pom_step_body.h) — the diagnostic truncation is the step kernels' business.  Empty in a normal build */
+__device__ __forceinline__ void pom_lane_diag_off(PomLane& L)
+{
+#if defined(POM_DIAG)
+    for (int k = 0; k < POM_PH_N; k++) L.t_acc[k] = 0;
+    L.t_last = 0;
+#endif
+#if defined(POM_TRUNC)
+    L.trunc = 990;
+#endif
+    (void)L;
+}
+
 /* the four lanes of an env as the SimpleAgent policy sees them (pom_policy_body.h): lane = agent, 16 envs per wavefront */
 struct PolicyStore {
     const uint32_t* tile0; /* the wavefront's tile */

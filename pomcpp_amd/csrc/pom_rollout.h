@@ -62,13 +62,7 @@ __global__ __launch_bounds__(64, POM_QUAD_WAVES) void pom_rollout_kernel(Rollout
     int time_step = 0;
     uint32_t status = 0;
     lane_from_tile(L, time_step, status, t, 16);
-#if defined(POM_DIAG)
-    for (int k = 0; k < POM_PH_N; k++) L.t_acc[k] = 0;
-    L.t_last = 0;
-#endif
-#if defined(POM_TRUNC)
-    L.trunc = 990; /* no cut: the diagnostic truncation is the step kernels' business */
-#endif
+    pom_lane_diag_off(L);
     LdsEnv<16, 4> acc(tile, ec, member);
     PomStepper<LdsEnv<16, 4>> stepper(acc, L);
 

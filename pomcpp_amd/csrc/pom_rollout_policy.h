@@ -85,13 +85,7 @@ __global__ __launch_bounds__(64, 4) void pom_rollout_policy_kernel(RolloutPolicy
         run &= 0xFFu & ~(uint32_t)POM_ST_RESTARTED;
         if (!valid) run |= POM_ST_DONE; /* the lanes of an env past the batch's end count as done from the start; they write nothing */
     }
-#if defined(POM_DIAG)
-    for (int k = 0; k < POM_PH_N; k++) L.t_acc[k] = 0;
-    L.t_last = 0;
-#endif
-#if defined(POM_TRUNC)
-    L.trunc = 990; /* no cut: the diagnostic truncation is the step kernels' business */
-#endif
+    pom_lane_diag_off(L);
 
     const int K = p.horizon;
     POM_NOUNROLL

@@ -12,24 +12,16 @@ import pytest
 from pomcpp_amd.state import STATE_DTYPE
 from tests import forecast_cases as FC
 from tests import rollout_oracle as RO
+from tests.rollout_gpu import POOL, _dev, _env, _everything, _played, _same, _words
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "rollout.npz")
 SIZES = [5, 16, 67, 200]          # a short last tile, one whole tile, n no multiple of 4, several tiles
 SAMPLES = [1, 3, 8]
 HORIZONS = [1, 8, 48]
-POOL = 200                        # the batches of every size are the first n states of one pool: env e has the same key in all
 # boards x move stream: every distribution, and the stress boards under POM_DIST_RANDOM, where a tick raises POM_UB_NULL_BOMB
 COMBOS = [("ffa", 57, RO.DIST_HARMLESS), ("ffa", 57, RO.DIST_RANDOM), ("stress", 23, RO.DIST_STRESS), ("stress", 23, RO.DIST_RANDOM)]
 SEED = 99
-
-
-@functools.lru_cache(maxsize=None)
-def _played(kind, ticks, n=POOL):
-    from tests.oracle_lib import Oracle
-    s = FC.played_states(Oracle(), kind, n, ticks)
-    s.setflags(write=False)
-    return s
 
 
 def _first_moves(with_moves, horizon, n=POOL):
@@ -44,29 +36,6 @@ def _want(kind, ticks, dist, horizon, with_moves, max_steps=0):
     w = RO.rollout(Oracle(), _played(kind, ticks), horizon, max(SAMPLES), SEED, dist, _first_moves(with_moves, horizon), max_steps)
     w.setflags(write=False)
     return w
-
-
-def _env(states, **kw):
-    from pomcpp_amd.batch import BatchEnvironment, MODE_ENV
-    kw.setdefault("mode", MODE_ENV)
-    env = BatchEnvironment(len(states), **kw)
-    env.make_game(states)
-    return env
-
-
-def _dev(a):
-    import torch
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
-
-
-def _words(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
-def _same(got, want, what):
-    got = _words(got)
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, f"{what}: {len(bad)} words differ, first (sample, env) {bad[0].tolist()}: got {got[tuple(bad[0])]:#x}, want {want[tuple(bad[0])]:#x}"
 
 
 @pytest.mark.gpu
@@ -199,15 +168,6 @@ def test_words_do_not_depend_on_the_wavefront_mates(hip_lib, oracle):
     with _env(states) as env:
         got = env.rollout(horizon, R, SEED, DIST_RANDOM, moves=_dev(moves))
         _same(got[:, _dev(at.astype(np.int64))], want, "actors among stress mates")
-
-
-def _everything(env):
-    """all the API can read of a handle"""
-    out = dict(state=env.get_state().tobytes(), terminal=env.get_terminal_state().tobytes(), counters=env.counters().tolist(),
-               episodes=env.episodes().tolist(), memory=env.policy_memory().tobytes(), chain=env.chain_stats())
-    out.update({"status_" + k: v.tolist() for k, v in env.status().items()})
-    out.update({"last_" + k: v.tolist() for k, v in env.last_results().items()})
-    return out
 
 
 @pytest.mark.gpu

@@ -14,6 +14,7 @@ from pomcpp_amd.state import STATE_DTYPE
 from tests import forecast_cases as FC
 from tests import rollout_oracle as RO
 from tests import rollout_policy_oracle as PO
+from tests.rollout_gpu import POOL, _dev, _env, _everything, _played, _same, _words
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "rollout_policy.npz")
@@ -21,18 +22,9 @@ SIZES = [5, 16, 67, 200]          # a short last tile, one whole tile, n no mult
 SAMPLES = [1, 3]
 HORIZONS = [1, 8, 48]
 MASKS = [0xF, 0xE, 0x5]
-POOL = 200                        # the batches of every size are the first n states of one pool: env e has the same key in all
 KINDS = [("ffa", 57, RO.DIST_RANDOM), ("stress", 23, RO.DIST_STRESS)]   # boards and the stream of the agents outside the mask
 FIRST = 0x3                       # with `first`: agents 0 and 1 — a SimpleAgent and, under 0xE, the random one
 SEED = 99
-
-
-@functools.lru_cache(maxsize=None)
-def _played(kind, ticks, n=POOL):
-    from tests.oracle_lib import Oracle
-    s = FC.played_states(Oracle(), kind, n, ticks)
-    s.setflags(write=False)
-    return s
 
 
 def _first_moves(horizon, n=POOL):
@@ -48,29 +40,6 @@ def _want(kind, ticks, dist, horizon, simple, first, samples=max(SAMPLES), n=POO
                    _first_moves(horizon)[:n] if first else None, max_steps)
     w.setflags(write=False)
     return w
-
-
-def _env(states, **kw):
-    from pomcpp_amd.batch import BatchEnvironment, MODE_ENV
-    kw.setdefault("mode", MODE_ENV)
-    env = BatchEnvironment(len(states), **kw)
-    env.make_game(states)
-    return env
-
-
-def _dev(a):
-    import torch
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
-
-
-def _words(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
-def _same(got, want, what):
-    got = _words(got)
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, f"{what}: {len(bad)} words differ, first (sample, env) {bad[0].tolist()}: got {got[tuple(bad[0])]:#x}, want {want[tuple(bad[0])]:#x}"
 
 
 @pytest.mark.gpu
@@ -208,6 +177,9 @@ def test_second_witness_mixed_mask(hip_lib):
 @pytest.mark.gpu
 @pytest.mark.parametrize("with_moves", [False, True])
 def test_without_simple_agents_it_is_the_existing_rollout(hip_lib, with_moves):
+    """the header's equivalence between the two entry points, which launch two kernels: pom_batch_rollout_policy with an empty
+    simple_mask (pom_rollout_policy_kernel<false>) and first_mask 0xF when it is given moves, 0 when not, gives pom_batch_rollout's
+    (pom_rollout_kernel's) words bit for bit; and moves that no agent is named for are not read"""
     from pomcpp_amd.batch import DIST_STRESS
     n = 67
     mv = _dev(FC.random_moves(n, 5)) if with_moves else None
@@ -259,15 +231,6 @@ def test_words_do_not_depend_on_the_wavefront_mates(hip_lib, oracle):
     with _env(states) as env:
         got = env.rollout(horizon, R, SEED, DIST_RANDOM, simple=0xF)
         _same(got[:, _dev(at.astype(np.int64))], want, "actors among stress mates")
-
-
-def _everything(env):
-    """all the API can read of a handle"""
-    out = dict(state=env.get_state().tobytes(), terminal=env.get_terminal_state().tobytes(), counters=env.counters().tolist(),
-               episodes=env.episodes().tolist(), memory=env.policy_memory().tobytes(), chain=env.chain_stats())
-    out.update({"status_" + k: v.tolist() for k, v in env.status().items()})
-    out.update({"last_" + k: v.tolist() for k, v in env.last_results().items()})
-    return out
 
 
 @pytest.mark.gpu
