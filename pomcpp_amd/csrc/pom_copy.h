@@ -92,7 +92,7 @@ __global__ __launch_bounds__(64) void pom_copy_gather_kernel(CopyParams p)
         }
     }
     __syncthreads();
-    store_tile16_x4(p.out_state + t * POM_TILE_DWORDS, POM_TILE_ENVS, tile, lane);
+    store_tile16_x4(p.out_state + t * POM_TILE_DWORDS, tile, lane);
 }
 
 /* scatter = false: only the snapshots (the host variant's shortcut, where K1 wrote the real arrays) */

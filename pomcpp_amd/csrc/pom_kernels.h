@@ -284,42 +284,59 @@ __device__ __forceinline__ void store_tile(uint32_t* col, int64_t np, const uint
 /* EPW = 16: the same movement in 16-byte pieces (gfx950's global_load_lds_dwordx4 / dwordx4 stores).  A tile row is 16 envs
  * = 64 contiguous bytes in HBM and in LDS, so lane l takes envs 4(l%4)..+3 of row r0 + l/4 and one instruction covers 16 rows:
  * for the 80 rows of a record five whole instructions per direction (a row count that is no multiple of 16 ends with one in which
- * only the lanes of the remaining rows take part).  `base` = the tile's first dword, np = the row stride: with the buffers laid out tile by tile
- * (pom_packed.h) np = 16 and a whole instruction moves 1,024 contiguous bytes. */
+ * only the lanes of the remaining rows take part).  `base` = the tile's first dword: the buffers are laid out tile by tile (pom_packed.h),
+ * a row stride of POM_TILE_ENVS = 16 dwords, and a whole instruction moves 1,024 contiguous bytes. */
 /* AUX: the instruction's cache policy bits (16 = sc1: served by the L2, never by this CU's vector cache) */
+/* Addresses: the tile's first byte is wave-uniform and a lane's piece lies less than 1,024 bytes behind it, so an address is a
+ * scalar base plus a 32-bit lane offset plus the instruction's immediate — no 64-bit vector arithmetic per instruction.  The
+ * immediate of a load to LDS counts for the LDS address as well (it holds up to 4,095): the rows of a record are reached from two
+ * bases, rows 0..63 and 64.. — on both sides — and the instructions of a base follow each other with nothing in between. */
+typedef __attribute__((address_space(3))) char pom_lds_char;
+template <int R0, int ROWS, int AUX>
+__device__ __forceinline__ void load_tile16_x4_from(const char* base, uint32_t off, pom_lds_char* tile) /* the whole row groups from row R0 on */
+{
+    if constexpr (R0 + 16 <= ROWS) {
+        constexpr int B0 = R0 / 64 * 64; /* the base this row group is reached from: 64 rows = 4,096 bytes */
+        const char* b = base + B0 * 64;
+        if (B0 != 0) asm("" : "+s"(b)); /* (a second scalar base — not the first with the 4,096 added per lane in 64 bits) */
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(b + off),
+                                         (__attribute__((address_space(3))) void*)(tile + B0 * 64), 16, (R0 - B0) * 64, AUX);
+        load_tile16_x4_from<R0 + 16, ROWS, AUX>(base, off, tile);
+    }
+}
 template <int ROWS = POM_REC_DWORDS, int AUX = 0>
-__device__ __forceinline__ void load_tile16_x4(const uint32_t* base, int64_t np, uint32_t* tile, int lane)
+__device__ __forceinline__ void load_tile16_x4(const uint32_t* base, uint32_t* tile, int lane)
 {
     static_assert(ROWS <= POM_REC_DWORDS, "inside the record");
-    const uint32_t* g = base + (int64_t)(lane >> 2) * np + 4 * (lane & 3);
-    const int64_t stride = 16 * np;
-#pragma unroll
-    for (int r0 = 0; r0 + 16 <= ROWS; r0 += 16) {
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                         (__attribute__((address_space(3))) void*)(tile + r0 * 16), 16, 0, AUX);
-        g += stride;
-    }
+    static_assert(POM_TILE_ENVS == 16, "a row is 64 contiguous bytes on both sides: what the immediates say");
+    const char* const b = reinterpret_cast<const char*>(base);
+    const uint32_t off = 16u * (uint32_t)lane;
+    pom_lds_char* const t = (pom_lds_char*)tile; /* (as an LDS address first, the offsets added to that) */
+    load_tile16_x4_from<0, ROWS, AUX>(b, off, t);
     if (ROWS % 16 != 0 && (lane >> 2) < ROWS % 16) /* the last rows: the lanes beyond them sit this one out */
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                         (__attribute__((address_space(3))) void*)(tile + (ROWS / 16) * 16 * 16), 16, 0, AUX);
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((b + (ROWS / 16) * 16 * 64) + off),
+                                         (__attribute__((address_space(3))) void*)(t + (ROWS / 16) * 16 * 64), 16, 0, AUX);
 }
 template <bool NT = false>
-__device__ __forceinline__ void store_tile16_x4(uint32_t* base, int64_t np, const uint32_t* tile, int lane)
+__device__ __forceinline__ void store_tile16_x4(uint32_t* base, const uint32_t* tile, int lane)
 {
     constexpr int ROWS = POM_REC_DWORDS;
-    uint4* g = reinterpret_cast<uint4*>(base + (int64_t)(lane >> 2) * np + 4 * (lane & 3));
-    const int64_t stride = 4 * np; /* in uint4 */
+    static_assert(POM_TILE_ENVS == 16, "a row is 64 contiguous bytes on both sides, as in load_tile16_x4");
+    const uint32_t off = 16u * (uint32_t)lane; /* bytes */
+    char* const b = reinterpret_cast<char*>(base);
+    constexpr int stride = 1024; /* bytes between row groups */
     const uint4* l = reinterpret_cast<const uint4*>(tile) + lane;
     typedef uint32_t pom_u32x4 __attribute__((ext_vector_type(4)));
 #pragma unroll
     for (int r0 = 0; r0 + 16 <= ROWS; r0 += 16) {
+        uint4* g = reinterpret_cast<uint4*>((b + (r0 / 16) * stride) + off); /* scalar base + lane offset */
         if (NT) {
             const uint4 v = l[r0 * 4];
             __builtin_nontemporal_store(pom_u32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<pom_u32x4*>(g));
         } else *g = l[r0 * 4];
-        g += stride;
     }
     if (ROWS % 16 != 0 && (lane >> 2) < ROWS % 16) {
+        uint4* g = reinterpret_cast<uint4*>((b + (ROWS / 16) * stride) + off);
         if (NT) {
             const uint4 v = l[(ROWS / 16) * 16 * 4];
             __builtin_nontemporal_store(pom_u32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<pom_u32x4*>(g));
@@ -1278,6 +1295,21 @@ __device__ __forceinline__ uint32_t pom_load_shared(const uint32_t* ptr)
     return CHAIN ? __hip_atomic_load(ptr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *ptr;
 }
 
+/* pom_rng_pick (pom_rng.h; the same values) where `dist` is wave-uniform: the stress distribution's compare chain behind a BRANCH —
+ * as a select (what the compiler makes of the host's form) every tick of every distribution pays for both picks.  The quad step
+ * kernels use this; the one-lane-per-env kernels and the rollouts (pom_rollout.h) keep the select form */
+__device__ __forceinline__ int pom_rng_pick_uniform(uint32_t r16, int dist)
+{
+    int mv;
+    if (dist == POM_DIST_STRESS) {
+        mv = pom_rng_pick(r16, POM_DIST_STRESS);
+        asm volatile("" : "+v"(mv)); /* (nothing to execute: a block with it in is not folded into selects) */
+    } else {
+        mv = pom_rng_pick(r16, dist); /* (its uniform pick: the stress side folds away behind the branch) */
+    }
+    return mv;
+}
+
 /* OBS: the launch also writes the observation of the state it leaves behind (pom_observe_tile) — an RL tick is then one launch
  * and one read of the record instead of two of each. */
 /* VIEW (with OBS): the observation is the four agents' fogged views (PomViewSpec) — an instantiation of its own, not a branch in the
@@ -1369,8 +1401,8 @@ __global__ __launch_bounds__(64 * POM_WPB, (POLICY ? 4 : G == 4 ? POM_QUAD_WAVES
         if (!pom_chain_enter(word, chain_xcd, p.chain_seq0, p.tape_len, p.chain_wait_limit, p.chain_err, lane, cv)) return;
         tick0 += (uint32_t)cv.dist;
         /* the loads below are issued after the word has been seen: the record they fetch is the stored one */
-        load_tile16_x4<POM_REC_DWORDS, 16>(p.state + tile_id * POM_TILE_DWORDS, POM_TILE_ENVS, tile, lane);
-    } else if (EPW == 16) load_tile16_x4(p.state + tile_id * POM_TILE_DWORDS, POM_TILE_ENVS, tile, lane); /* 16-byte pieces, 7 instructions of 1 KB */
+        load_tile16_x4<POM_REC_DWORDS, 16>(p.state + tile_id * POM_TILE_DWORDS, tile, lane);
+    } else if (EPW == 16) load_tile16_x4(p.state + tile_id * POM_TILE_DWORDS, tile, lane); /* 16-byte pieces, 7 instructions of 1 KB */
     else load_tile<EPW>(col_d, POM_TILE_ENVS, tile, sub);
     uint32_t m0 = 0, m1 = 0; /* POLICY: this lane's agent's memory */
     if (POLICY) {
@@ -1380,23 +1412,35 @@ __global__ __launch_bounds__(64 * POM_WPB, (POLICY ? 4 : G == 4 ? POM_QUAD_WAVES
     /* the first tick's moves do not depend on the record: hash / fetch them while the record is on its way */
     uint64_t draw0 = 0;
     int4 moves0 = make_int4(0, 0, 0, 0);
+    int mine0 = POM_MOVE_IDLE; /* the one-tick quad kernels: lane m's agent's move, the one value that is carried to the tick */
     /* explicit moves come one tick per launch: the several-tick quad kernel never sees any (step_kernel) */
     constexpr bool TAKES_MOVES = SINGLE || G == 1;
+    constexpr bool QUAD1 = SINGLE && G == 4;
     if (!POLICY) {
-        if (TAKES_MOVES && p.moves) {
+        if (TAKES_MOVES && p.moves) { /* wave-uniform, and a branch: the side not taken costs nothing */
             /* chained: tick `chain_dist` of the caller's move tape (pom_batch_step_device_many) */
-            if (valid) moves0 = reinterpret_cast<const int4*>(p.moves)[(CHAIN ? (int64_t)cv.dist * p.n : (int64_t)0) + e];
+            if (QUAD1) { /* the quad's lanes take a dword each of their env's Move[4] */
+                /* Move[4] of env e = tile_id * 16 + lane / 4, agent lane % 4: the tile's 64 moves lie one behind the other */
+                const int32_t* const mt = p.moves + ((CHAIN ? (int64_t)cv.dist * p.n : (int64_t)0) + tile_id * EPW) * 4;
+                if (valid) mine0 = *reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(mt) + 4u * (uint32_t)lane);
+            } else if (valid) moves0 = reinterpret_cast<const int4*>(p.moves)[(CHAIN ? (int64_t)cv.dist * p.n : (int64_t)0) + e];
         } else {
             if (G == 4 && !SINGLE) { /* several ticks per launch: the draw is made where it is used, nothing to carry */
-            } else if (G == 4) draw0 = pom_rng_draw_half(p.seed, env_key, tick0, member >> 1); /* lane m needs agent m's 16 bits only */
-            else draw0 = pom_rng_draw(p.seed, env_key, tick0);
+            } else if (G == 4) { /* lane m needs agent m's 16 bits only */
+                mine0 = pom_rng_pick_uniform((pom_rng_draw_half(p.seed, env_key, tick0, member >> 1) >> (16 * (member & 1))) & 0xFFFFu, p.dist);
+            } else draw0 = pom_rng_draw(p.seed, env_key, tick0);
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); /* the DMA rows have landed (one wavefront per workgroup: no barrier) */
     PomLane L;
     int time_step = 0;
     uint32_t status = 0;
-    lane_from_tile(L, time_step, status, t, EPW);
+    /* the one-tick kernels that restart at the start of the tick look at the status byte alone first: whether an env restarts is
+     * known before its register rows are unpacked, and they are unpacked ONCE, behind the restarts — not a second time in the
+     * wavefronts that restart somebody (about half of them) */
+    constexpr bool UNPACK_LATE = SINGLE && !ATEND;
+    if (UNPACK_LATE) status = t[(POM_REC_AGENTS + 3) * EPW] >> 24; /* (as pom_lane_load reads it) */
+    else lane_from_tile(L, time_step, status, t, EPW);
     bool restarted = false;
 
     LdsEnv<EPW, G> acc(tile, ec, member);
@@ -1434,7 +1478,7 @@ __global__ __launch_bounds__(64 * POM_WPB, (POLICY ? 4 : G == 4 ? POM_QUAD_WAVES
                 pom_boardgen_wave<EPW, POM_REC_DWORDS>(tile, ec_u, (uint32_t)__builtin_amdgcn_readfirstlane((int)key), lane);
             }
             asm volatile("" ::: "memory"); /* other lanes wrote this lane's column: no read of it may be scheduled earlier */
-            if (reload) lane_from_tile(L, time_step, status, t, EPW); /* the register-resident rows, from the new record */
+            if (!UNPACK_LATE && reload) lane_from_tile(L, time_step, status, t, EPW); /* the register-resident rows, from the new record */
             restarted = reload;
             c_resets += __popcll(__ballot(reload && owner));
         } else {
@@ -1454,10 +1498,11 @@ __global__ __launch_bounds__(64 * POM_WPB, (POLICY ? 4 : G == 4 ? POM_QUAD_WAVES
                     restart_column<EPW>(tile, ec_u, p.snap + (tile_id * EPW + ec_u) * POM_REC_DWORDS, lane_now);
                 } while (todo);
                 asm volatile("" ::: "memory"); /* other lanes wrote this lane's column: no read of it may be scheduled earlier */
-                if (reload) lane_from_tile(L, time_step, status, t, EPW); /* the register-resident rows, from the new record */
+                if (!UNPACK_LATE && reload) lane_from_tile(L, time_step, status, t, EPW); /* the register-resident rows, from the new record */
             }
             restarted = reload;
         }
+        if (UNPACK_LATE) lane_from_tile(L, time_step, status, t, EPW); /* every lane's register rows, restarted or not */
         const bool active = valid && !(env_mode && (status & POM_ST_DONE));
         bool newly_done = false, new_ub = false;
         int mv_own = POM_MOVE_IDLE;
@@ -1505,12 +1550,11 @@ __global__ __launch_bounds__(64 * POM_WPB, (POLICY ? 4 : G == 4 ? POM_QUAD_WAVES
                 int mine;
                 if (POLICY) {
                     mine = mv_own;
-                } else if (TAKES_MOVES && p.moves) { /* explicit moves: one tick per launch */
-                    const int lo = (member & 1) ? moves0.y : moves0.x, hi = (member & 1) ? moves0.w : moves0.z;
-                    mine = (member & 2) ? hi : lo;
+                } else if (SINGLE) { /* explicit or drawn: chosen while the record was on its way */
+                    mine = mine0;
                 } else {
-                    const uint32_t r = SINGLE ? (uint32_t)draw0 : pom_rng_draw_half(p.seed, env_key, tick0 + (uint32_t)tk, member >> 1);
-                    mine = pom_rng_pick((r >> (16 * (member & 1))) & 0xFFFFu, p.dist);
+                    const uint32_t r = pom_rng_draw_half(p.seed, env_key, tick0 + (uint32_t)tk, member >> 1);
+                    mine = pom_rng_pick_uniform((r >> (16 * (member & 1))) & 0xFFFFu, p.dist);
                 }
                 mvp = stepper.pack_moves_quad(mine);
             } else {
@@ -1620,7 +1664,7 @@ __global__ __launch_bounds__(64 * POM_WPB, (POLICY ? 4 : G == 4 ? POM_QUAD_WAVES
         asm volatile("" : "+v"(lane_late));
         /* chained: with the non-temporal hint (-2.5 % per step: the stores are acknowledged sooner and the wavefront's slot is free
          * sooner; on the sub-batch kernels' stores, or on the loads, the hint gains nothing or loses) */
-        store_tile16_x4<CHAIN>(p.state + tile_id * POM_TILE_DWORDS, POM_TILE_ENVS, tile, lane_late);
+        store_tile16_x4<CHAIN>(p.state + tile_id * POM_TILE_DWORDS, tile, lane_late);
     } else {
         store_tile<EPW>(col_d, POM_TILE_ENVS, tile, sub, el);
     }
@@ -1713,7 +1757,7 @@ __global__ __launch_bounds__(64) void pom_chain_litmus_kernel(LitmusParams p)
     unsigned long long* const word = p.tile_seq + tile_id * POM_CHAIN_WORD_STRIDE;
     PomChainVisit cv;
     if (!pom_chain_enter(word, xcd, p.chain_seq0, 0u, p.wait_limit, p.err, lane, cv)) return;
-    load_tile16_x4<POM_REC_DWORDS, 16>(p.data + tile_id * POM_TILE_DWORDS, POM_TILE_ENVS, tile, lane);
+    load_tile16_x4<POM_REC_DWORDS, 16>(p.data + tile_id * POM_TILE_DWORDS, tile, lane);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const uint32_t expect = p.chain_seq0 + (uint32_t)cv.dist; /* = this visit's number: as many visits are stored */
     const uint32_t tag = (uint32_t)tile_id * 2654435761u;
@@ -1725,7 +1769,7 @@ __global__ __launch_bounds__(64) void pom_chain_litmus_kernel(LitmusParams p)
     }
     for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    store_tile16_x4<true>(p.data + tile_id * POM_TILE_DWORDS, POM_TILE_ENVS, tile, lane);
+    store_tile16_x4<true>(p.data + tile_id * POM_TILE_DWORDS, tile, lane);
     pom_chain_leave(word, lane, cv);
     if (lane == 0) {
         if (bad) {
@@ -1808,7 +1852,7 @@ __global__ __launch_bounds__(64) void pom_policy_kernel(PolicyParams p)
 #if defined(POM_DIAG)
     long long t_last = (long long)clock64(), t_acc[POM_PP_N] = {0, 0, 0, 0, 0, 0, 0};
 #endif
-    load_tile16_x4<POL_LOAD_ROWS>(p.state + tile_id * POM_TILE_DWORDS, POM_TILE_ENVS, tile, lane);
+    load_tile16_x4<POL_LOAD_ROWS>(p.state + tile_id * POM_TILE_DWORDS, tile, lane);
     /* the policy: lane -> (env lane/4, agent lane%4) */
     const int ec = lane >> 2, id = lane & 3;
     const int64_t e = tile_id * 16 + ec;
@@ -1894,7 +1938,7 @@ __global__ __launch_bounds__(64) void pom_observe_kernel(ObserveParams p)
     const int lane = threadIdx.x;
     const int64_t tile_local = pom_xcd_tile_order(blockIdx.x, gridDim.x);
     const int64_t tile_id = p.block0 + tile_local;
-    load_tile16_x4(p.state + tile_id * POM_TILE_DWORDS, POM_TILE_ENVS, tile, lane);
+    load_tile16_x4(p.state + tile_id * POM_TILE_DWORDS, tile, lane);
     /* The builtin, not inline asm: the compiler's own wait-count bookkeeping must SEE that the LDS-DMA rows have landed before the
      * pass loop begins — otherwise it assumes at the loop's head that they may still be in flight and puts an s_waitcnt vmcnt(0) in
      * front of the first tile read of EVERY pass, which (stores count in vmcnt too) waits for the previous pass's global stores:
@@ -1912,7 +1956,7 @@ __global__ __launch_bounds__(64) void pom_observe_view_kernel(ObserveParams p)
     const int lane = threadIdx.x;
     const int64_t tile_local = pom_xcd_tile_order(blockIdx.x, gridDim.x);
     const int64_t tile_id = p.block0 + tile_local;
-    load_tile16_x4(p.state + tile_id * POM_TILE_DWORDS, POM_TILE_ENVS, tile, lane);
+    load_tile16_x4(p.state + tile_id * POM_TILE_DWORDS, tile, lane);
     __builtin_amdgcn_s_waitcnt(0x0F70); /* (as in pom_observe_kernel: the compiler must see that the rows have landed) */
     asm volatile("" ::: "memory");
     pom_observe_tile<OBS_PASS_ENVS_ALONE, true>(p, tile, stage, tile_id, lane);
@@ -1935,7 +1979,7 @@ __global__ __launch_bounds__(64) void pom_generate_kernel(uint32_t* state, uint3
     if (tile_id * 16 + lane < n && lane < 16) episode[tile_id * 16 + lane] = 0u;
     __syncthreads();
     /* whole tiles: the buffers hold n_pad columns; columns past n are blank records here, as after creation */
-    store_tile16_x4(state + tile_id * POM_TILE_DWORDS, POM_TILE_ENVS, tile, lane);
+    store_tile16_x4(state + tile_id * POM_TILE_DWORDS, tile, lane);
     for (int ec = 0; ec < 16; ec++) { /* the snapshot: array of structs (restart_column); columns past n are blank like the state's */
         column_to_record<16>(tile, ec, snap + (tile_id * 16 + ec) * POM_REC_DWORDS, lane);
     }

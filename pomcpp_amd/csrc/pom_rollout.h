@@ -46,7 +46,7 @@ __global__ __launch_bounds__(64, POM_QUAD_WAVES) void pom_rollout_kernel(Rollout
     const int64_t tile_id = pom_xcd_tile_order(slot, p.tiles);
     /* the HBM layout is 16-env tiles whatever the handle's launch shape; the buffers hold n_pad columns, so a last, short tile is
      * loaded whole */
-    load_tile16_x4(p.state + tile_id * POM_TILE_DWORDS, POM_TILE_ENVS, tile, lane);
+    load_tile16_x4(p.state + tile_id * POM_TILE_DWORDS, tile, lane);
     /* the tick: lane -> (env lane / 4, member lane % 4) as in pom_step_kernel<16, 4> */
     const int ec = lane >> 2, member = lane & 3;
     const int64_t e = tile_id * 16 + ec;

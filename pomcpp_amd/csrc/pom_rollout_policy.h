@@ -53,7 +53,7 @@ __global__ __launch_bounds__(64, 4) void pom_rollout_policy_kernel(RolloutPolicy
     const uint32_t sample = blockIdx.x / p.tiles8, slot = blockIdx.x - sample * p.tiles8;
     if (slot >= p.tiles) return; /* a workgroup of the padding */
     const int64_t tile_id = pom_xcd_tile_order(slot, p.tiles);
-    load_tile16_x4(p.state + tile_id * POM_TILE_DWORDS, POM_TILE_ENVS, tile, lane);
+    load_tile16_x4(p.state + tile_id * POM_TILE_DWORDS, tile, lane);
     /* lane -> (env lane / 4, agent lane % 4) */
     const int ec = lane >> 2, member = lane & 3;
     const int64_t e = tile_id * 16 + ec;
