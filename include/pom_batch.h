@@ -443,11 +443,12 @@ int pom_batch_forecast(PomBatch* h, const PomForecastSpec* spec);
  *          (POM_ROLLOUT_SPEC_SIZE), horizon outside 1 .. POM_ROLLOUT_MAX_TICKS, samples outside 1 .. POM_ROLLOUT_MAX_SAMPLES, dist
  *          no POM_DIST_*, nonzero reserved_, a null result_dev, result_dev not 16-byte aligned, moves_dev not 4-byte aligned; and a
  *          batch so large that samples x tiles does not fit one grid (more than 2^31 workgroups: call with fewer samples).
- * Not here: SimpleAgent playouts (pom_batch_rollout_policy below), reductions over the samples (torch does them on the words),
- *          rollouts of a range of envs.
+ * Not here: SimpleAgent playouts (pom_batch_rollout_policy below), reductions over the samples (torch does them on the words).
+ *          Playouts of SOME envs, or several per env with different first moves: pom_batch_rollout_jobs below.
  */
 enum { POM_ROLLOUT_MAX_TICKS = 1024, POM_ROLLOUT_MAX_SAMPLES = 256, POM_ROLLOUT_SPEC_SIZE = 48 };
 enum { /* the result word */
+    POM_RO_NONE = 0,           /* pom_batch_rollout_jobs: an entry of the list without a job (a played job's length is >= 1, or its DONE bit set) */
     POM_RO_ALIVE = 0xF,        /* bit a: agent a alive in the last state played */
     POM_RO_DONE = 0x10,
     POM_RO_DRAW = 0x20,
@@ -525,6 +526,48 @@ typedef struct PomRolloutPolicySpec {
     int32_t reserved_;         /* must be 0 */
 } PomRolloutPolicySpec;
 int pom_batch_rollout_policy(PomBatch* h, const PomRolloutPolicySpec* spec);
+
+/*
+ * ROLLOUT OF A LIST OF JOBS: pom_batch_rollout_policy's playouts for a device-side list of (source env, moves of tick 1) instead of
+ * one entry per env of the batch — what a search asks for: an agent's six-move table in ONE call (six jobs per env), the leaves
+ * worth evaluating out of a large batch without playing the others and without a second handle.  ONE launch plays
+ * all R x m playouts.
+ * Semantics, by reduction: result[r][j] is, bit for bit, the word pom_batch_rollout_policy would write at result[r][src[j]] for the
+ *          same horizon, samples, dist, seed, masks and flags, given a moves_dev whose row src[j] is moves[j].  That is: S_0 = a
+ *          private copy of env src[j]'s current record and status; M_0 = a private copy of that env's SimpleAgent memory, or fresh
+ *          agents, as pom_batch_rollout_policy defines it; seed_r = pom_splitmix64(seed + r); every draw is keyed by the SOURCE env,
+ *          env_offset + src[j] — the job's number is never the key.  Hence:
+ *          - jobs that share a source play under common random numbers: their words differ only through their first moves, the
+ *            paired comparison a move table wants;
+ *          - two jobs with the same source and the same moves give the same words.  More independent playouts come from `samples`.
+ *          Sources may repeat and come in any order.  An entry with src[j] < 0 or src[j] >= n (indices in [n, n_pad) included) is
+ *          "no job": its R words are written as POM_RO_NONE = 0, which no job produces (a game not finished at S_0 plays at least one
+ *          tick: length >= 1; a finished one has POM_RO_DONE).  jobs == 0: POM_OK, nothing is written.
+ * Nothing else changes, Ordering: exactly as pom_batch_rollout_policy — the handle is settled, then ONE launch on the handle's
+ *          stream; src_dev, moves_dev and the agents' memory are read and result_dev is written in stream order.
+ * POM_E_ARG (with a pom_last_error text naming pom_batch_rollout_jobs; nothing is written): everything pom_batch_rollout_policy
+ *          refuses (struct_size != sizeof(PomRolloutJobsSpec) = POM_ROLLOUT_JOBS_SPEC_SIZE); jobs < 0; with jobs > 0 a null src_dev or
+ *          result_dev, src_dev not 8-byte or result_dev not 16-byte aligned; first_mask != 0 with a null moves_dev; and a list so
+ *          long that samples x groups of 16 jobs (rounded up to 8) does not fit one grid.
+ * Not here: stream keys per job, a host-pointer variant, reductions over the samples, a source's snapshot as S_0.
+ */
+enum { POM_ROLLOUT_JOBS_SPEC_SIZE = 72 };
+typedef struct PomRolloutJobsSpec {
+    int32_t struct_size;       /*  0  = sizeof(PomRolloutJobsSpec) */
+    int32_t horizon;           /*  4  K, 1..POM_ROLLOUT_MAX_TICKS */
+    int32_t samples;           /*  8  R, 1..POM_ROLLOUT_MAX_SAMPLES */
+    int32_t dist;              /* 12  POM_DIST_*: the stream of the agents not in simple_mask */
+    uint64_t seed;             /* 16 */
+    int64_t jobs;              /* 24  m >= 0 */
+    const int64_t* src_dev;    /* 32  required if m > 0: int64 [m], job j plays env src[j]; 8-byte aligned */
+    const int32_t* moves_dev;  /* 40  nullable: int32 [m][4], PER JOB: tick-1 moves of the agents in first_mask */
+    uint32_t* result_dev;      /* 48  required if m > 0: uint32 [R][m], sample-major, 16-byte aligned */
+    int32_t simple_mask;       /* 56 */
+    int32_t first_mask;        /* 60 */
+    int32_t flags;             /* 64  0 or POM_ROLLOUT_FRESH_AGENTS */
+    int32_t reserved_;         /* 68  must be 0 */
+} PomRolloutJobsSpec;
+int pom_batch_rollout_jobs(PomBatch* h, const PomRolloutJobsSpec* spec);
 
 /* A stand-in for a learned policy in measurements and tests of the closed loop (NOT part of the stepper): one launch on `stream`
  * that writes Move[4] of the envs [first, first + count) into moves_dev (int32 [n][4]).  codes_dev != NULL: the POM_OBS_CODES

@@ -496,6 +496,9 @@ public:
     // how does the game end: spec.samples random playouts of every game to a finished game or spec.horizon ticks, the games themselves
     // untouched; one result word (POM_RO_*) per sample and game; all pointers of the spec are DEVICE memory (pom_batch_rollout)
     void Rollout(const PomRolloutSpec& spec) { pom_check(pom_batch_rollout(h_, &spec)); }
+    // the same for a device-side list of jobs: job j plays game spec.src_dev[j] with its own tick-1 moves spec.moves_dev[j], the agents of
+    // spec.simple_mask play SimpleAgent; result word [r][j]; a move table or a selection of leaves in one launch (pom_batch_rollout_jobs)
+    void RolloutJobs(const PomRolloutJobsSpec& spec) { pom_check(pom_batch_rollout_jobs(h_, &spec)); }
     bool IsDone(int64_t e) { return Query(e, 0) != 0; }
     bool IsDraw(int64_t e) { return Query(e, 2) != 0; }
     int GetWinner(int64_t e) { return Query(e, 1); }

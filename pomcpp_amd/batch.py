@@ -94,7 +94,17 @@ class _RolloutPolicySpec(C.Structure):
     ]
 
 
+class _RolloutJobsSpec(C.Structure):
+    """PomRolloutJobsSpec (include/pom_batch.h): the policy rollout's spec for a device-side list of (source env, tick-1 moves)"""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("horizon", C.c_int32), ("samples", C.c_int32), ("dist", C.c_int32), ("seed", C.c_uint64),
+        ("jobs", C.c_int64), ("src_dev", C.c_void_p), ("moves_dev", C.c_void_p), ("result_dev", C.c_void_p),
+        ("simple_mask", C.c_int32), ("first_mask", C.c_int32), ("flags", C.c_int32), ("reserved_", C.c_int32),
+    ]
+
+
 ROLLOUT_FRESH_AGENTS = 1  # POM_ROLLOUT_FRESH_AGENTS
+RO_NONE = 0  # POM_RO_NONE: rollout_jobs' word of an entry without a job
 
 
 def _agent_mask(v, name: str) -> int:
@@ -178,6 +188,8 @@ def load_library() -> C.CDLL:
         lib.pom_batch_rollout.argtypes = [P, C.POINTER(_RolloutSpec)]
     if not os.environ.get("POM_LIB") or hasattr(lib, "pom_batch_rollout_policy"):
         lib.pom_batch_rollout_policy.argtypes = [P, C.POINTER(_RolloutPolicySpec)]
+    if not os.environ.get("POM_LIB") or hasattr(lib, "pom_batch_rollout_jobs"):
+        lib.pom_batch_rollout_jobs.argtypes = [P, C.POINTER(_RolloutJobsSpec)]
     if hasattr(lib, "pom_batch_step_device_range"):
         lib.pom_batch_step_device_range.argtypes = [P, I64, I64, VP, VP, VP, I32, I32, VP, VP]
         lib.pom_bench_policy.argtypes = [VP, VP, I64, I64, C.c_uint32, VP]
@@ -717,6 +729,83 @@ class BatchEnvironment:
         if mine.cuda_stream != theirs.cuda_stream:
             theirs.wait_stream(mine)
         return out
+
+    # ---- rollout of a list of jobs (pom_batch_rollout_jobs) ----------------------------------------------
+    def rollout_jobs(self, src, horizon: int, samples: int, seed: int, dist: int = DIST_RANDOM, moves=None, out=None, *, simple=None,
+                     first=None, fresh_agents: bool = False):
+        """rollout()'s playouts for a list of jobs instead of every env: job j plays env `src[j]` (a device int64 tensor [m]; sources
+        may repeat and come in any order; an entry outside 0..n-1 is "no job" and gets the word RO_NONE = 0) with its OWN tick-1
+        moves `moves[j]` (a device int32 tensor [m, 4]), all by one kernel on the handle's stream; the batch is left exactly as it is
+        (pom_batch_rollout_jobs, include/pom_batch.h).  Returns the result words, int32 [samples, m]: word [r, j] is what
+        rollout(..., simple=, first=) writes at [r, src[j]] given moves whose row src[j] is moves[j] — every draw is keyed by the
+        source env, so jobs of one source play under common random numbers and differ only through their first moves.
+        `simple`, `first`, `fresh_agents`, `out`: as rollout() (the playouts are always pom_batch_rollout_policy's; with none of
+        the three given: random playouts, all four tick-1 moves from `moves` if it is given)."""
+        import torch
+        if not 1 <= int(horizon) <= 1024:
+            raise ValueError("horizon must be 1..1024")
+        if not 1 <= int(samples) <= 256:
+            raise ValueError("samples must be 1..256")
+        if dist not in (DIST_HARMLESS, DIST_RANDOM, DIST_STRESS):
+            raise ValueError("dist must be DIST_HARMLESS, DIST_RANDOM or DIST_STRESS")
+        simple_mask = 0 if simple is None else _agent_mask(simple, "simple")
+        first_mask = (0 if moves is None else 0xF) if first is None else _agent_mask(first, "first")
+        if first_mask and moves is None:
+            raise ValueError("first names agents but moves is None")
+        dev = torch.device("cuda", self.device)
+        if not isinstance(src, torch.Tensor) or src.dtype != torch.int64 or src.dim() != 1 or not src.is_contiguous():
+            raise ValueError("src must be a contiguous int64[m] device tensor")
+        if src.device != dev:
+            raise ValueError(f"src lives on {src.device}, the batch on {dev}")
+        m = int(src.shape[0])
+        shape = (int(samples), m)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int32, device=dev)
+        elif tuple(out.shape) != shape or out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"out must be a contiguous int32 tensor of shape {shape} on {dev}")
+        if moves is not None:
+            if tuple(getattr(moves, "shape", ())) != (m, 4) or "int32" not in str(getattr(moves, "dtype", "")) or not moves.is_contiguous():
+                raise ValueError(f"moves must be a contiguous int32[{m}, 4] device tensor")
+            if moves.device != dev:
+                raise ValueError(f"moves live on {moves.device}, the batch on {dev}")
+        # the kernel runs on the handle's stream, the tensors live on torch's current stream: order the two with events
+        mine, theirs = torch.cuda.ExternalStream(self.stream_handle(), device=dev), torch.cuda.current_stream(dev)
+        if mine.cuda_stream != theirs.cuda_stream:
+            mine.wait_stream(theirs)
+        spec = _RolloutJobsSpec(C.sizeof(_RolloutJobsSpec), int(horizon), int(samples), int(dist), int(seed) & 0xFFFFFFFFFFFFFFFF, m,
+                                src.data_ptr() if m else None, None if moves is None or not m else moves.data_ptr(),
+                                out.data_ptr() if m else None, simple_mask, first_mask if m else 0,
+                                ROLLOUT_FRESH_AGENTS if fresh_agents else 0, 0)
+        _check(self._lib, self._lib.pom_batch_rollout_jobs(self._h, C.byref(spec)))
+        if mine.cuda_stream != theirs.cuda_stream:
+            theirs.wait_stream(mine)
+        return out
+
+    def move_table(self, agent: int, horizon: int, samples: int, seed: int, dist: int = DIST_RANDOM, others=None, *, simple=None,
+                   fresh_agents: bool = False):
+        """`agent`'s six-move table in ONE rollout_jobs call of 6 n jobs: returns int32 [6, samples, n], [c, r, e] = the word of sample
+        r of env e with `agent`'s tick-1 move fixed to c (0..5) — what six rollout(..., moves=, first=[agent]) calls give, stacked.
+        The six playouts of an env and a sample share every draw (common random numbers): they differ through the move alone.
+        `others`: a device int32 tensor [n, 4] — the other three agents' tick-1 moves are fixed to its entries too (`agent`'s own
+        column is ignored); None: only `agent`'s move is fixed.  `simple`, `fresh_agents`, `dist`: as rollout()."""
+        import torch
+        if not 0 <= int(agent) <= 3:
+            raise ValueError("agent must be 0..3")
+        dev = torch.device("cuda", self.device)
+        n = self.n
+        if others is not None:
+            if tuple(getattr(others, "shape", ())) != (n, 4) or "int32" not in str(getattr(others, "dtype", "")):
+                raise ValueError(f"others must be an int32[{n}, 4] device tensor")
+            if others.device != dev:
+                raise ValueError(f"others live on {others.device}, the batch on {dev}")
+            moves = others.unsqueeze(0).repeat(6, 1, 1)
+        else:
+            moves = torch.zeros((6, n, 4), dtype=torch.int32, device=dev)
+        moves[:, :, int(agent)] = torch.arange(6, dtype=torch.int32, device=dev).unsqueeze(1)
+        src = torch.arange(n, dtype=torch.int64, device=dev).repeat(6)  # job c * n + e plays env e
+        res = self.rollout_jobs(src, horizon, samples, seed, dist, moves.view(6 * n, 4), simple=0 if simple is None else simple,
+                                first=0xF if others is not None else [int(agent)], fresh_agents=fresh_agents)
+        return res.view(int(samples), 6, n).permute(1, 0, 2).contiguous()
 
     def moves_tensor(self):
         """The handle's device move buffer as a torch int32 tensor [n, 4] (zero-copy): what policy_simple() fills and

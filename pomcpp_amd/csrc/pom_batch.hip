@@ -1342,6 +1342,7 @@ extern "C" int pom_batch_forecast(PomBatch* h, const PomForecastSpec* s)
 
 static_assert(sizeof(PomRolloutSpec) == POM_ROLLOUT_SPEC_SIZE, "pom_batch.h states the size");
 static_assert(sizeof(PomRolloutPolicySpec) == POM_ROLLOUT_POLICY_SPEC_SIZE, "pom_batch.h states the size");
+static_assert(sizeof(PomRolloutJobsSpec) == POM_ROLLOUT_JOBS_SPEC_SIZE, "pom_batch.h states the size");
 
 static int rollout_bad_arg(const char* who, const char* what)
 {
@@ -1349,23 +1350,27 @@ static int rollout_bad_arg(const char* who, const char* what)
     return POM_E_ARG;
 }
 
-/* What the two entry points share, up to the launch: the checks on the handle and on the fields both specs have (the callers have
- * checked what is their own), the device, the settling, and the grid — tiles of 16 envs, and the same rounded up to a multiple of
- * 8 (the grid is samples * tiles8).  *tiles == 0 on return: nothing to launch (an error, or an empty batch) */
+/* What the entry points share, up to the launch: the checks on the handle and on the fields all specs have (the callers have
+ * checked what is their own), the device, the settling, and the grid — tiles of 16 envs (pom_batch_rollout_jobs: `items` = its jobs,
+ * groups of 16 of them; the others pass -1: the batch's envs), and the same rounded up to a multiple of 8 (the grid is
+ * samples * tiles8).  *tiles == 0 on return: nothing to launch (an error, an empty batch or an empty list: result_dev may then be NULL) */
 static int rollout_begin(PomBatch* h, const char* who, int32_t horizon, int32_t samples, int32_t dist, const int32_t* moves_dev,
-                         const uint32_t* result_dev, int64_t* tiles, int64_t* tiles8)
+                         const uint32_t* result_dev, int64_t* tiles, int64_t* tiles8, int64_t items = -1)
 {
     const char* what = nullptr;
-    const int64_t t = h ? (h->n + 15) / 16 : 0, t8 = (t + 7) / 8 * 8;
+    const int64_t count = items >= 0 ? items : h ? h->n : 0; /* (a count near 2^63 must not wrap) */
+    const int64_t t = count / 16 + (count % 16 != 0), t8 = t > INT_MAX ? t : (t + 7) / 8 * 8;
     *tiles = *tiles8 = 0;
     if (!h) what = "the handle is NULL";
     else if (horizon < 1 || horizon > POM_ROLLOUT_MAX_TICKS) what = "horizon must be 1..1024";
     else if (samples < 1 || samples > POM_ROLLOUT_MAX_SAMPLES) what = "samples must be 1..256";
     else if (dist < POM_DIST_HARMLESS || dist > POM_DIST_STRESS) what = "dist must be POM_DIST_HARMLESS, _RANDOM or _STRESS";
-    else if (!result_dev) what = "result_dev is NULL";
+    else if (!result_dev && items != 0) what = "result_dev is NULL";
     else if ((uintptr_t)result_dev & 15) what = "result_dev must be 16-byte aligned";
     else if ((uintptr_t)moves_dev & 3) what = "moves_dev must be 4-byte aligned";
-    else if (t8 * samples > (int64_t)INT_MAX) what = "samples x tiles of 16 envs exceed one grid: call with fewer samples";
+    else if (t8 > (int64_t)INT_MAX || t8 * samples > (int64_t)INT_MAX)
+        what = items >= 0 ? "samples x groups of 16 jobs exceed one grid: call with fewer samples or jobs"
+                          : "samples x tiles of 16 envs exceed one grid: call with fewer samples";
     if (what) return rollout_bad_arg(who, what);
     HIPCHK(hipSetDevice(h->device));
     /* quiesce, not only join (as pom_batch_forecast): after chained launches a tile left behind is caught up first — the playouts
@@ -1438,6 +1443,49 @@ extern "C" int pom_batch_rollout_policy(PomBatch* h, const PomRolloutPolicySpec*
     const dim3 grid((unsigned)(tiles8 * s->samples));
     if (s->simple_mask) pom_rollout_policy_kernel<true><<<grid, dim3(64), 0, h->stream>>>(p);
     else pom_rollout_policy_kernel<false><<<grid, dim3(64), 0, h->stream>>>(p);
+    HIPCHK(hipGetLastError());
+    return POM_OK;
+}
+
+extern "C" int pom_batch_rollout_jobs(PomBatch* h, const PomRolloutJobsSpec* s)
+{
+    static const char who[] = "pom_batch_rollout_jobs";
+    const char* what = nullptr;
+    if (!s) what = "the spec is NULL";
+    else if (s->struct_size != (int32_t)sizeof(PomRolloutJobsSpec)) what = "struct_size is not sizeof(PomRolloutJobsSpec)";
+    else if (s->simple_mask < 0 || s->simple_mask > 15) what = "simple_mask must be 0..15";
+    else if (s->first_mask < 0 || s->first_mask > 15) what = "first_mask must be 0..15";
+    else if (s->flags & ~(int32_t)POM_ROLLOUT_FRESH_AGENTS) what = "flags must be 0 or POM_ROLLOUT_FRESH_AGENTS";
+    else if (s->reserved_ != 0) what = "reserved_ must be 0";
+    else if (s->jobs < 0) what = "jobs must be >= 0";
+    else if (s->first_mask != 0 && !s->moves_dev) what = "first_mask names agents but moves_dev is NULL";
+    else if (s->jobs > 0 && !s->src_dev) what = "src_dev is NULL";
+    else if ((uintptr_t)s->src_dev & 7) what = "src_dev must be 8-byte aligned";
+    if (what) return rollout_bad_arg(who, what);
+    int64_t groups, groups8;
+    const int rc = rollout_begin(h, who, s->horizon, s->samples, s->dist, s->moves_dev, s->result_dev, &groups, &groups8, s->jobs);
+    if (rc || groups == 0) return rc; /* an empty list: the handle is settled, nothing is launched */
+    RolloutJobsParams p;
+    p.state = h->state;
+    p.moves = s->first_mask ? s->moves_dev : nullptr; /* not read when no agent's first move is fixed */
+    p.agent_mem = (s->flags & POM_ROLLOUT_FRESH_AGENTS) ? nullptr : h->agent_mem;
+    p.result = s->result_dev;
+    p.n = h->n;
+    p.n_pad = h->n_pad;
+    p.env_offset = h->env_offset;
+    p.seed = s->seed;
+    p.horizon = s->horizon;
+    p.dist = s->dist;
+    p.max_steps = h->max_steps;
+    p.simple_mask = s->simple_mask;
+    p.first_mask = s->first_mask;
+    p.tiles = (uint32_t)groups;
+    p.tiles8 = (uint32_t)groups8;
+    p.src = s->src_dev;
+    p.jobs = s->jobs;
+    const dim3 grid((unsigned)(groups8 * s->samples));
+    if (s->simple_mask) pom_rollout_policy_kernel<true, true><<<grid, dim3(64), 0, h->stream>>>(p);
+    else pom_rollout_policy_kernel<false, true><<<grid, dim3(64), 0, h->stream>>>(p);
     HIPCHK(hipGetLastError());
     return POM_OK;
 }

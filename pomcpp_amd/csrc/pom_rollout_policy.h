@@ -23,6 +23,25 @@
  * at 4 wavefronts per SIMD).  8,704 B per wavefront: the 16 wavefronts of a CU fit.  128 VGPRs, no scratch.
  *
  * Grid: as pom_rollout_kernel — workgroup b = r * tiles8 + slot, all samples of a tile on one XCD; slots >= tiles exit.
+ *
+ * JOBS = true (pom_batch_rollout_jobs, PomRolloutJobsSpec): the same playouts for a device-side list of jobs instead of the batch's
+ * envs in order.  One wavefront per (group of 16 consecutive jobs, sample); job 16 g + ec belongs to quad ec.  Only the front and the
+ * indices differ:
+ *   the load   the LDS tile is put together from 16 different columns of the state buffer: column src & 15 of tile src >> 4 becomes
+ *              column ec.  Lane l moves the items of column l & 15 — board bytes k = (l >> 4) + 4 t, t = 0 .. 30, and dwords
+ *              31 + (l >> 4) + 4 t, t = 0 .. 12 — so a lane has ONE source address and all its loads are immediates behind it, and
+ *              every lane issues all its loads, for all 16 columns at once, before anything waits (pom_copy_gather_kernel moves its
+ *              columns one after another and waits for each).  The bytes go through registers (an LDS-DMA of one byte per lane is
+ *              not something this project has measured), and so do the dwords: a lane without a job stores zeros with the same
+ *              instructions.  Where the 16 sources are the 16 envs of one tile in order (wave-uniform: a ballot) the tile is loaded
+ *              as the other kernels load it, load_tile16_x4 — every group of a move table (BatchEnvironment.move_table) whose batch is
+ *              a multiple of 16 envs is of that kind.
+ *   no job     an entry with src outside [0, n) and the slots past the list's end: a blank record (zeros), its lanes done from the
+ *              start; they still enter pom_policy_wave with actor = false.  The owner lane writes the word 0 for an entry of the list.
+ *   indices    the agents' memory and the draws' key are the SOURCE env's (env_offset + src: jobs of one source play under common
+ *              random numbers), the moves of tick 1 and the result word the job's.
+ * The two instances without JOBS are, instruction for instruction, what they were before the parameter existed
+ * (profiles/rollout_jobs_kernel_resources.txt).
  */
 #ifndef POM_ROLLOUT_POLICY_H_
 #define POM_ROLLOUT_POLICY_H_
@@ -42,33 +61,104 @@ struct RolloutPolicyParams {
     uint32_t tiles, tiles8;    /* tiles of 16 envs; the same rounded up to a multiple of 8: the grid is samples * tiles8 */
 };
 
+/* JOBS: `tiles` / `tiles8` count groups of 16 jobs, `moves` is int32[jobs][4] and `result` uint32 [samples][jobs] */
+struct RolloutJobsParams : RolloutPolicyParams {
+    const int64_t* src;        /* device int64[jobs]: job j plays env src[j]; outside [0, n): no job */
+    int64_t jobs;
+};
+
 enum { RP_ROWS = POM_REC_DWORDS + 44 > LDS_ROWS ? POM_REC_DWORDS + 44 : LDS_ROWS, RP_PARK_ROWS = 3 * 4 };
 
-template <bool POLICY>
-__global__ __launch_bounds__(64, 4) void pom_rollout_policy_kernel(RolloutPolicyParams p)
+/* The front of the JOBS kernel: column `col` = lane & 15 of the LDS tile becomes a copy of env s's column of the state buffer, or a
+ * blank record if `ok` is false.  All of a lane's loads are issued before the first of them is waited for. */
+__device__ __forceinline__ void pom_gather_tile16(const uint32_t* state, int64_t s, bool ok, uint32_t* tile, int lane)
+{
+    constexpr int NB = POM_COL_BOARD_ITEMS / 4, ND = (POM_REC_DWORDS - POM_REC_TIMESTEP + 3) / 4; /* 31 byte loads, 13 dword loads */
+    static_assert(POM_COL_BOARD_ITEMS % 4 == 0 && POM_TILE_ENVS == 16, "64 lanes take 4 items of each of the 16 columns at a time");
+    const int sub = lane >> 4; /* which of the four items of a round */
+    const uint32_t* const src_tile = state + (ok ? s >> 4 : 0) * POM_TILE_DWORDS;
+    const int src_col = ok ? (int)(s & 15) : 0;
+    const uint8_t* const gb = reinterpret_cast<const uint8_t*>(src_tile) + sub * 16 + src_col; /* byte k * 16 + src_col, k = sub + 4 t */
+    const uint32_t* const gd = src_tile + (POM_REC_TIMESTEP + sub) * 16 + src_col;             /* dword (31 + sub + 4 t) * 16 + src_col */
+    const bool last = sub < (POM_REC_DWORDS - POM_REC_TIMESTEP) - 4 * (ND - 1); /* the last round of dwords is short: row 79 only */
+    uint32_t b[NB], d[ND];
+#pragma unroll
+    for (int t = 0; t < NB; t++) b[t] = 0;
+#pragma unroll
+    for (int t = 0; t < ND; t++) d[t] = 0;
+    if (ok) {
+#pragma unroll
+        for (int t = 0; t < ND - 1; t++) d[t] = gd[t * 64];
+        if (last) d[ND - 1] = gd[(ND - 1) * 64];
+#pragma unroll
+        for (int t = 0; t < NB; t++) b[t] = gb[t * 64];
+    }
+    uint8_t* const lb = reinterpret_cast<uint8_t*>(tile) + lane; /* byte k * 16 + col, k = sub + 4 t */
+    uint32_t* const ld = tile + POM_REC_TIMESTEP * 16 + lane;     /* dword (31 + sub + 4 t) * 16 + col */
+#pragma unroll
+    for (int t = 0; t < ND - 1; t++) ld[t * 64] = d[t];
+    if (last) ld[(ND - 1) * 64] = d[ND - 1];
+#pragma unroll
+    for (int t = 0; t < NB; t++) lb[t * 64] = (uint8_t)b[t];
+}
+
+template <bool JOBS>
+struct RolloutParamsOf { typedef RolloutPolicyParams type; };
+template <>
+struct RolloutParamsOf<true> { typedef RolloutJobsParams type; };
+
+template <bool POLICY, bool JOBS = false>
+__global__ __launch_bounds__(64, 4) void pom_rollout_policy_kernel(typename RolloutParamsOf<JOBS>::type p)
 {
     /* POLICY: behind the tile three dwords per lane that are parked through the tick: the agent's memory and its move of tick 1 */
     __shared__ __attribute__((aligned(16))) uint32_t tile[(POLICY ? RP_ROWS + RP_PARK_ROWS : LDS_ROWS) * 16];
     const int lane = threadIdx.x;
     const uint32_t sample = blockIdx.x / p.tiles8, slot = blockIdx.x - sample * p.tiles8;
     if (slot >= p.tiles) return; /* a workgroup of the padding */
-    const int64_t tile_id = pom_xcd_tile_order(slot, p.tiles);
-    load_tile16_x4(p.state + tile_id * POM_TILE_DWORDS, tile, lane);
+    const int64_t tile_id = pom_xcd_tile_order(slot, p.tiles); /* JOBS: the group of 16 jobs */
     /* lane -> (env lane / 4, agent lane % 4) */
     const int ec = lane >> 2, member = lane & 3;
-    const int64_t e = tile_id * 16 + ec;
-    const bool valid = e < p.n;
+    int64_t e;        /* the env this lane plays: its record, its agents' memory, the key of its draws (JOBS: 0 where there is no job) */
+    int64_t slot_out; /* where its moves of tick 1 and its result word are: the env, or the job */
+    bool valid;       /* there is a game to play */
+    uint32_t env_key = 0; /* JOBS: the env's number in the whole job, what its draws are keyed by (per lane; else key0 + ec below) */
+    if constexpr (JOBS) {
+        /* the list's entries of this group, twice: the one this lane's quad plays, and the one whose column this lane helps to move */
+        const int64_t j0 = tile_id * 16, jc = j0 + (lane & 15);
+        slot_out = j0 + ec;
+        const int64_t s = slot_out < p.jobs ? p.src[slot_out] : -1, sc = jc < p.jobs ? p.src[jc] : -1;
+        valid = s >= 0 && s < p.n;
+        e = valid ? s : 0;
+        const bool okc = sc >= 0 && sc < p.n;
+        /* wave-uniform: the 16 sources are the 16 envs of one tile, in order */
+        const int64_t t0 = __builtin_amdgcn_readfirstlane((int)((okc ? sc : 0) >> 4));
+        if (__ballot(okc && sc == t0 * 16 + (lane & 15)) == ~0ull) load_tile16_x4(p.state + t0 * POM_TILE_DWORDS, tile, lane);
+        else pom_gather_tile16(p.state, sc, okc, tile, lane);
+        env_key = (uint32_t)(p.env_offset + e);
+    } else {
+        load_tile16_x4(p.state + tile_id * POM_TILE_DWORDS, tile, lane);
+        e = tile_id * 16 + ec;
+        slot_out = e;
+        valid = e < p.n;
+    }
     const uint32_t key0 = (uint32_t)(p.env_offset + tile_id * 16); /* + ec: the env's number in the whole job, what its draws are keyed by */
     const uint64_t seed_r = pom_splitmix64(p.seed + sample); /* uniform: scalar code */
     /* neither tick 1's moves nor the agents' memory depend on the record: fetch them while it is on its way */
     int first = POM_MOVE_IDLE;
-    if (((p.first_mask >> member) & 1) && valid) first = p.moves[e * 4 + member]; /* (dead agents' entries included) */
+    if (((p.first_mask >> member) & 1) && valid) first = p.moves[slot_out * 4 + member]; /* (dead agents' entries included) */
     if (POLICY) {
         /* this lane's agent's memory: this sample's own copy, never stored to global memory (the buffers hold n_pad columns) */
         uint32_t m0 = 0, m1 = 0;
         if (p.agent_mem) {
-            m0 = p.agent_mem[tile_id * 64 + lane];
-            m1 = p.agent_mem[4 * p.n_pad + tile_id * 64 + lane];
+            if constexpr (JOBS) {
+                if (valid) {
+                    m0 = p.agent_mem[e * 4 + member];
+                    m1 = p.agent_mem[4 * p.n_pad + e * 4 + member];
+                }
+            } else {
+                m0 = p.agent_mem[tile_id * 64 + lane];
+                m1 = p.agent_mem[4 * p.n_pad + tile_id * 64 + lane];
+            }
         }
         uint32_t* park = tile + RP_ROWS * 16 + lane; /* (rows no DMA touches) */
         park[0] = m0;
@@ -102,7 +192,7 @@ __global__ __launch_bounds__(64, 4) void pom_rollout_policy_kernel(RolloutPolicy
         const bool simple = POLICY && ((p.simple_mask >> member_p) & 1);        /* this lane's agent plays SimpleAgent */
         const bool fixed = tk == 1 && ((p.first_mask >> member_p) & 1);         /* ... and this tick's move is the caller's */
         /* agent m's 16 bits of the tick's draw: SimpleAgent's one random choice, or the stream's move */
-        const uint32_t r = pom_rng_draw_half(seed_r, key0 + (uint32_t)ec_p, (uint32_t)(tk - 1), member_p >> 1);
+        const uint32_t r = pom_rng_draw_half(seed_r, JOBS ? env_key : key0 + (uint32_t)ec_p, (uint32_t)(tk - 1), member_p >> 1);
         const uint32_t r16 = (r >> (16 * (member_p & 1))) & 0xFFFFu;
         int mine = first;
         if (POLICY) {
@@ -161,8 +251,11 @@ __global__ __launch_bounds__(64, 4) void pom_rollout_policy_kernel(RolloutPolicy
         const uint32_t word = alive | ((status & (POM_ST_DONE | POM_ST_DRAW)) << 4) | ((status & POM_ST_TIMEOUT) << 1) |
                               ((run & 0x100u) ? (uint32_t)POM_RO_UB : 0u) | (((status >> POM_ST_WINNER_SHIFT) & 7u) << POM_RO_WINNER_SHIFT) |
                               ((run >> 16) << POM_RO_LENGTH_SHIFT);
-        p.result[(int64_t)sample * p.n + e] = word;
+        if constexpr (JOBS) p.result[(int64_t)sample * p.jobs + slot_out] = word;
+        else p.result[(int64_t)sample * p.n + e] = word;
     }
+    if constexpr (JOBS) /* an entry of the list without a job: POM_RO_NONE */
+        if (!valid && member == 0 && slot_out < p.jobs) p.result[(int64_t)sample * p.jobs + slot_out] = (uint32_t)POM_RO_NONE;
 }
 
 #endif /* POM_ROLLOUT_POLICY_H_ */
