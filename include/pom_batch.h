@@ -569,6 +569,66 @@ typedef struct PomRolloutJobsSpec {
 } PomRolloutJobsSpec;
 int pom_batch_rollout_jobs(PomBatch* h, const PomRolloutJobsSpec* spec);
 
+/*
+ * EXPAND: create the nodes of a search — for a device-side list, env first + j becomes the SUCCESSOR of env src[j] under moves[j]:
+ * the copy of pom_batch_copy_envs (flags 0) and one tick, in ONE launch, for any range of destinations (not only whole 16-env
+ * tiles), with one result word per child in pom_batch_rollout's format — which children are terminal is known without reading
+ * pom_batch_status back — and, optionally, the observation of the new nodes for a value network.  With src[j] = first + j the same
+ * call is a MASKED STEP: tick these envs only, with these moves.
+ * Semantics: job j has destination d = first + j and source s = src[j].
+ *   No job: env d is left bit for bit as it was and result[j] = POM_RO_NONE = 0 when s < 0; when s >= n (indices in [n, n_pad) and
+ *          huge values included); and when s lies inside [first, first + count) and s != d.  The last is the only aliasing a one-pass
+ *          kernel cannot serve — a slot that is being filled cannot be somebody's parent in the same call — and a search never has
+ *          it: parents are not among the slots being filled.  Sources outside the range may repeat and come in any order.
+ *   Otherwise env d first becomes what pom_batch_copy_envs with flags 0 makes of it: the source's current record with status and
+ *          ubflags, its SimpleAgent memory (if allocated), its episode counter and, with POM_RESET_AT_END, its terminal record and
+ *          last results; for s == d nothing is copied.  Then ONE tick is played on d with moves[j] (all four entries, dead agents'
+ *          included: step_utility.cpp:138-170), as the handle's mode says: POM_MODE_RAW bare bboard::Step, no timeStep++;
+ *          POM_MODE_ENV a finished source gives an unticked copy (environment.cpp:125-128), otherwise Step, timeStep++ and done /
+ *          winner / draw / max_steps as in every tick (environment.cpp:148-168, :71).  The tick's POM_UB_* flags are ORed into the
+ *          child's ubflags as in any tick.
+ *   No restart is ever played and no fresh board drawn, whatever auto_reset and fresh_boards say: a child that finishes STAYS
+ *          finished (with POM_RESET_AT_END it is not marked "restarted" and its terminal record stays its source's) — a search wants
+ *          its terminal nodes.  What later ordinary steps do with such an env: with POM_RESET_AT_START the next tick restarts it
+ *          (snapshot or next generated board) and steps that; with auto_reset 0 and with POM_RESET_AT_END it is skipped, tick after
+ *          tick, until it is overwritten (pom_batch_copy_envs, pom_batch_upload, another expansion).
+ * result[j] (nullable; uint32 [count]): the POM_RO_* word of the child as it now stands — POM_RO_ALIVE bits, POM_RO_DONE / _DRAW /
+ *          _TIMEOUT, winner + 1 — POM_RO_UB if THIS tick raised a flag, and the length: 1 if a tick was played, 0 for the unticked copy
+ *          of a finished source (which has POM_RO_DONE, so no job's word is 0).  With POM_MODE_RAW the status bits are whatever the
+ *          record carries (0).
+ * Counters: expansion ticks are steps of the batch.  POM_CNT_STEPS grows by the ticks played, POM_CNT_EPISODES by the children that
+ *          finish in this tick, POM_CNT_UB_TICKS as usual; POM_CNT_RESETS, the handle's tick, the snapshots and the chain statistics
+ *          do not change.
+ * Observation: with planes_dev the launch also writes the observation of every env < n of the destination tiles first / 16 ..
+ *          (first + count - 1) / 16 — arguments, layouts and alignment exactly as pom_batch_step_device_range, the arrays sized for
+ *          the WHOLE batch.  Envs of a partly covered tile that are not destinations get the observation of their unchanged state.
+ *          Fogged views are not part of this.
+ * Ordering: as pom_batch_copy_envs_device — the handle is settled first, then ONE launch on the handle's stream; src_dev and
+ *          moves_dev are read in stream order, the call does not block.
+ * POM_E_ARG (with a pom_last_error text naming pom_batch_expand; nothing is written): a null handle or spec, struct_size !=
+ *          sizeof(PomExpandSpec) (POM_EXPAND_SPEC_SIZE), nonzero flags or reserved_, count < 0, a range outside [0, n); with count > 0
+ *          a null src_dev or moves_dev, src_dev not 8-byte, moves_dev or result_dev not 4-byte aligned; with planes_dev whatever
+ *          pom_batch_observe refuses; a launch shape other than the quad shape.  count == 0: POM_OK, nothing is written.
+ * Not here: a host-pointer list, fogged views, more than one tick per job, sources read from snapshots, a stream argument.
+ */
+enum { POM_EXPAND_SPEC_SIZE = 88 }; /* 2 x int32, 2 x int64, 4 pointers, 2 x int32, 2 pointers, int64: no implicit padding on an LP64 target */
+typedef struct PomExpandSpec {
+    int32_t struct_size;       /*  0  = sizeof(PomExpandSpec) */
+    int32_t flags;             /*  4  must be 0 */
+    int64_t first;             /*  8  destinations: env first + j, j in [0, count); any range inside [0, n) */
+    int64_t count;             /* 16 */
+    const int64_t* src_dev;    /* 24  required if count > 0: int64 [count], 8-byte aligned */
+    const int32_t* moves_dev;  /* 32  required if count > 0: int32 [count][4], a row per JOB, dead agents' entries included */
+    uint32_t* result_dev;      /* 40  nullable: uint32 [count], 4-byte aligned */
+    void* planes_dev;          /* 48  nullable: the observation of the tiles touched, as pom_batch_step_device_range */
+    int32_t dtype;             /* 56  POM_OBS_* */
+    int32_t per_agent;         /* 60 */
+    int32_t* agent_attrs_dev;  /* 64  nullable */
+    int32_t* env_attrs_dev;    /* 72  nullable */
+    int64_t reserved_;         /* 80  must be 0 */
+} PomExpandSpec;
+int pom_batch_expand(PomBatch* h, const PomExpandSpec* spec);
+
 /* A stand-in for a learned policy in measurements and tests of the closed loop (NOT part of the stepper): one launch on `stream`
  * that writes Move[4] of the envs [first, first + count) into moves_dev (int32 [n][4]).  codes_dev != NULL: the POM_OBS_CODES
  * observation of the batch (uint8 [n][5][11][11]) — every byte of the range's observations is read and the moves depend on them;

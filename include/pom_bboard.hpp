@@ -499,6 +499,10 @@ public:
     // the same for a device-side list of jobs: job j plays game spec.src_dev[j] with its own tick-1 moves spec.moves_dev[j], the agents of
     // spec.simple_mask play SimpleAgent; result word [r][j]; a move table or a selection of leaves in one launch (pom_batch_rollout_jobs)
     void RolloutJobs(const PomRolloutJobsSpec& spec) { pom_check(pom_batch_rollout_jobs(h_, &spec)); }
+    // the nodes of a search: game spec.first + j becomes the successor of game spec.src_dev[j] under spec.moves_dev[j] — copy and one tick
+    // in one launch, no restart played; a result word (POM_RO_*) per child, optionally the observation of the new nodes; src_dev[j] =
+    // first + j is a masked step; all pointers of the spec are DEVICE memory (pom_batch_expand)
+    void Expand(const PomExpandSpec& spec) { pom_check(pom_batch_expand(h_, &spec)); }
     bool IsDone(int64_t e) { return Query(e, 0) != 0; }
     bool IsDraw(int64_t e) { return Query(e, 2) != 0; }
     int GetWinner(int64_t e) { return Query(e, 1); }

@@ -103,6 +103,15 @@ class _RolloutJobsSpec(C.Structure):
     ]
 
 
+class _ExpandSpec(C.Structure):
+    """PomExpandSpec (include/pom_batch.h): env first + j becomes the successor of env src[j] under moves[j]"""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("flags", C.c_int32), ("first", C.c_int64), ("count", C.c_int64), ("src_dev", C.c_void_p),
+        ("moves_dev", C.c_void_p), ("result_dev", C.c_void_p), ("planes_dev", C.c_void_p), ("dtype", C.c_int32), ("per_agent", C.c_int32),
+        ("agent_attrs_dev", C.c_void_p), ("env_attrs_dev", C.c_void_p), ("reserved_", C.c_int64),
+    ]
+
+
 ROLLOUT_FRESH_AGENTS = 1  # POM_ROLLOUT_FRESH_AGENTS
 RO_NONE = 0  # POM_RO_NONE: rollout_jobs' word of an entry without a job
 
@@ -190,6 +199,8 @@ def load_library() -> C.CDLL:
         lib.pom_batch_rollout_policy.argtypes = [P, C.POINTER(_RolloutPolicySpec)]
     if not os.environ.get("POM_LIB") or hasattr(lib, "pom_batch_rollout_jobs"):
         lib.pom_batch_rollout_jobs.argtypes = [P, C.POINTER(_RolloutJobsSpec)]
+    if not os.environ.get("POM_LIB") or hasattr(lib, "pom_batch_expand"):
+        lib.pom_batch_expand.argtypes = [P, C.POINTER(_ExpandSpec)]
     if hasattr(lib, "pom_batch_step_device_range"):
         lib.pom_batch_step_device_range.argtypes = [P, I64, I64, VP, VP, VP, I32, I32, VP, VP]
         lib.pom_bench_policy.argtypes = [VP, VP, I64, I64, C.c_uint32, VP]
@@ -780,6 +791,80 @@ class BatchEnvironment:
         if mine.cuda_stream != theirs.cuda_stream:
             theirs.wait_stream(mine)
         return out
+
+    # ---- expand: listed games copied into slots and ticked once (pom_batch_expand) ------------------------
+    def expand(self, src, moves, first: int = 0, *, out=None, codes=None, planes=None, per_agent: Optional[bool] = None,
+               attrs: bool = True):
+        """Create the nodes of a search in one launch: env `first + j` becomes the successor of env `src[j]` under `moves[j]` — the
+        copy of copy_envs() and one tick as the handle's mode says, no restart ever played (pom_batch_expand, include/pom_batch.h).
+        `src`: int64 [count], `moves`: int32 [count, 4], a row per JOB (dead agents' entries included); torch tensors on the handle's
+        device, or numpy arrays, which are copied there.  An entry < 0, >= n, or inside [first, first + count) without being its own
+        slot is "no job": its env is left alone and its word is RO_NONE = 0.  src[j] = first + j is a masked step of env first + j.
+        Returns the result words, int32 [count] on the handle's device holding the header's uint32 words of the children as they now
+        stand (decode_rollout names the fields; length 1 = ticked, 0 = the unticked copy of a finished game).  `out`: such a tensor of
+        an earlier call.  `codes` (uint8 [n, 5, 11, 11]) or `planes` ([n, 16, 11, 11] or, with per_agent, [n, 4, 16, 11, 11] of uint8 /
+        float16 / float32): tensors sized for the WHOLE batch into which the same launch writes the observation of the tiles of 16 envs
+        the range touches; the call then returns (words, agent_attrs, env_attrs), the latter two int32 [n, 4, 8] and [n, 4] written
+        for the same envs (None, None with attrs=False)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+
+        def device_tensor(a, tdt, what):
+            if isinstance(a, np.ndarray):
+                if not np.issubdtype(a.dtype, np.integer):
+                    raise ValueError(f"{what} must be an integer array")
+                a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64 if tdt == torch.int64 else np.int32)).to(dev)
+            if not isinstance(a, torch.Tensor) or a.dtype != tdt or not a.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous {tdt} device tensor or a numpy integer array")
+            if a.device != dev:
+                raise ValueError(f"{what} lives on {a.device}, the batch on {dev}")
+            return a
+
+        src = device_tensor(src, torch.int64, "src")
+        if src.dim() != 1:
+            raise ValueError(f"src must be int64[count], got shape {tuple(src.shape)}")
+        m = int(src.shape[0])
+        moves = device_tensor(moves, torch.int32, "moves")
+        if tuple(moves.shape) != (m, 4):
+            raise ValueError(f"moves must be int32[{m}, 4], a row per job, got shape {tuple(moves.shape)}")
+        first = int(first)
+        if first < 0 or first + m > self.n:
+            raise ValueError(f"the range [{first}, {first + m}) lies outside the batch of {self.n} envs")
+        if out is None:
+            out = torch.empty((m,), dtype=torch.int32, device=dev)
+        elif tuple(out.shape) != (m,) or out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"out must be a contiguous int32 tensor of shape ({m},) on {dev}")
+        obs, code, per_agent = None, 0, bool(per_agent)
+        if codes is not None and planes is not None:
+            raise ValueError("codes and planes are two forms of one observation: pass one")
+        if codes is not None:
+            if per_agent:
+                raise ValueError("the codes layout has no per-agent view")
+            obs, code, shape = codes, 3, (self.n, 5, 11, 11)
+        elif planes is not None:
+            code = {torch.uint8: 0, torch.float16: 1, torch.float32: 2}.get(getattr(planes, "dtype", None))
+            if code is None:
+                raise ValueError("planes must be uint8, float16 or float32")
+            obs, shape = planes, (self.n, 4, 16, 11, 11) if per_agent else (self.n, 16, 11, 11)
+        a_attrs = e_attrs = None
+        if obs is not None:
+            if not isinstance(obs, torch.Tensor) or tuple(obs.shape) != shape or not obs.is_contiguous() or obs.device != dev or \
+                    (codes is not None and obs.dtype != torch.uint8):
+                raise ValueError(f"the observation must be a contiguous tensor of shape {shape} on {dev}")
+            if attrs:
+                a_attrs = torch.empty((self.n, 4, 8), dtype=torch.int32, device=dev)
+                e_attrs = torch.empty((self.n, 4), dtype=torch.int32, device=dev)
+        # the kernel runs on the handle's stream, the tensors live on torch's current stream: order the two with events
+        mine, theirs = torch.cuda.ExternalStream(self.stream_handle(), device=dev), torch.cuda.current_stream(dev)
+        if mine.cuda_stream != theirs.cuda_stream:
+            mine.wait_stream(theirs)
+        spec = _ExpandSpec(C.sizeof(_ExpandSpec), 0, first, m, src.data_ptr() if m else None, moves.data_ptr() if m else None,
+                           out.data_ptr() if m else None, None if obs is None else obs.data_ptr(), code, int(per_agent),
+                           None if a_attrs is None else a_attrs.data_ptr(), None if e_attrs is None else e_attrs.data_ptr(), 0)
+        _check(self._lib, self._lib.pom_batch_expand(self._h, C.byref(spec)))
+        if mine.cuda_stream != theirs.cuda_stream:
+            theirs.wait_stream(mine)
+        return out if obs is None else (out, a_attrs, e_attrs)
 
     def move_table(self, agent: int, horizon: int, samples: int, seed: int, dist: int = DIST_RANDOM, others=None, *, simple=None,
                    fresh_agents: bool = False):

@@ -1489,3 +1489,63 @@ extern "C" int pom_batch_rollout_jobs(PomBatch* h, const PomRolloutJobsSpec* s)
     HIPCHK(hipGetLastError());
     return POM_OK;
 }
+
+/* ---- the expansion (pom_batch.h PomExpandSpec): listed games copied into slots and ticked once, one launch.  Its kernel comes after
+ * the rollouts', so that every kernel before it is emitted as it was without it ---- */
+#include "pom_expand.h"
+
+static_assert(sizeof(PomExpandSpec) == POM_EXPAND_SPEC_SIZE, "pom_batch.h states the size");
+
+extern "C" int pom_batch_expand(PomBatch* h, const PomExpandSpec* s)
+{
+    static const char who[] = "pom_batch_expand";
+    const char* what = nullptr;
+    /* the spec's own fields first, then the handle and what depends on it */
+    if (!s) what = "the spec is NULL";
+    else if (s->struct_size != (int32_t)sizeof(PomExpandSpec)) what = "struct_size is not sizeof(PomExpandSpec)";
+    else if (s->flags != 0) what = "flags must be 0";
+    else if (s->reserved_ != 0) what = "reserved_ must be 0";
+    else if (s->count < 0) what = "count must be >= 0";
+    else if (s->count > 0 && !s->src_dev) what = "src_dev is NULL";
+    else if (s->count > 0 && !s->moves_dev) what = "moves_dev is NULL";
+    else if (s->count > 0 && ((uintptr_t)s->src_dev & 7)) what = "src_dev must be 8-byte aligned";
+    else if (s->count > 0 && ((uintptr_t)s->moves_dev & 3)) what = "moves_dev must be 4-byte aligned";
+    else if (s->count > 0 && ((uintptr_t)s->result_dev & 3)) what = "result_dev must be 4-byte aligned";
+    else if (s->planes_dev && (s->dtype < POM_OBS_U8 || s->dtype > POM_OBS_CODES)) what = "dtype is no POM_OBS_*";
+    else if (!h) what = "the handle is NULL";
+    else if (s->first < 0 || s->first > h->n || s->count > h->n - s->first) what = "the range [first, first + count) lies outside the batch";
+    else if (!h->quad) what = "needs the quad launch shape (envs_per_wave 16, lanes_per_env 4)";
+    if (what) return rollout_bad_arg(who, what);
+    if (s->planes_dev)
+        if (int ar = observe_args(who, s->planes_dev, s->dtype, s->per_agent, s->agent_attrs_dev, s->env_attrs_dev)) return ar;
+    if (s->count == 0) return POM_OK;
+    HIPCHK(hipSetDevice(h->device));
+    /* quiesce, not only join (as pom_batch_copy_envs_device): after chained launches a tile left behind is caught up first */
+    if (int jr = quiesce(h)) return jr;
+    ExpandParams p;
+    p.state = h->state;
+    p.src = s->src_dev;
+    p.moves = s->moves_dev;
+    p.result = s->result_dev;
+    p.first = s->first;
+    p.count = s->count;
+    p.n = h->n;
+    p.n_pad = h->n_pad;
+    p.tile0 = s->first / POM_TILE_ENVS;
+    p.agent_mem = h->agent_mem;
+    p.episode = h->episode;
+    p.terminal = h->terminal;
+    p.wave_counters = h->wave_counters;
+    p.mode = h->mode;
+    p.max_steps = h->max_steps;
+    p.obs_planes = s->planes_dev;
+    p.obs_agent_attrs = s->agent_attrs_dev;
+    p.obs_env_attrs = s->env_attrs_dev;
+    p.obs_dtype = s->dtype;
+    p.obs_per_agent = s->per_agent ? 1 : 0;
+    const dim3 grid((unsigned)((s->first + s->count - 1) / POM_TILE_ENVS - p.tile0 + 1));
+    if (s->planes_dev) pom_expand_kernel<true><<<grid, dim3(64), 0, h->stream>>>(p);
+    else pom_expand_kernel<false><<<grid, dim3(64), 0, h->stream>>>(p);
+    HIPCHK(hipGetLastError());
+    return POM_OK;
+}
