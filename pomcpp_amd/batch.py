@@ -14,6 +14,7 @@ creating a batch raises — nothing falls back to the CPU.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import sys
@@ -58,9 +59,13 @@ class _ViewSpec(C.Structure):
     ]
 
 
+def _ptr(t):
+    """what a spec's pointer field takes: None, a tensor's device address, or a raw address"""
+    return None if t is None else t.data_ptr() if hasattr(t, "data_ptr") else int(t)
+
+
 def _view_spec(code: int, radius: int, planes, viewer_attrs=None, env_attrs=None) -> _ViewSpec:
-    ptr = lambda t: None if t is None else t.data_ptr() if hasattr(t, "data_ptr") else int(t)  # noqa: E731
-    return _ViewSpec(C.sizeof(_ViewSpec), code, int(radius), 0, ptr(planes), ptr(viewer_attrs), ptr(env_attrs))
+    return _ViewSpec(C.sizeof(_ViewSpec), code, int(radius), 0, _ptr(planes), _ptr(viewer_attrs), _ptr(env_attrs))
 
 
 class _ForecastSpec(C.Structure):
@@ -72,9 +77,8 @@ class _ForecastSpec(C.Structure):
 
 
 def _forecast_spec(horizon: int, moves, flame_tick, agent_tick=None, ubflags=None) -> _ForecastSpec:
-    ptr = lambda t: None if t is None else t.data_ptr() if hasattr(t, "data_ptr") else int(t)  # noqa: E731
-    return _ForecastSpec(C.sizeof(_ForecastSpec), int(horizon), (C.c_int32 * 2)(0, 0), ptr(moves), ptr(flame_tick), ptr(agent_tick),
-                         ptr(ubflags))
+    return _ForecastSpec(C.sizeof(_ForecastSpec), int(horizon), (C.c_int32 * 2)(0, 0), _ptr(moves), _ptr(flame_tick), _ptr(agent_tick),
+                         _ptr(ubflags))
 
 
 class _RolloutSpec(C.Structure):
@@ -132,6 +136,24 @@ def _agent_mask(v, name: str) -> int:
     return sum(1 << a for a in set(ids))
 
 
+def _rollout_args(horizon, samples, dist, moves, simple, first, fresh_agents, policy: bool = True):
+    """rollout()'s and rollout_jobs()'s arguments checked: (horizon, samples, dist, simple_mask, first_mask, flags); without `policy`
+    (pom_batch_rollout's playouts) the masks are 0"""
+    if not 1 <= int(horizon) <= 1024:
+        raise ValueError("horizon must be 1..1024")
+    if not 1 <= int(samples) <= 256:
+        raise ValueError("samples must be 1..256")
+    if dist not in (DIST_HARMLESS, DIST_RANDOM, DIST_STRESS):
+        raise ValueError("dist must be DIST_HARMLESS, DIST_RANDOM or DIST_STRESS")
+    simple_mask = first_mask = 0
+    if policy:
+        simple_mask = 0 if simple is None else _agent_mask(simple, "simple")
+        first_mask = (0 if moves is None else 0xF) if first is None else _agent_mask(first, "first")
+        if first_mask and moves is None:
+            raise ValueError("first names agents but moves is None")
+    return int(horizon), int(samples), int(dist), simple_mask, first_mask, ROLLOUT_FRESH_AGENTS if fresh_agents else 0
+
+
 # the result word of a rollout (the header's POM_RO_*)
 RO_ALIVE, RO_DONE, RO_DRAW, RO_TIMEOUT, RO_UB, RO_WINNER_SHIFT, RO_WINNER_MASK, RO_LENGTH_SHIFT = 0xF, 0x10, 0x20, 0x40, 0x80, 8, 0x700, 16
 
@@ -178,76 +200,55 @@ def load_library() -> C.CDLL:
             "pomcpp_amd has no CPU stepper to fall back to.")
     lib = C.CDLL(path)
     P, I32, I64, U64, VP = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_void_p
-    lib.pom_last_error.restype = C.c_char_p
-    lib.pom_device_count.restype = C.c_int
-    lib.pom_batch_create.argtypes = [C.POINTER(P), I64, C.POINTER(_Options)]
-    lib.pom_batch_destroy.argtypes = [P]
-    lib.pom_batch_size.argtypes = [P]
-    lib.pom_batch_size.restype = I64
-    lib.pom_batch_observe.argtypes = [P, VP, I32, I32, VP, VP]
-    if not os.environ.get("POM_LIB") or hasattr(lib, "pom_batch_step_device_observe"):
-        lib.pom_batch_step_device_observe.argtypes = [P, VP, VP, I32, I32, VP, VP]
-    if not os.environ.get("POM_LIB") or hasattr(lib, "pom_batch_observe_view"):
-        lib.pom_batch_observe_view.argtypes = [P, C.POINTER(_ViewSpec)]
-        lib.pom_batch_step_device_observe_view.argtypes = [P, VP, C.POINTER(_ViewSpec)]
-        lib.pom_batch_step_device_range_view.argtypes = [P, I64, I64, VP, VP, C.POINTER(_ViewSpec)]
-    if not os.environ.get("POM_LIB") or hasattr(lib, "pom_batch_forecast"):
-        lib.pom_batch_forecast.argtypes = [P, C.POINTER(_ForecastSpec)]
-    if not os.environ.get("POM_LIB") or hasattr(lib, "pom_batch_rollout"):
-        lib.pom_batch_rollout.argtypes = [P, C.POINTER(_RolloutSpec)]
-    if not os.environ.get("POM_LIB") or hasattr(lib, "pom_batch_rollout_policy"):
-        lib.pom_batch_rollout_policy.argtypes = [P, C.POINTER(_RolloutPolicySpec)]
-    if not os.environ.get("POM_LIB") or hasattr(lib, "pom_batch_rollout_jobs"):
-        lib.pom_batch_rollout_jobs.argtypes = [P, C.POINTER(_RolloutJobsSpec)]
-    if not os.environ.get("POM_LIB") or hasattr(lib, "pom_batch_expand"):
-        lib.pom_batch_expand.argtypes = [P, C.POINTER(_ExpandSpec)]
-    if hasattr(lib, "pom_batch_step_device_range"):
-        lib.pom_batch_step_device_range.argtypes = [P, I64, I64, VP, VP, VP, I32, I32, VP, VP]
-        lib.pom_bench_policy.argtypes = [VP, VP, I64, I64, C.c_uint32, VP]
-    lib.pom_batch_stream.argtypes = [P, C.POINTER(C.c_void_p)]
-    lib.pom_batch_moves_device.argtypes = [P, C.POINTER(C.POINTER(C.c_int32))]
-    lib.pom_batch_generate.argtypes = [P, U64]
-    lib.pom_batch_episodes.argtypes = [P, I64, I64, VP]
-    lib.pom_batch_upload.argtypes = [P, VP, I64, I64]
-    lib.pom_batch_download.argtypes = [P, VP, I64, I64]
-    lib.pom_batch_snapshot.argtypes = [P]
-    if not os.environ.get("POM_LIB") or hasattr(lib, "pom_batch_copy_envs"):
-        lib.pom_batch_copy_envs.argtypes = [P, VP, I64, I64, I32]
-        lib.pom_batch_copy_envs_device.argtypes = [P, VP, I64, I64, I32]
-    lib.pom_batch_step.argtypes = [P, VP]
-    lib.pom_batch_step_device.argtypes = [P, VP]
-    if not os.environ.get("POM_LIB") or hasattr(lib, "pom_batch_step_device_many"):
-        lib.pom_batch_step_device_many.argtypes = [P, VP, I32]
-        lib.pom_batch_chain_stats.argtypes = [P, VP]
-    lib.pom_batch_step_random.argtypes = [P, U64, I32, I32, I32]
-    lib.pom_batch_set_tick.argtypes = [P, I64]
-    lib.pom_batch_policy_simple.argtypes = [P, U64, VP]
-    lib.pom_batch_step_policy.argtypes = [P]
-    lib.pom_batch_step_simple.argtypes = [P, U64, I32]
-    lib.pom_batch_policy_memory.argtypes = [P, I64, I64, VP]
-    lib.pom_batch_status.argtypes = [P, I64, I64, VP, VP, VP, VP, VP, VP]
-    if not os.environ.get("POM_LIB") or hasattr(lib, "pom_batch_last_results"):  # (POM_LIB: older experimental builds lack these)
-        lib.pom_batch_last_results.argtypes = [P, I64, I64, VP, VP, VP, VP, VP]
-        lib.pom_batch_download_terminal.argtypes = [P, VP, I64, I64]
-    lib.pom_batch_counters.argtypes = [P, VP]
-    lib.pom_batch_counters_device.argtypes = [P, VP]
-    lib.pom_batch_reset_counters.argtypes = [P]
-    lib.pom_batch_sync.argtypes = [P]
-    lib.pom_batch_flush.argtypes = [P]
-    if not os.environ.get("POM_LIB") or hasattr(lib, "pom_batch_fork"):
-        lib.pom_batch_fork.argtypes = [P]
-    lib.pom_batch_set_streams.argtypes = [P, I32]
-    lib.pom_batch_profile.argtypes = [P, C.c_int]
-    lib.pom_batch_profile_read.argtypes = [P, C.POINTER(C.c_double), C.POINTER(I64)]
-    lib.pom_batch_launch_shape.argtypes = [P, C.POINTER(I32), C.POINTER(I32), C.POINTER(I32)]
-    if not os.environ.get("POM_LIB") or hasattr(lib, "pom_batch_issue_info"):
-        lib.pom_batch_issue_info.argtypes = [P, C.POINTER(I32), C.POINTER(I32)]
-    lib.pom_batch_device_view.argtypes = [P, C.POINTER(VP), C.POINTER(I64), C.POINTER(I32)]
-    if not os.environ.get("POM_LIB") or hasattr(lib, "pom_chain_litmus"):
-        lib.pom_chain_litmus.argtypes = [I32, I64, I32, I32, VP]
-    lib.pom_step.argtypes = [VP, VP]
-    if not os.environ.get("POM_LIB") or hasattr(lib, "pom_env_step"):
-        lib.pom_env_step.argtypes = [VP, VP, I32, VP, VP, VP, VP]
+    table = (  # (name, argtypes or None: undeclared, restype or None: int)
+        ("pom_last_error", None, C.c_char_p), ("pom_device_count", None, C.c_int),
+        ("pom_batch_create", [C.POINTER(P), I64, C.POINTER(_Options)], None), ("pom_batch_destroy", [P], None),
+        ("pom_batch_size", [P], I64),
+        ("pom_batch_observe", [P, VP, I32, I32, VP, VP], None),
+        ("pom_batch_step_device_observe", [P, VP, VP, I32, I32, VP, VP], None),
+        ("pom_batch_observe_view", [P, C.POINTER(_ViewSpec)], None),
+        ("pom_batch_step_device_observe_view", [P, VP, C.POINTER(_ViewSpec)], None),
+        ("pom_batch_step_device_range_view", [P, I64, I64, VP, VP, C.POINTER(_ViewSpec)], None),
+        ("pom_batch_forecast", [P, C.POINTER(_ForecastSpec)], None),
+        ("pom_batch_rollout", [P, C.POINTER(_RolloutSpec)], None),
+        ("pom_batch_rollout_policy", [P, C.POINTER(_RolloutPolicySpec)], None),
+        ("pom_batch_rollout_jobs", [P, C.POINTER(_RolloutJobsSpec)], None),
+        ("pom_batch_expand", [P, C.POINTER(_ExpandSpec)], None),
+        ("pom_batch_step_device_range", [P, I64, I64, VP, VP, VP, I32, I32, VP, VP], None),
+        ("pom_bench_policy", [VP, VP, I64, I64, C.c_uint32, VP], None),
+        ("pom_batch_stream", [P, C.POINTER(C.c_void_p)], None),
+        ("pom_batch_moves_device", [P, C.POINTER(C.POINTER(C.c_int32))], None),
+        ("pom_batch_generate", [P, U64], None), ("pom_batch_episodes", [P, I64, I64, VP], None),
+        ("pom_batch_upload", [P, VP, I64, I64], None), ("pom_batch_download", [P, VP, I64, I64], None),
+        ("pom_batch_snapshot", [P], None),
+        ("pom_batch_copy_envs", [P, VP, I64, I64, I32], None), ("pom_batch_copy_envs_device", [P, VP, I64, I64, I32], None),
+        ("pom_batch_step", [P, VP], None), ("pom_batch_step_device", [P, VP], None),
+        ("pom_batch_step_device_many", [P, VP, I32], None), ("pom_batch_chain_stats", [P, VP], None),
+        ("pom_batch_step_random", [P, U64, I32, I32, I32], None), ("pom_batch_set_tick", [P, I64], None),
+        ("pom_batch_policy_simple", [P, U64, VP], None), ("pom_batch_step_policy", [P], None),
+        ("pom_batch_step_simple", [P, U64, I32], None), ("pom_batch_policy_memory", [P, I64, I64, VP], None),
+        ("pom_batch_status", [P, I64, I64, VP, VP, VP, VP, VP, VP], None),
+        ("pom_batch_last_results", [P, I64, I64, VP, VP, VP, VP, VP], None),
+        ("pom_batch_download_terminal", [P, VP, I64, I64], None),
+        ("pom_batch_counters", [P, VP], None), ("pom_batch_counters_device", [P, VP], None),
+        ("pom_batch_reset_counters", [P], None), ("pom_batch_sync", [P], None), ("pom_batch_flush", [P], None),
+        ("pom_batch_fork", [P], None), ("pom_batch_set_streams", [P, I32], None), ("pom_batch_profile", [P, C.c_int], None),
+        ("pom_batch_profile_read", [P, C.POINTER(C.c_double), C.POINTER(I64)], None),
+        ("pom_batch_launch_shape", [P, C.POINTER(I32), C.POINTER(I32), C.POINTER(I32)], None),
+        ("pom_batch_issue_info", [P, C.POINTER(I32), C.POINTER(I32)], None),
+        ("pom_batch_device_view", [P, C.POINTER(VP), C.POINTER(I64), C.POINTER(I32)], None),
+        ("pom_chain_litmus", [I32, I64, I32, I32, VP], None),
+        ("pom_step", [VP, VP], None), ("pom_env_step", [VP, VP, I32, VP, VP, VP, VP], None),
+    )
+    lenient = bool(os.environ.get("POM_LIB"))  # an older experimental build may lack the newer calls: a missing symbol is skipped
+    for name, argtypes, restype in table:
+        if lenient and not hasattr(lib, name):
+            continue
+        fn = getattr(lib, name)  # (the project's own library: a missing symbol raises)
+        if argtypes is not None:
+            fn.argtypes = argtypes
+        if restype is not None:
+            fn.restype = restype
     _lib = lib
     return lib
 
@@ -328,6 +329,52 @@ class BatchEnvironment:
     def __exit__(self, *exc):
         self.close()
 
+    # ---- what the calls that take device tensors share -----------------------------------------------
+    def _device_tensor(self, t, what: str, dtype, shape):
+        """`t` as an argument that a kernel reads or writes through its address: anything with data_ptr / shape / dtype (e.g. a torch
+        tensor) of element type `dtype` (a name such as "int32", or a torch dtype) and of `shape` (None: a free dimension), contiguous
+        and on this handle's device; contiguity and device are checked where the object tells them.  Returns `t`."""
+        dtype = str(dtype).rsplit(".", 1)[-1]
+        want = f"{dtype}[{', '.join('*' if w is None else str(w) for w in shape)}]"
+        if not hasattr(t, "data_ptr"):
+            raise ValueError(f"{what} must be a device tensor {want}, got {type(t).__name__}")
+        got = tuple(getattr(t, "shape", ()))
+        if len(got) != len(shape) or any(w is not None and w != g for w, g in zip(shape, got)):
+            raise ValueError(f"{what} must be {want}, got shape {got}")
+        if str(getattr(t, "dtype", "")).rsplit(".", 1)[-1] != dtype:
+            raise ValueError(f"{what} must be {dtype}, got {getattr(t, 'dtype', None)}")
+        if hasattr(t, "is_contiguous") and not t.is_contiguous():
+            raise ValueError(f"{what} must be contiguous")
+        dev = getattr(t, "device", None)
+        if dev is not None and (getattr(dev, "type", "cuda") != "cuda" or getattr(dev, "index", self.device) not in (None, self.device)):
+            raise ValueError(f"{what} lives on {dev}, the batch on device {self.device}")
+        return t
+
+    def _out_tensor(self, out, shape, dtype, what: str = "out"):
+        """the tensor a call writes its result to: a new one, or the caller's `out` of an earlier call, checked"""
+        if out is None:
+            import torch
+            return torch.empty(shape, dtype=dtype, device=torch.device("cuda", self.device))
+        return self._device_tensor(out, what, dtype, shape)
+
+    @contextlib.contextmanager
+    def _ordered(self, back: bool = True, tensor=None):
+        """The kernel runs on the handle's stream, the tensors live on torch's current stream: the two are ordered with events.  Before
+        the body the handle's stream waits for torch's — a tensor the caller has just produced there is complete before the call that
+        reads it begins — and, with `back`, torch's waits for the handle's after it: what the call wrote is complete before torch
+        reads it.  A no-op if both are the same stream, or if `tensor` is not torch's."""
+        if "torch" not in sys.modules or (tensor is not None and not hasattr(tensor, "is_cuda")):
+            yield
+            return
+        import torch
+        dev = torch.device("cuda", self.device)
+        mine, theirs = torch.cuda.ExternalStream(self.stream_handle(), device=dev), torch.cuda.current_stream(dev)
+        if mine.cuda_stream != theirs.cuda_stream:
+            mine.wait_stream(theirs)
+        yield
+        if back and mine.cuda_stream != theirs.cuda_stream:
+            theirs.wait_stream(mine)
+
     # ---- Environment::MakeGame / GetState ---------------------------------------------------
     def make_game(self, states: np.ndarray, first: int = 0) -> None:
         """Upload start states; they also become the reset snapshot (MakeGame, environment.cpp:53-66)."""
@@ -371,18 +418,9 @@ class BatchEnvironment:
         with `count`."""
         flags = (COPY_FROM_SNAPSHOT if from_snapshot else 0) | (COPY_SET_SNAPSHOT if set_snapshot else 0)
         if hasattr(src, "data_ptr"):
-            shape = tuple(getattr(src, "shape", ()))
-            if len(shape) != 1 or (count is not None and count != shape[0]):
-                raise ValueError(f"src must be a 1-d int64 tensor, got shape {shape}")
-            if "int64" not in str(getattr(src, "dtype", "")):
-                raise ValueError(f"src must be int64, got {getattr(src, 'dtype', None)}")
-            if hasattr(src, "is_contiguous") and not src.is_contiguous():
-                raise ValueError("src must be contiguous")
-            dev = getattr(src, "device", None)
-            if dev is not None and (getattr(dev, "type", "cuda") != "cuda" or getattr(dev, "index", self.device) not in (None, self.device)):
-                raise ValueError(f"src lives on {dev}, the batch on device {self.device}")
-            self._after_torch(src)
-            _check(self._lib, self._lib.pom_batch_copy_envs_device(self._h, src.data_ptr(), int(first), shape[0], flags))
+            self._device_tensor(src, "src", "int64", (count,))
+            with self._ordered(back=False, tensor=src):
+                _check(self._lib, self._lib.pom_batch_copy_envs_device(self._h, src.data_ptr(), int(first), src.shape[0], flags))
         elif isinstance(src, (int, np.integer)) and not isinstance(src, bool):
             if count is None:
                 raise ValueError("a raw device address needs `count`")
@@ -427,56 +465,25 @@ class BatchEnvironment:
         """moves: a device tensor int32[n,4] on this handle's device (anything with data_ptr / shape / dtype, e.g. a torch
         tensor: shape, element type, contiguity and device are checked), or the raw device address of such an array."""
         if hasattr(moves, "data_ptr"):
-            shape = tuple(getattr(moves, "shape", ()))
-            if shape != (self.n, 4):
-                raise ValueError(f"moves must be int32[{self.n}, 4] (dead agents included), got shape {shape}")
-            if "int32" not in str(getattr(moves, "dtype", "")):
-                raise ValueError(f"moves must be int32, got {getattr(moves, 'dtype', None)}")
-            if hasattr(moves, "is_contiguous") and not moves.is_contiguous():
-                raise ValueError("moves must be contiguous")
-            dev = getattr(moves, "device", None)
-            if dev is not None and (getattr(dev, "type", "cuda") != "cuda" or getattr(dev, "index", self.device) not in (None, self.device)):
-                raise ValueError(f"moves live on {dev}, the batch on device {self.device}")
-            self._after_torch(moves)
-            moves = moves.data_ptr()
-        _check(self._lib, self._lib.pom_batch_step_device(self._h, int(moves)))
-
-    def _after_torch(self, tensor) -> None:
-        """order the handle's stream behind torch's current stream: a tensor the caller has just produced there is complete
-        before the step that reads it begins (no-op if both are the same stream)"""
-        if "torch" not in sys.modules or not hasattr(tensor, "is_cuda"):
-            return
-        import torch
-        dev = torch.device("cuda", self.device)
-        mine, theirs = torch.cuda.ExternalStream(self.stream_handle(), device=dev), torch.cuda.current_stream(dev)
-        if mine.cuda_stream != theirs.cuda_stream:
-            mine.wait_stream(theirs)
+            self._device_tensor(moves, "moves", "int32", (self.n, 4))
+        with self._ordered(back=False, tensor=moves):
+            _check(self._lib, self._lib.pom_batch_step_device(self._h, _ptr(moves)))
 
     def step_device_many(self, moves, ticks: Optional[int] = None) -> None:
         """K ticks with explicit moves from a tape in device memory: a tensor int32[K, n, 4] on this handle's device (or the raw
         device address of one, with `ticks` = K).  Chained launches where the handle chains (pom_batch_step_device_many)."""
         if hasattr(moves, "data_ptr"):
-            shape = tuple(getattr(moves, "shape", ()))
-            if len(shape) != 3 or shape[1:] != (self.n, 4) or (ticks is not None and ticks != shape[0]):
-                raise ValueError(f"moves must be int32[ticks, {self.n}, 4] (dead agents included), got shape {shape}")
-            if "int32" not in str(getattr(moves, "dtype", "")):
-                raise ValueError(f"moves must be int32, got {getattr(moves, 'dtype', None)}")
-            if hasattr(moves, "is_contiguous") and not moves.is_contiguous():
-                raise ValueError("moves must be contiguous")
-            dev = getattr(moves, "device", None)
-            if dev is not None and (getattr(dev, "type", "cuda") != "cuda" or getattr(dev, "index", self.device) not in (None, self.device)):
-                raise ValueError(f"moves live on {dev}, the batch on device {self.device}")
-            ticks = shape[0]
+            self._device_tensor(moves, "moves", "int32", (ticks, self.n, 4))
+            ticks = moves.shape[0]
             # the tape is read asynchronously and must stay unchanged until the handle has been synchronised: keep the tensor (and
             # with it its memory) alive until then, whatever the caller does with its own reference
             if len(self._tapes) >= 4:  # a loop that never synchronises must not keep every tape alive: wait for the old ones
                 self.sync()
             self._tapes.append(moves)
-            self._after_torch(moves)
-            moves = moves.data_ptr()
         if ticks is None:
             raise ValueError("a raw device address needs `ticks`")
-        _check(self._lib, self._lib.pom_batch_step_device_many(self._h, int(moves), int(ticks)))
+        with self._ordered(back=False, tensor=moves):
+            _check(self._lib, self._lib.pom_batch_step_device_many(self._h, _ptr(moves), int(ticks)))
 
     def step_device_range(self, first: int, count: int, moves, stream=None, codes=None, planes=None, view_radius: Optional[int] = None,
                           viewer_attrs=None, env_attrs=None) -> None:
@@ -612,35 +619,23 @@ class BatchEnvironment:
         shape = (self.n, 5, 11, 11) if dtype == "codes" else (self.n, 4, 16, 11, 11) if per_agent or view else (self.n, 16, 11, 11)
         if view:
             shape = (self.n, 4) + shape[-3:]
-        if out is None:
-            out = torch.empty(shape, dtype=tdt, device=dev)
-        elif tuple(out.shape) != shape or out.dtype != tdt or not out.is_contiguous() or out.device != dev:
-            raise ValueError("out does not match the requested view")
+        out = self._out_tensor(out, shape, tdt)
         a_attrs = torch.empty((self.n, 4, 12 if view else 8), dtype=torch.int32, device=dev) if attrs else None
         e_attrs = torch.empty((self.n, 4), dtype=torch.int32, device=dev) if attrs else None
-        # the kernel runs on the handle's stream, the tensors live on torch's current stream: order the two with events
-        mine, theirs = torch.cuda.ExternalStream(self.stream_handle(), device=dev), torch.cuda.current_stream(dev)
-        if mine.cuda_stream != theirs.cuda_stream:
-            mine.wait_stream(theirs)
         if _step_moves is not None:
-            if tuple(_step_moves.shape) != (self.n, 4) or "int32" not in str(_step_moves.dtype) or not _step_moves.is_contiguous():
-                raise ValueError(f"moves must be a contiguous int32[{self.n}, 4] device tensor")
-        if view:
-            spec = _view_spec(code, view_radius, out, a_attrs, e_attrs)
-            if _step_moves is not None:
-                _check(self._lib, self._lib.pom_batch_step_device_observe_view(self._h, _step_moves.data_ptr(), C.byref(spec)))
+            self._device_tensor(_step_moves, "moves", "int32", (self.n, 4))
+        with self._ordered():
+            if view:
+                spec = _view_spec(code, view_radius, out, a_attrs, e_attrs)
+                if _step_moves is not None:
+                    _check(self._lib, self._lib.pom_batch_step_device_observe_view(self._h, _step_moves.data_ptr(), C.byref(spec)))
+                else:
+                    _check(self._lib, self._lib.pom_batch_observe_view(self._h, C.byref(spec)))
+            elif _step_moves is not None:
+                _check(self._lib, self._lib.pom_batch_step_device_observe(self._h, _step_moves.data_ptr(), out.data_ptr(), code, int(per_agent),
+                                                                          _ptr(a_attrs), _ptr(e_attrs)))
             else:
-                _check(self._lib, self._lib.pom_batch_observe_view(self._h, C.byref(spec)))
-        elif _step_moves is not None:
-            _check(self._lib, self._lib.pom_batch_step_device_observe(self._h, _step_moves.data_ptr(), out.data_ptr(), code, int(per_agent),
-                                                                      a_attrs.data_ptr() if attrs else None,
-                                                                      e_attrs.data_ptr() if attrs else None))
-        else:
-            _check(self._lib, self._lib.pom_batch_observe(self._h, out.data_ptr(), code, int(per_agent),
-                                                          a_attrs.data_ptr() if attrs else None,
-                                                          e_attrs.data_ptr() if attrs else None))
-        if mine.cuda_stream != theirs.cuda_stream:
-            theirs.wait_stream(mine)
+                _check(self._lib, self._lib.pom_batch_observe(self._h, out.data_ptr(), code, int(per_agent), _ptr(a_attrs), _ptr(e_attrs)))
         return out, a_attrs, e_attrs
 
     # ---- forecast: flames and deaths K ticks ahead (pom_batch_forecast) ---------------------------------
@@ -656,33 +651,17 @@ class BatchEnvironment:
         import torch
         if not 1 <= int(horizon) <= 32:
             raise ValueError("horizon must be 1..32")
-        dev = torch.device("cuda", self.device)
         want = {"flame_tick": ((self.n, 11, 11), torch.uint8)}
         if agent_ticks:
             want["agent_tick"] = ((self.n, 4), torch.int32)
         if ubflags:
             want["ubflags"] = ((self.n,), torch.int32)
-        res = {}
-        for name, (shape, tdt) in want.items():
-            t = None if out is None else out.get(name)
-            if t is None:
-                t = torch.empty(shape, dtype=tdt, device=dev)
-            elif tuple(t.shape) != shape or t.dtype != tdt or not t.is_contiguous() or t.device != dev:
-                raise ValueError(f"out[{name!r}] must be a contiguous {tdt} tensor of shape {shape} on {dev}")
-            res[name] = t
+        res = {name: self._out_tensor(None if out is None else out.get(name), shape, tdt, f"out[{name!r}]") for name, (shape, tdt) in want.items()}
         if moves is not None:
-            if tuple(getattr(moves, "shape", ())) != (self.n, 4) or "int32" not in str(getattr(moves, "dtype", "")) or not moves.is_contiguous():
-                raise ValueError(f"moves must be a contiguous int32[{self.n}, 4] device tensor")
-            if moves.device != dev:
-                raise ValueError(f"moves live on {moves.device}, the batch on {dev}")
-        # the kernel runs on the handle's stream, the tensors live on torch's current stream: order the two with events
-        mine, theirs = torch.cuda.ExternalStream(self.stream_handle(), device=dev), torch.cuda.current_stream(dev)
-        if mine.cuda_stream != theirs.cuda_stream:
-            mine.wait_stream(theirs)
-        spec = _forecast_spec(horizon, moves, res["flame_tick"], res.get("agent_tick"), res.get("ubflags"))
-        _check(self._lib, self._lib.pom_batch_forecast(self._h, C.byref(spec)))
-        if mine.cuda_stream != theirs.cuda_stream:
-            theirs.wait_stream(mine)
+            self._device_tensor(moves, "moves", "int32", (self.n, 4))
+        with self._ordered():
+            spec = _forecast_spec(horizon, moves, res["flame_tick"], res.get("agent_tick"), res.get("ubflags"))
+            _check(self._lib, self._lib.pom_batch_forecast(self._h, C.byref(spec)))
         return res
 
     # ---- rollout: R random playouts of every env (pom_batch_rollout) ---------------------------------------
@@ -700,45 +679,19 @@ class BatchEnvironment:
         reports (`fresh_agents`: from new agents); the others draw from `dist`.  `first` (likewise) names the agents whose move of
         tick 1 is `moves[e][a]`; with `moves` given and `first` not, all four are."""
         import torch
-        if not 1 <= int(horizon) <= 1024:
-            raise ValueError("horizon must be 1..1024")
-        if not 1 <= int(samples) <= 256:
-            raise ValueError("samples must be 1..256")
-        if dist not in (DIST_HARMLESS, DIST_RANDOM, DIST_STRESS):
-            raise ValueError("dist must be DIST_HARMLESS, DIST_RANDOM or DIST_STRESS")
         with_policy = simple is not None or first is not None or bool(fresh_agents)
-        simple_mask = first_mask = 0
-        if with_policy:
-            simple_mask = 0 if simple is None else _agent_mask(simple, "simple")
-            first_mask = (0 if moves is None else 0xF) if first is None else _agent_mask(first, "first")
-            if first_mask and moves is None:
-                raise ValueError("first names agents but moves is None")
-        dev = torch.device("cuda", self.device)
-        shape = (int(samples), self.n)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.int32, device=dev)
-        elif tuple(out.shape) != shape or out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
-            raise ValueError(f"out must be a contiguous int32 tensor of shape {shape} on {dev}")
+        horizon, samples, dist, simple_mask, first_mask, flags = _rollout_args(horizon, samples, dist, moves, simple, first, fresh_agents, with_policy)
+        out = self._out_tensor(out, (samples, self.n), torch.int32)
         if moves is not None:
-            if tuple(getattr(moves, "shape", ())) != (self.n, 4) or "int32" not in str(getattr(moves, "dtype", "")) or not moves.is_contiguous():
-                raise ValueError(f"moves must be a contiguous int32[{self.n}, 4] device tensor")
-            if moves.device != dev:
-                raise ValueError(f"moves live on {moves.device}, the batch on {dev}")
-        # the kernel runs on the handle's stream, the tensors live on torch's current stream: order the two with events
-        mine, theirs = torch.cuda.ExternalStream(self.stream_handle(), device=dev), torch.cuda.current_stream(dev)
-        if mine.cuda_stream != theirs.cuda_stream:
-            mine.wait_stream(theirs)
-        if with_policy:
-            spec = _RolloutPolicySpec(C.sizeof(_RolloutPolicySpec), int(horizon), int(samples), int(dist), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                      None if moves is None else moves.data_ptr(), out.data_ptr(), simple_mask, first_mask,
-                                      ROLLOUT_FRESH_AGENTS if fresh_agents else 0, 0)
-            _check(self._lib, self._lib.pom_batch_rollout_policy(self._h, C.byref(spec)))
-        else:
-            spec = _RolloutSpec(C.sizeof(_RolloutSpec), int(horizon), int(samples), int(dist), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                None if moves is None else moves.data_ptr(), out.data_ptr(), 0)
-            _check(self._lib, self._lib.pom_batch_rollout(self._h, C.byref(spec)))
-        if mine.cuda_stream != theirs.cuda_stream:
-            theirs.wait_stream(mine)
+            self._device_tensor(moves, "moves", "int32", (self.n, 4))
+        with self._ordered():
+            if with_policy:
+                spec = _RolloutPolicySpec(C.sizeof(_RolloutPolicySpec), horizon, samples, dist, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(moves),
+                                          out.data_ptr(), simple_mask, first_mask, flags, 0)
+                _check(self._lib, self._lib.pom_batch_rollout_policy(self._h, C.byref(spec)))
+            else:
+                spec = _RolloutSpec(C.sizeof(_RolloutSpec), horizon, samples, dist, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(moves), out.data_ptr(), 0)
+                _check(self._lib, self._lib.pom_batch_rollout(self._h, C.byref(spec)))
         return out
 
     # ---- rollout of a list of jobs (pom_batch_rollout_jobs) ----------------------------------------------
@@ -753,43 +706,16 @@ class BatchEnvironment:
         `simple`, `first`, `fresh_agents`, `out`: as rollout() (the playouts are always pom_batch_rollout_policy's; with none of
         the three given: random playouts, all four tick-1 moves from `moves` if it is given)."""
         import torch
-        if not 1 <= int(horizon) <= 1024:
-            raise ValueError("horizon must be 1..1024")
-        if not 1 <= int(samples) <= 256:
-            raise ValueError("samples must be 1..256")
-        if dist not in (DIST_HARMLESS, DIST_RANDOM, DIST_STRESS):
-            raise ValueError("dist must be DIST_HARMLESS, DIST_RANDOM or DIST_STRESS")
-        simple_mask = 0 if simple is None else _agent_mask(simple, "simple")
-        first_mask = (0 if moves is None else 0xF) if first is None else _agent_mask(first, "first")
-        if first_mask and moves is None:
-            raise ValueError("first names agents but moves is None")
-        dev = torch.device("cuda", self.device)
-        if not isinstance(src, torch.Tensor) or src.dtype != torch.int64 or src.dim() != 1 or not src.is_contiguous():
-            raise ValueError("src must be a contiguous int64[m] device tensor")
-        if src.device != dev:
-            raise ValueError(f"src lives on {src.device}, the batch on {dev}")
-        m = int(src.shape[0])
-        shape = (int(samples), m)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.int32, device=dev)
-        elif tuple(out.shape) != shape or out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
-            raise ValueError(f"out must be a contiguous int32 tensor of shape {shape} on {dev}")
+        horizon, samples, dist, simple_mask, first_mask, flags = _rollout_args(horizon, samples, dist, moves, simple, first, fresh_agents)
+        m = int(self._device_tensor(src, "src", "int64", (None,)).shape[0])
+        out = self._out_tensor(out, (samples, m), torch.int32)
         if moves is not None:
-            if tuple(getattr(moves, "shape", ())) != (m, 4) or "int32" not in str(getattr(moves, "dtype", "")) or not moves.is_contiguous():
-                raise ValueError(f"moves must be a contiguous int32[{m}, 4] device tensor")
-            if moves.device != dev:
-                raise ValueError(f"moves live on {moves.device}, the batch on {dev}")
-        # the kernel runs on the handle's stream, the tensors live on torch's current stream: order the two with events
-        mine, theirs = torch.cuda.ExternalStream(self.stream_handle(), device=dev), torch.cuda.current_stream(dev)
-        if mine.cuda_stream != theirs.cuda_stream:
-            mine.wait_stream(theirs)
-        spec = _RolloutJobsSpec(C.sizeof(_RolloutJobsSpec), int(horizon), int(samples), int(dist), int(seed) & 0xFFFFFFFFFFFFFFFF, m,
-                                src.data_ptr() if m else None, None if moves is None or not m else moves.data_ptr(),
-                                out.data_ptr() if m else None, simple_mask, first_mask if m else 0,
-                                ROLLOUT_FRESH_AGENTS if fresh_agents else 0, 0)
-        _check(self._lib, self._lib.pom_batch_rollout_jobs(self._h, C.byref(spec)))
-        if mine.cuda_stream != theirs.cuda_stream:
-            theirs.wait_stream(mine)
+            self._device_tensor(moves, "moves", "int32", (m, 4))
+        with self._ordered():
+            spec = _RolloutJobsSpec(C.sizeof(_RolloutJobsSpec), horizon, samples, dist, int(seed) & 0xFFFFFFFFFFFFFFFF, m,
+                                    src.data_ptr() if m else None, _ptr(moves) if m else None, out.data_ptr() if m else None, simple_mask,
+                                    first_mask if m else 0, flags, 0)
+            _check(self._lib, self._lib.pom_batch_rollout_jobs(self._h, C.byref(spec)))
         return out
 
     # ---- expand: listed games copied into slots and ticked once (pom_batch_expand) ------------------------
@@ -809,61 +735,42 @@ class BatchEnvironment:
         import torch
         dev = torch.device("cuda", self.device)
 
-        def device_tensor(a, tdt, what):
+        def device_tensor(a, what, dtype, shape):  # numpy arrays are copied to the device, anything else is _device_tensor's
             if isinstance(a, np.ndarray):
                 if not np.issubdtype(a.dtype, np.integer):
                     raise ValueError(f"{what} must be an integer array")
-                a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64 if tdt == torch.int64 else np.int32)).to(dev)
-            if not isinstance(a, torch.Tensor) or a.dtype != tdt or not a.is_contiguous():
-                raise ValueError(f"{what} must be a contiguous {tdt} device tensor or a numpy integer array")
-            if a.device != dev:
-                raise ValueError(f"{what} lives on {a.device}, the batch on {dev}")
-            return a
+                a = torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
+            return self._device_tensor(a, what, dtype, shape)
 
-        src = device_tensor(src, torch.int64, "src")
-        if src.dim() != 1:
-            raise ValueError(f"src must be int64[count], got shape {tuple(src.shape)}")
+        src = device_tensor(src, "src", "int64", (None,))
         m = int(src.shape[0])
-        moves = device_tensor(moves, torch.int32, "moves")
-        if tuple(moves.shape) != (m, 4):
-            raise ValueError(f"moves must be int32[{m}, 4], a row per job, got shape {tuple(moves.shape)}")
+        moves = device_tensor(moves, "moves", "int32", (m, 4))
         first = int(first)
         if first < 0 or first + m > self.n:
             raise ValueError(f"the range [{first}, {first + m}) lies outside the batch of {self.n} envs")
-        if out is None:
-            out = torch.empty((m,), dtype=torch.int32, device=dev)
-        elif tuple(out.shape) != (m,) or out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
-            raise ValueError(f"out must be a contiguous int32 tensor of shape ({m},) on {dev}")
+        out = self._out_tensor(out, (m,), torch.int32)
         obs, code, per_agent = None, 0, bool(per_agent)
         if codes is not None and planes is not None:
             raise ValueError("codes and planes are two forms of one observation: pass one")
         if codes is not None:
             if per_agent:
                 raise ValueError("the codes layout has no per-agent view")
-            obs, code, shape = codes, 3, (self.n, 5, 11, 11)
+            obs, code, shape, name = codes, 3, (self.n, 5, 11, 11), "codes"
         elif planes is not None:
             code = {torch.uint8: 0, torch.float16: 1, torch.float32: 2}.get(getattr(planes, "dtype", None))
             if code is None:
                 raise ValueError("planes must be uint8, float16 or float32")
-            obs, shape = planes, (self.n, 4, 16, 11, 11) if per_agent else (self.n, 16, 11, 11)
+            obs, shape, name = planes, (self.n, 4, 16, 11, 11) if per_agent else (self.n, 16, 11, 11), "planes"
         a_attrs = e_attrs = None
         if obs is not None:
-            if not isinstance(obs, torch.Tensor) or tuple(obs.shape) != shape or not obs.is_contiguous() or obs.device != dev or \
-                    (codes is not None and obs.dtype != torch.uint8):
-                raise ValueError(f"the observation must be a contiguous tensor of shape {shape} on {dev}")
+            self._device_tensor(obs, name, torch.uint8 if codes is not None else obs.dtype, shape)
             if attrs:
                 a_attrs = torch.empty((self.n, 4, 8), dtype=torch.int32, device=dev)
                 e_attrs = torch.empty((self.n, 4), dtype=torch.int32, device=dev)
-        # the kernel runs on the handle's stream, the tensors live on torch's current stream: order the two with events
-        mine, theirs = torch.cuda.ExternalStream(self.stream_handle(), device=dev), torch.cuda.current_stream(dev)
-        if mine.cuda_stream != theirs.cuda_stream:
-            mine.wait_stream(theirs)
-        spec = _ExpandSpec(C.sizeof(_ExpandSpec), 0, first, m, src.data_ptr() if m else None, moves.data_ptr() if m else None,
-                           out.data_ptr() if m else None, None if obs is None else obs.data_ptr(), code, int(per_agent),
-                           None if a_attrs is None else a_attrs.data_ptr(), None if e_attrs is None else e_attrs.data_ptr(), 0)
-        _check(self._lib, self._lib.pom_batch_expand(self._h, C.byref(spec)))
-        if mine.cuda_stream != theirs.cuda_stream:
-            theirs.wait_stream(mine)
+        with self._ordered():
+            spec = _ExpandSpec(C.sizeof(_ExpandSpec), 0, first, m, src.data_ptr() if m else None, moves.data_ptr() if m else None,
+                               out.data_ptr() if m else None, _ptr(obs), code, int(per_agent), _ptr(a_attrs), _ptr(e_attrs), 0)
+            _check(self._lib, self._lib.pom_batch_expand(self._h, C.byref(spec)))
         return out if obs is None else (out, a_attrs, e_attrs)
 
     def move_table(self, agent: int, horizon: int, samples: int, seed: int, dist: int = DIST_RANDOM, others=None, *, simple=None,
@@ -879,11 +786,7 @@ class BatchEnvironment:
         dev = torch.device("cuda", self.device)
         n = self.n
         if others is not None:
-            if tuple(getattr(others, "shape", ())) != (n, 4) or "int32" not in str(getattr(others, "dtype", "")):
-                raise ValueError(f"others must be an int32[{n}, 4] device tensor")
-            if others.device != dev:
-                raise ValueError(f"others live on {others.device}, the batch on {dev}")
-            moves = others.unsqueeze(0).repeat(6, 1, 1)
+            moves = self._device_tensor(others, "others", "int32", (n, 4)).unsqueeze(0).repeat(6, 1, 1)
         else:
             moves = torch.zeros((6, n, 4), dtype=torch.int32, device=dev)
         moves[:, :, int(agent)] = torch.arange(6, dtype=torch.int32, device=dev).unsqueeze(1)

@@ -5,6 +5,7 @@
  */
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 
 #include "pom_runtime.h"
 #include "pom_copy.h"
@@ -43,6 +44,20 @@ static int fetch_columns(PomBatch* h, int64_t first, int64_t count, void* const*
     }
     return POM_OK;
 }
+
+/* The head of every spec's check (pom_batch.h Pom*Spec): what is wrong with it, or nullptr.  SPEC_HEAD names the type for the text. */
+template <class S>
+static const char* spec_head(const S* s, const char* size_text)
+{
+    if (!s) return "the spec is NULL";
+    if (s->struct_size != (int32_t)sizeof(S)) return size_text;
+    if constexpr (std::is_array<decltype(S::reserved_)>::value) {
+        for (const auto r : s->reserved_)
+            if (r != 0) return "reserved_ must be 0";
+    } else if (s->reserved_ != 0) return "reserved_ must be 0";
+    return nullptr;
+}
+#define SPEC_HEAD(S, s) spec_head<S>(s, "struct_size is not sizeof(" #S ")")
 
 extern "C" {
 
@@ -697,6 +712,14 @@ int pom_batch_sync(PomBatch* h)
     return POM_OK;
 }
 
+/* the alignment the export kernels ask of their outputs: the planes on 4 elements (an env's four views start on that boundary), the
+ * attribute arrays on 16 bytes */
+static bool obs_misaligned(const void* planes_dev, int32_t dtype, const void* attrs_a, const void* attrs_b)
+{
+    const uintptr_t esz = dtype == POM_OBS_F16 ? 2 : dtype == POM_OBS_F32 ? 4 : 1;
+    return ((uintptr_t)planes_dev & (4 * esz - 1)) || ((uintptr_t)attrs_a & 15) || ((uintptr_t)attrs_b & 15);
+}
+
 /* what both observation entry points ask of their arguments */
 static int observe_args(const char* who, const void* planes_dev, int32_t dtype, int32_t per_agent, const int32_t* agent_attrs_dev,
                         const int32_t* env_attrs_dev)
@@ -706,10 +729,7 @@ static int observe_args(const char* who, const void* planes_dev, int32_t dtype, 
         snprintf(g_err, sizeof g_err, "%s: POM_OBS_CODES names the agents by id (10..13), there is no per-agent view of it", who);
         return POM_E_ARG;
     }
-    const uintptr_t esz = dtype == POM_OBS_F16 ? 2 : dtype == POM_OBS_F32 ? 4 : 1;
-    if (((uintptr_t)planes_dev & (4 * esz - 1)) || ((uintptr_t)agent_attrs_dev & 15) || ((uintptr_t)env_attrs_dev & 15) ||
-        (dtype == POM_OBS_U8 && !per_agent && ((uintptr_t)planes_dev & 15)))
-    {
+    if (obs_misaligned(planes_dev, dtype, agent_attrs_dev, env_attrs_dev) || (dtype == POM_OBS_U8 && !per_agent && ((uintptr_t)planes_dev & 15))) {
         snprintf(g_err, sizeof g_err, "%s: output pointers must be 16-byte aligned", who);
         return POM_E_ARG;
     }
@@ -805,20 +825,16 @@ int pom_batch_step_device_range(PomBatch* h, int64_t first, int64_t count, const
 static_assert(sizeof(PomViewSpec) == POM_VIEW_SPEC_SIZE, "pom_batch.h states the size");
 static int view_args(const char* who, const PomViewSpec* s)
 {
-    const char* what = nullptr;
-    if (!s) what = "the spec is NULL";
-    else if (s->struct_size != (int32_t)sizeof(PomViewSpec)) what = "struct_size is not sizeof(PomViewSpec)";
+    const char* what = SPEC_HEAD(PomViewSpec, s);
+    if (what) {}
     else if (s->dtype < POM_OBS_U8 || s->dtype > POM_OBS_CODES) what = "unknown dtype";
     else if (s->view_radius < 0 || s->view_radius > POM_VIEW_RADIUS_MAX) what = "view_radius must be 0..10";
-    else if (s->reserved_ != 0) what = "reserved_ must be 0";
     else if (!s->planes_dev) what = "planes_dev is NULL";
     if (what) {
         snprintf(g_err, sizeof g_err, "%s: %s", who, what);
         return POM_E_ARG;
     }
-    /* the alignment rule of per_agent = 1 (observe_args): 4 x the element size, an env's four views start on that boundary */
-    const uintptr_t esz = s->dtype == POM_OBS_F16 ? 2 : s->dtype == POM_OBS_F32 ? 4 : 1;
-    if (((uintptr_t)s->planes_dev & (4 * esz - 1)) || ((uintptr_t)s->viewer_attrs_dev & 15) || ((uintptr_t)s->env_attrs_dev & 15)) {
+    if (obs_misaligned(s->planes_dev, s->dtype, s->viewer_attrs_dev, s->env_attrs_dev)) { /* the rule of per_agent = 1 (observe_args) */
         snprintf(g_err, sizeof g_err, "%s: planes_dev must be aligned to 4 elements, the attribute pointers to 16 bytes", who);
         return POM_E_ARG;
     }
@@ -1303,12 +1319,9 @@ static_assert(sizeof(PomForecastSpec) == POM_FORECAST_SPEC_SIZE, "pom_batch.h st
 
 extern "C" int pom_batch_forecast(PomBatch* h, const PomForecastSpec* s)
 {
-    const char* what = nullptr;
-    if (!h) what = "the handle is NULL";
-    else if (!s) what = "the spec is NULL";
-    else if (s->struct_size != (int32_t)sizeof(PomForecastSpec)) what = "struct_size is not sizeof(PomForecastSpec)";
+    const char* what = !h ? "the handle is NULL" : SPEC_HEAD(PomForecastSpec, s);
+    if (what) {}
     else if (s->horizon < 1 || s->horizon > POM_FORECAST_MAX_TICKS) what = "horizon must be 1..32";
-    else if (s->reserved_[0] != 0 || s->reserved_[1] != 0) what = "reserved_ must be 0";
     else if (!s->flame_tick_dev) what = "flame_tick_dev is NULL";
     else if (((uintptr_t)s->flame_tick_dev & 15) || ((uintptr_t)s->agent_tick_dev & 15)) what = "flame_tick_dev and agent_tick_dev must be 16-byte aligned";
     else if (((uintptr_t)s->ubflags_dev & 3) || ((uintptr_t)s->moves_dev & 3)) what = "ubflags_dev and moves_dev must be 4-byte aligned";
@@ -1384,11 +1397,7 @@ static int rollout_begin(PomBatch* h, const char* who, int32_t horizon, int32_t 
 extern "C" int pom_batch_rollout(PomBatch* h, const PomRolloutSpec* s)
 {
     static const char who[] = "pom_batch_rollout";
-    const char* what = nullptr;
-    if (!s) what = "the spec is NULL";
-    else if (s->struct_size != (int32_t)sizeof(PomRolloutSpec)) what = "struct_size is not sizeof(PomRolloutSpec)";
-    else if (s->reserved_ != 0) what = "reserved_ must be 0";
-    if (what) return rollout_bad_arg(who, what);
+    if (const char* what = SPEC_HEAD(PomRolloutSpec, s)) return rollout_bad_arg(who, what);
     int64_t tiles, tiles8;
     const int rc = rollout_begin(h, who, s->horizon, s->samples, s->dist, s->moves_dev, s->result_dev, &tiles, &tiles8);
     if (rc || tiles == 0) return rc;
@@ -1409,22 +1418,22 @@ extern "C" int pom_batch_rollout(PomBatch* h, const PomRolloutSpec* s)
     return POM_OK;
 }
 
-extern "C" int pom_batch_rollout_policy(PomBatch* h, const PomRolloutPolicySpec* s)
+/* What pom_batch_rollout_policy and pom_batch_rollout_jobs share, one template over the spec type: the check of the head, the masks,
+ * the flags and the moves rule (what is wrong, or nullptr) ... */
+template <class S>
+static const char* rollout_policy_spec(const S* s, const char* size_text)
 {
-    static const char who[] = "pom_batch_rollout_policy";
-    const char* what = nullptr;
-    if (!s) what = "the spec is NULL";
-    else if (s->struct_size != (int32_t)sizeof(PomRolloutPolicySpec)) what = "struct_size is not sizeof(PomRolloutPolicySpec)";
-    else if (s->simple_mask < 0 || s->simple_mask > 15) what = "simple_mask must be 0..15";
-    else if (s->first_mask < 0 || s->first_mask > 15) what = "first_mask must be 0..15";
-    else if (s->flags & ~(int32_t)POM_ROLLOUT_FRESH_AGENTS) what = "flags must be 0 or POM_ROLLOUT_FRESH_AGENTS";
-    else if (s->reserved_ != 0) what = "reserved_ must be 0";
-    else if (s->first_mask != 0 && !s->moves_dev) what = "first_mask names agents but moves_dev is NULL";
-    if (what) return rollout_bad_arg(who, what);
-    int64_t tiles, tiles8;
-    const int rc = rollout_begin(h, who, s->horizon, s->samples, s->dist, s->moves_dev, s->result_dev, &tiles, &tiles8);
-    if (rc || tiles == 0) return rc;
-    RolloutPolicyParams p;
+    if (const char* head = spec_head(s, size_text)) return head;
+    if (s->simple_mask < 0 || s->simple_mask > 15) return "simple_mask must be 0..15";
+    if (s->first_mask < 0 || s->first_mask > 15) return "first_mask must be 0..15";
+    if (s->flags & ~(int32_t)POM_ROLLOUT_FRESH_AGENTS) return "flags must be 0 or POM_ROLLOUT_FRESH_AGENTS";
+    if (s->first_mask != 0 && !s->moves_dev) return "first_mask names agents but moves_dev is NULL";
+    return nullptr;
+}
+/* ... and the kernel's arguments: `tiles` / `tiles8` as rollout_begin gave them */
+template <class S>
+static void rollout_policy_params(const PomBatch* h, const S* s, int64_t tiles, int64_t tiles8, RolloutPolicyParams& p)
+{
     p.state = h->state;
     p.moves = s->first_mask ? s->moves_dev : nullptr; /* not read when no agent's first move is fixed */
     p.agent_mem = (s->flags & POM_ROLLOUT_FRESH_AGENTS) ? nullptr : h->agent_mem; /* a handle that never ran the policy has none: fresh agents */
@@ -1440,6 +1449,17 @@ extern "C" int pom_batch_rollout_policy(PomBatch* h, const PomRolloutPolicySpec*
     p.first_mask = s->first_mask;
     p.tiles = (uint32_t)tiles;
     p.tiles8 = (uint32_t)tiles8;
+}
+
+extern "C" int pom_batch_rollout_policy(PomBatch* h, const PomRolloutPolicySpec* s)
+{
+    static const char who[] = "pom_batch_rollout_policy";
+    if (const char* what = rollout_policy_spec(s, "struct_size is not sizeof(PomRolloutPolicySpec)")) return rollout_bad_arg(who, what);
+    int64_t tiles, tiles8;
+    const int rc = rollout_begin(h, who, s->horizon, s->samples, s->dist, s->moves_dev, s->result_dev, &tiles, &tiles8);
+    if (rc || tiles == 0) return rc;
+    RolloutPolicyParams p;
+    rollout_policy_params(h, s, tiles, tiles8, p);
     const dim3 grid((unsigned)(tiles8 * s->samples));
     if (s->simple_mask) pom_rollout_policy_kernel<true><<<grid, dim3(64), 0, h->stream>>>(p);
     else pom_rollout_policy_kernel<false><<<grid, dim3(64), 0, h->stream>>>(p);
@@ -1450,15 +1470,9 @@ extern "C" int pom_batch_rollout_policy(PomBatch* h, const PomRolloutPolicySpec*
 extern "C" int pom_batch_rollout_jobs(PomBatch* h, const PomRolloutJobsSpec* s)
 {
     static const char who[] = "pom_batch_rollout_jobs";
-    const char* what = nullptr;
-    if (!s) what = "the spec is NULL";
-    else if (s->struct_size != (int32_t)sizeof(PomRolloutJobsSpec)) what = "struct_size is not sizeof(PomRolloutJobsSpec)";
-    else if (s->simple_mask < 0 || s->simple_mask > 15) what = "simple_mask must be 0..15";
-    else if (s->first_mask < 0 || s->first_mask > 15) what = "first_mask must be 0..15";
-    else if (s->flags & ~(int32_t)POM_ROLLOUT_FRESH_AGENTS) what = "flags must be 0 or POM_ROLLOUT_FRESH_AGENTS";
-    else if (s->reserved_ != 0) what = "reserved_ must be 0";
+    const char* what = rollout_policy_spec(s, "struct_size is not sizeof(PomRolloutJobsSpec)");
+    if (what) {}
     else if (s->jobs < 0) what = "jobs must be >= 0";
-    else if (s->first_mask != 0 && !s->moves_dev) what = "first_mask names agents but moves_dev is NULL";
     else if (s->jobs > 0 && !s->src_dev) what = "src_dev is NULL";
     else if ((uintptr_t)s->src_dev & 7) what = "src_dev must be 8-byte aligned";
     if (what) return rollout_bad_arg(who, what);
@@ -1466,21 +1480,7 @@ extern "C" int pom_batch_rollout_jobs(PomBatch* h, const PomRolloutJobsSpec* s)
     const int rc = rollout_begin(h, who, s->horizon, s->samples, s->dist, s->moves_dev, s->result_dev, &groups, &groups8, s->jobs);
     if (rc || groups == 0) return rc; /* an empty list: the handle is settled, nothing is launched */
     RolloutJobsParams p;
-    p.state = h->state;
-    p.moves = s->first_mask ? s->moves_dev : nullptr; /* not read when no agent's first move is fixed */
-    p.agent_mem = (s->flags & POM_ROLLOUT_FRESH_AGENTS) ? nullptr : h->agent_mem;
-    p.result = s->result_dev;
-    p.n = h->n;
-    p.n_pad = h->n_pad;
-    p.env_offset = h->env_offset;
-    p.seed = s->seed;
-    p.horizon = s->horizon;
-    p.dist = s->dist;
-    p.max_steps = h->max_steps;
-    p.simple_mask = s->simple_mask;
-    p.first_mask = s->first_mask;
-    p.tiles = (uint32_t)groups;
-    p.tiles8 = (uint32_t)groups8;
+    rollout_policy_params(h, s, groups, groups8, p);
     p.src = s->src_dev;
     p.jobs = s->jobs;
     const dim3 grid((unsigned)(groups8 * s->samples));
@@ -1499,12 +1499,10 @@ static_assert(sizeof(PomExpandSpec) == POM_EXPAND_SPEC_SIZE, "pom_batch.h states
 extern "C" int pom_batch_expand(PomBatch* h, const PomExpandSpec* s)
 {
     static const char who[] = "pom_batch_expand";
-    const char* what = nullptr;
     /* the spec's own fields first, then the handle and what depends on it */
-    if (!s) what = "the spec is NULL";
-    else if (s->struct_size != (int32_t)sizeof(PomExpandSpec)) what = "struct_size is not sizeof(PomExpandSpec)";
+    const char* what = SPEC_HEAD(PomExpandSpec, s);
+    if (what) {}
     else if (s->flags != 0) what = "flags must be 0";
-    else if (s->reserved_ != 0) what = "reserved_ must be 0";
     else if (s->count < 0) what = "count must be >= 0";
     else if (s->count > 0 && !s->src_dev) what = "src_dev is NULL";
     else if (s->count > 0 && !s->moves_dev) what = "moves_dev is NULL";
@@ -1538,11 +1536,7 @@ extern "C" int pom_batch_expand(PomBatch* h, const PomExpandSpec* s)
     p.wave_counters = h->wave_counters;
     p.mode = h->mode;
     p.max_steps = h->max_steps;
-    p.obs_planes = s->planes_dev;
-    p.obs_agent_attrs = s->agent_attrs_dev;
-    p.obs_env_attrs = s->env_attrs_dev;
-    p.obs_dtype = s->dtype;
-    p.obs_per_agent = s->per_agent ? 1 : 0;
+    p.obs = observe_params(h, s->planes_dev, s->dtype, s->per_agent, s->agent_attrs_dev, s->env_attrs_dev);
     const dim3 grid((unsigned)((s->first + s->count - 1) / POM_TILE_ENVS - p.tile0 + 1));
     if (s->planes_dev) pom_expand_kernel<true><<<grid, dim3(64), 0, h->stream>>>(p);
     else pom_expand_kernel<false><<<grid, dim3(64), 0, h->stream>>>(p);

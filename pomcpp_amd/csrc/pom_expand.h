@@ -5,13 +5,13 @@
  *
  * One wavefront per DESTINATION tile, a quad per env, as the one-tick step kernels:
  *   1  the list's entries, then the destination tile into LDS as it stands (load_tile16_x4);
- *   2  the source columns of the tile's jobs over it — the gather of pom_gather_tile16 (pom_rollout_policy.h): lane l moves the items
+ *   2  the source columns of the tile's jobs over it — the gather of PomGather16 (pom_rollout_policy.h): lane l moves the items
  *      of column l & 15, has ONE source address, and all its loads are in flight before the first wait.  Only columns with a job that
- *      copies (src != destination) are loaded and stored.  Where the 16 sources are the 16 envs of one tile in order (wave-uniform: a
- *      ballot) the source tile is loaded as a tile;
+ *      copies (src != destination) are loaded and stored.  Where the 16 sources are the 16 envs of one tile in order (pom_sources_one_tile)
+ *      the source tile is loaded as a tile;
  *   3  the children's agent memory and episode counter — the source's: loaded with the gather, stored as soon as it has arrived (no
  *      index is both read and written, see below, so their place in the order does not matter; here nothing is carried through the tick);
- *   4  the tick for the job quads only (PomStepper<LdsEnv<16, 4>>, pack_moves_quad, pom_env_epilogue), as the handle's mode says; no
+ *   4  the tick for the job quads only (PomStepper<LdsEnv<16, 4>>, pom_tile_env_tick), as the handle's mode says; no
  *      restart is ever played;
  *   5  the register rows back into the columns that were ticked;
  *   6  the whole tile out (store_tile16_x4);
@@ -49,11 +49,7 @@ struct ExpandParams {
     uint32_t* terminal;        /* [n_pad][80] or nullptr (not POM_RESET_AT_END) */
     int64_t* wave_counters;
     int32_t mode, max_steps;
-    /* OBS: pom_batch_observe's outputs, sized for the whole batch */
-    void* obs_planes;
-    int32_t* obs_agent_attrs;
-    int32_t* obs_env_attrs;
-    int32_t obs_dtype, obs_per_agent;
+    ObserveParams obs;         /* OBS: pom_batch_observe's own arguments (observe_params), its outputs sized for the whole batch */
 };
 
 /* is entry s of the list a job for destination d: a source of the batch that is not another slot of the range */
@@ -91,49 +87,21 @@ __global__ __launch_bounds__(64, 4) void pom_expand_kernel(ExpandParams p)
         }
         if (member == 0) ep = p.episode[s];
     }
-    /* wave-uniform: the 16 sources are the 16 envs of one other tile, in order */
-    const int64_t t0 = __builtin_amdgcn_readfirstlane((int)((copyc ? sc : 0) >> 4));
-    const bool in_order = __ballot(copyc && sc == t0 * 16 + col) == ~0ull;
-    /* pom_gather_tile16's movement, written out here because its two halves are apart — every load (these, the move, the side arrays)
-     * is issued before the ONE wait that also covers the tile's DMA rows, and only then may a column be laid over the tile — and because
-     * a column without a copying job is neither loaded nor stored (there it is stored as zeros) */
-    /* the gather (pom_gather_tile16): lane l takes board bytes k = (l >> 4) + 4 t and dwords 31 + (l >> 4) + 4 t of column l & 15 */
-    constexpr int NB = POM_COL_BOARD_ITEMS / 4, ND = (POM_REC_DWORDS - POM_REC_TIMESTEP + 3) / 4; /* 31 byte loads, 13 dword loads */
-    static_assert(POM_COL_BOARD_ITEMS % 4 == 0 && POM_TILE_ENVS == 16, "64 lanes take 4 items of each of the 16 columns at a time");
-    const int sub = lane >> 4;
-    const bool last = sub < (POM_REC_DWORDS - POM_REC_TIMESTEP) - 4 * (ND - 1); /* the last round of dwords is short: row 79 only */
-    const bool gather = copyc && !in_order;
-    uint32_t gb[NB], gd[ND];
-#pragma unroll
-    for (int t = 0; t < NB; t++) gb[t] = 0;
-#pragma unroll
-    for (int t = 0; t < ND; t++) gd[t] = 0;
-    if (gather) {
-        const uint32_t* const src_tile = p.state + (sc >> 4) * POM_TILE_DWORDS;
-        const int src_col = (int)(sc & 15);
-        const uint8_t* const gbp = reinterpret_cast<const uint8_t*>(src_tile) + sub * 16 + src_col;
-        const uint32_t* const gdp = src_tile + (POM_REC_TIMESTEP + sub) * 16 + src_col;
-#pragma unroll
-        for (int t = 0; t < ND - 1; t++) gd[t] = gdp[t * 64];
-        if (last) gd[ND - 1] = gdp[(ND - 1) * 64];
-#pragma unroll
-        for (int t = 0; t < NB; t++) gb[t] = gbp[t * 64];
-    }
+    /* the 16 sources are the 16 envs of one other tile, in order: loaded as a tile below.  Else the gather's load half (PomGather16,
+     * pom_rollout_policy.h) here and its store half behind the wait: every load (these, the move, the side arrays) is issued before the
+     * ONE wait that also covers the tile's DMA rows, and only then may a column be laid over the tile.  A column without a copying job
+     * is neither loaded nor stored */
+    const int64_t t0 = pom_sources_one_tile(sc, copyc, lane);
+    const bool gather = copyc && t0 < 0;
+    PomGather16 g;
+    g.load(p.state, sc, gather, lane);
     /* the destination tile's DMA rows have landed (one wavefront per workgroup: no barrier) — before any column is laid over them */
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("" : "+v"(mine)); /* (the move is looked at from here on: nothing of the tick's packing waits for it earlier) */
-    if (in_order) {
+    if (t0 >= 0) {
         load_tile16_x4(p.state + t0 * POM_TILE_DWORDS, tile, lane);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else if (gather) {
-        uint8_t* const lb = reinterpret_cast<uint8_t*>(tile) + lane; /* byte k * 16 + col, k = sub + 4 t */
-        uint32_t* const ld = tile + POM_REC_TIMESTEP * 16 + lane;     /* dword (31 + sub + 4 t) * 16 + col */
-#pragma unroll
-        for (int t = 0; t < ND - 1; t++) ld[t * 64] = gd[t];
-        if (last) ld[(ND - 1) * 64] = gd[ND - 1];
-#pragma unroll
-        for (int t = 0; t < NB; t++) lb[t * 64] = (uint8_t)gb[t];
-    }
+    } else if (gather) g.store(tile, lane);
     /* the children's agent memory and episode counter: their source's */
     if (copy) {
         if (p.agent_mem) {
@@ -157,20 +125,11 @@ __global__ __launch_bounds__(64, 4) void pom_expand_kernel(ExpandParams p)
     if (active) { /* the quad's four lanes agree */
         LdsEnv<16, 4> acc(tile, ec, member);
         PomStepper<LdsEnv<16, 4>> stepper(acc, L);
-        const uint32_t mvp = stepper.pack_moves_quad(mine);
         const uint32_t rec_ub = L.ub; /* the record's flags: this tick's are added to them */
-        L.ub = 0;
-        status &= ~(uint32_t)POM_ST_RESTARTED;
-        stepper.step_packed(mvp);
+        status = pom_tile_env_tick(stepper, L, mine, tile, ec, member, env_mode, p.max_steps, status & ~(uint32_t)POM_ST_RESTARTED);
         new_ub = L.ub != 0;
         L.ub |= rec_ub;
-        if (env_mode) {
-            /* timeStep is looked at here only: read back from the tile instead of living in a register through the tick */
-            time_step = (int)t[POM_REC_TIMESTEP * 16] + 1;
-            if (member == 0) t[POM_REC_TIMESTEP * 16] = (uint32_t)time_step;
-            status = pom_env_epilogue(L, time_step, p.max_steps, status);
-            newly_done = (status & POM_ST_DONE) != 0;
-        }
+        newly_done = env_mode && (status & POM_ST_DONE) != 0;
         /* the register-resident rows back into the column: the played destinations only, every other column leaves as it came */
         if (member == 0) {
 #pragma unroll
@@ -184,17 +143,7 @@ __global__ __launch_bounds__(64, 4) void pom_expand_kernel(ExpandParams p)
         store_tile16_x4(p.state + tile_id * POM_TILE_DWORDS, tile, lane_late);
     }
     /* the result word, pom_batch_rollout's: one dword per entry of the list from its owner lane; POM_RO_NONE without a job */
-    if (p.result && in_range && member == 0) {
-        uint32_t word = (uint32_t)POM_RO_NONE;
-        if (job) {
-            uint32_t alive = 0;
-#pragma unroll
-            for (int i = 0; i < 4; i++) alive |= (uint32_t)(ag_dead(L.a0[i]) ^ 1) << i;
-            word = alive | ((status & (POM_ST_DONE | POM_ST_DRAW)) << 4) | ((status & POM_ST_TIMEOUT) << 1) | (new_ub ? (uint32_t)POM_RO_UB : 0u) |
-                   (((status >> POM_ST_WINNER_SHIFT) & 7u) << POM_RO_WINNER_SHIFT) | ((active ? 1u : 0u) << POM_RO_LENGTH_SHIFT);
-        }
-        p.result[j] = word;
-    }
+    if (p.result && in_range && member == 0) p.result[j] = job ? pom_rollout_word(L, status, new_ub, active ? 1u : 0u) : (uint32_t)POM_RO_NONE;
     /* POM_RESET_AT_END: the children's terminal records are their sources', one child after the other by the whole wavefront */
     if (p.terminal) {
         uint64_t todo = __ballot(copy && member == 0);
@@ -212,19 +161,7 @@ __global__ __launch_bounds__(64, 4) void pom_expand_kernel(ExpandParams p)
         /* the observation of what lies in the tile now, while the record's stores are on their way (they have been read out of LDS
          * into registers; the staging area lies behind the record rows) */
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        ObserveParams op;
-        op.state = nullptr;
-        op.n = p.n;
-        op.n_pad = p.n_pad;
-        op.block0 = 0;
-        op.planes = p.obs_planes;
-        op.agent_attrs = p.obs_agent_attrs;
-        op.env_attrs = p.obs_env_attrs;
-        op.dtype = p.obs_dtype;
-        op.per_agent = p.obs_per_agent;
-        op.viewer_attrs = nullptr;
-        op.view_radius = 0;
-        pom_observe_tile<OBS_PASS_ENVS_FUSED, false>(op, tile, reinterpret_cast<uint4*>(tile + POM_REC_DWORDS * 16), tile_id, lane);
+        pom_observe_tile<OBS_PASS_ENVS_FUSED, false>(p.obs, tile, reinterpret_cast<uint4*>(tile + POM_REC_DWORDS * 16), tile_id, lane);
     }
     /* expansion ticks are steps of the batch; no restart is ever played */
     const long long c_steps = __popcll(__ballot(active && member == 0)), c_episodes = __popcll(__ballot(newly_done && member == 0)),

@@ -37,6 +37,17 @@ static_assert(POM_ROLLOUT_MAX_TICKS < (1 << 16), "the tick count has 16 bits of 
 static_assert(POM_RO_DONE == (POM_ST_DONE << 4) && POM_RO_DRAW == (POM_ST_DRAW << 4) && POM_RO_TIMEOUT == (POM_ST_TIMEOUT << 1),
               "the status byte's bits move into the result word by shifts");
 
+/* The result word (pom_batch.h POM_RO_*) of the env whose lane this is: who is alive, how the status byte says the game stands, whether
+ * a played tick raised a flag, and the ticks played.  The owner lane of an env stores it. */
+__device__ __forceinline__ uint32_t pom_rollout_word(const PomLane& L, uint32_t status, bool ub, uint32_t length)
+{
+    uint32_t alive = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) alive |= (uint32_t)(ag_dead(L.a0[i]) ^ 1) << i;
+    return alive | ((status & (POM_ST_DONE | POM_ST_DRAW)) << 4) | ((status & POM_ST_TIMEOUT) << 1) | (ub ? (uint32_t)POM_RO_UB : 0u) |
+           (((status >> POM_ST_WINNER_SHIFT) & 7u) << POM_RO_WINNER_SHIFT) | (length << POM_RO_LENGTH_SHIFT);
+}
+
 __global__ __launch_bounds__(64, POM_QUAD_WAVES) void pom_rollout_kernel(RolloutParams p)
 {
     __shared__ __attribute__((aligned(16))) uint32_t tile[LDS_ROWS * 16];
@@ -94,15 +105,7 @@ __global__ __launch_bounds__(64, POM_QUAD_WAVES) void pom_rollout_kernel(Rollout
     }
 
     /* out: one dword per env from its owner lane, 16 consecutive dwords per wavefront; a last, short tile writes its envs only */
-    if (valid && member == 0) {
-        uint32_t alive = 0;
-#pragma unroll
-        for (int i = 0; i < 4; i++) alive |= (uint32_t)(ag_dead(L.a0[i]) ^ 1) << i;
-        const uint32_t word = alive | ((status & (POM_ST_DONE | POM_ST_DRAW)) << 4) | ((status & POM_ST_TIMEOUT) << 1) |
-                              (ub ? (uint32_t)POM_RO_UB : 0u) | (((status >> POM_ST_WINNER_SHIFT) & 7u) << POM_RO_WINNER_SHIFT) |
-                              ((uint32_t)length << POM_RO_LENGTH_SHIFT);
-        p.result[(int64_t)sample * p.n + e] = word;
-    }
+    if (valid && member == 0) p.result[(int64_t)sample * p.n + e] = pom_rollout_word(L, status, ub != 0, (uint32_t)length);
 }
 
 #endif /* POM_ROLLOUT_H_ */

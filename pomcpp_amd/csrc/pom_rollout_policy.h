@@ -28,19 +28,17 @@
  * envs in order.  One wavefront per (group of 16 consecutive jobs, sample); job 16 g + ec belongs to quad ec.  Only the front and the
  * indices differ:
  *   the load   the LDS tile is put together from 16 different columns of the state buffer: column src & 15 of tile src >> 4 becomes
- *              column ec.  Lane l moves the items of column l & 15 — board bytes k = (l >> 4) + 4 t, t = 0 .. 30, and dwords
- *              31 + (l >> 4) + 4 t, t = 0 .. 12 — so a lane has ONE source address and all its loads are immediates behind it, and
- *              every lane issues all its loads, for all 16 columns at once, before anything waits (pom_copy_gather_kernel moves its
- *              columns one after another and waits for each).  The bytes go through registers (an LDS-DMA of one byte per lane is
- *              not something this project has measured), and so do the dwords: a lane without a job stores zeros with the same
- *              instructions.  Where the 16 sources are the 16 envs of one tile in order (wave-uniform: a ballot) the tile is loaded
- *              as the other kernels load it, load_tile16_x4 — every group of a move table (BatchEnvironment.move_table) whose batch is
- *              a multiple of 16 envs is of that kind.
+ *              column ec (PomGather16 below: one source address per lane, every lane issues all its loads, for all 16 columns at once,
+ *              before anything waits; pom_copy_gather_kernel moves its columns one after another and waits for each).  The bytes go
+ *              through registers (an LDS-DMA of one byte per lane is not something this project has measured), and so do the dwords:
+ *              a lane without a job stores zeros with the same instructions.  Where the 16 sources are the 16 envs of one tile in
+ *              order (pom_sources_one_tile) the tile is loaded as the other kernels load it, load_tile16_x4 — every group of a move
+ *              table (BatchEnvironment.move_table) whose batch is a multiple of 16 envs is of that kind.
  *   no job     an entry with src outside [0, n) and the slots past the list's end: a blank record (zeros), its lanes done from the
  *              start; they still enter pom_policy_wave with actor = false.  The owner lane writes the word 0 for an entry of the list.
  *   indices    the agents' memory and the draws' key are the SOURCE env's (env_offset + src: jobs of one source play under common
  *              random numbers), the moves of tick 1 and the result word the job's.
- * The two instances without JOBS are, instruction for instruction, what they were before the parameter existed
+ * The two instances without JOBS were, instruction for instruction, what they had been before the parameter existed
  * (profiles/rollout_jobs_kernel_resources.txt).
  */
 #ifndef POM_ROLLOUT_POLICY_H_
@@ -69,37 +67,84 @@ struct RolloutJobsParams : RolloutPolicyParams {
 
 enum { RP_ROWS = POM_REC_DWORDS + 44 > LDS_ROWS ? POM_REC_DWORDS + 44 : LDS_ROWS, RP_PARK_ROWS = 3 * 4 };
 
-/* The front of the JOBS kernel: column `col` = lane & 15 of the LDS tile becomes a copy of env s's column of the state buffer, or a
- * blank record if `ok` is false.  All of a lane's loads are issued before the first of them is waited for. */
+/* The column gather of the list-driven kernels: column `col` = lane & 15 of the LDS tile becomes a copy of env s's column of the state
+ * buffer.  Lane l moves the items of column l & 15 — board bytes k = (l >> 4) + 4 t, t = 0 .. 30, and dwords 31 + (l >> 4) + 4 t,
+ * t = 0 .. 12 — so a lane has ONE source address and all its loads are immediates behind it.  Two halves, because a caller may have
+ * other loads to issue and one wait to share between them: load() issues all of a lane's loads and waits for none (a lane whose `ok`
+ * is false loads nothing and holds a blank record, zeros), store() lays what has arrived over the tile. */
+struct PomGather16 {
+    static constexpr int NB = POM_COL_BOARD_ITEMS / 4, ND = (POM_REC_DWORDS - POM_REC_TIMESTEP + 3) / 4; /* 31 byte loads, 13 dword loads */
+    static_assert(POM_COL_BOARD_ITEMS % 4 == 0 && POM_TILE_ENVS == 16, "64 lanes take 4 items of each of the 16 columns at a time");
+    uint32_t b[NB], d[ND];
+
+    /* the last round of dwords is short (row 79 only): the lanes that have an item in it; sub = lane >> 4, which of a round's four items */
+    static __device__ __forceinline__ bool last(int sub) { return sub < (POM_REC_DWORDS - POM_REC_TIMESTEP) - 4 * (ND - 1); }
+
+    __device__ __forceinline__ void load(const uint32_t* state, int64_t s, bool ok, int lane)
+    {
+        const int sub = lane >> 4;
+        const uint32_t* const src_tile = state + (ok ? s >> 4 : 0) * POM_TILE_DWORDS;
+        const int src_col = ok ? (int)(s & 15) : 0;
+        const uint8_t* const gb = reinterpret_cast<const uint8_t*>(src_tile) + sub * 16 + src_col; /* byte k * 16 + src_col, k = sub + 4 t */
+        const uint32_t* const gd = src_tile + (POM_REC_TIMESTEP + sub) * 16 + src_col;             /* dword (31 + sub + 4 t) * 16 + src_col */
+#pragma unroll
+        for (int t = 0; t < NB; t++) b[t] = 0;
+#pragma unroll
+        for (int t = 0; t < ND; t++) d[t] = 0;
+        if (ok) {
+#pragma unroll
+            for (int t = 0; t < ND - 1; t++) d[t] = gd[t * 64];
+            if (last(sub)) d[ND - 1] = gd[(ND - 1) * 64];
+#pragma unroll
+            for (int t = 0; t < NB; t++) b[t] = gb[t * 64];
+        }
+    }
+
+    __device__ __forceinline__ void store(uint32_t* tile, int lane) const
+    {
+        uint8_t* const lb = reinterpret_cast<uint8_t*>(tile) + lane; /* byte k * 16 + col, k = sub + 4 t */
+        uint32_t* const ld = tile + POM_REC_TIMESTEP * 16 + lane;     /* dword (31 + sub + 4 t) * 16 + col */
+#pragma unroll
+        for (int t = 0; t < ND - 1; t++) ld[t * 64] = d[t];
+        if (last(lane >> 4)) ld[(ND - 1) * 64] = d[ND - 1];
+#pragma unroll
+        for (int t = 0; t < NB; t++) lb[t * 64] = (uint8_t)b[t];
+    }
+};
+
+/* The front of the JOBS kernel: the whole tile gathered, a blank record where `ok` is false.  All of a lane's loads are issued before
+ * the first of them is waited for. */
 __device__ __forceinline__ void pom_gather_tile16(const uint32_t* state, int64_t s, bool ok, uint32_t* tile, int lane)
 {
-    constexpr int NB = POM_COL_BOARD_ITEMS / 4, ND = (POM_REC_DWORDS - POM_REC_TIMESTEP + 3) / 4; /* 31 byte loads, 13 dword loads */
-    static_assert(POM_COL_BOARD_ITEMS % 4 == 0 && POM_TILE_ENVS == 16, "64 lanes take 4 items of each of the 16 columns at a time");
-    const int sub = lane >> 4; /* which of the four items of a round */
-    const uint32_t* const src_tile = state + (ok ? s >> 4 : 0) * POM_TILE_DWORDS;
-    const int src_col = ok ? (int)(s & 15) : 0;
-    const uint8_t* const gb = reinterpret_cast<const uint8_t*>(src_tile) + sub * 16 + src_col; /* byte k * 16 + src_col, k = sub + 4 t */
-    const uint32_t* const gd = src_tile + (POM_REC_TIMESTEP + sub) * 16 + src_col;             /* dword (31 + sub + 4 t) * 16 + src_col */
-    const bool last = sub < (POM_REC_DWORDS - POM_REC_TIMESTEP) - 4 * (ND - 1); /* the last round of dwords is short: row 79 only */
-    uint32_t b[NB], d[ND];
-#pragma unroll
-    for (int t = 0; t < NB; t++) b[t] = 0;
-#pragma unroll
-    for (int t = 0; t < ND; t++) d[t] = 0;
-    if (ok) {
-#pragma unroll
-        for (int t = 0; t < ND - 1; t++) d[t] = gd[t * 64];
-        if (last) d[ND - 1] = gd[(ND - 1) * 64];
-#pragma unroll
-        for (int t = 0; t < NB; t++) b[t] = gb[t * 64];
-    }
-    uint8_t* const lb = reinterpret_cast<uint8_t*>(tile) + lane; /* byte k * 16 + col, k = sub + 4 t */
-    uint32_t* const ld = tile + POM_REC_TIMESTEP * 16 + lane;     /* dword (31 + sub + 4 t) * 16 + col */
-#pragma unroll
-    for (int t = 0; t < ND - 1; t++) ld[t * 64] = d[t];
-    if (last) ld[(ND - 1) * 64] = d[ND - 1];
-#pragma unroll
-    for (int t = 0; t < NB; t++) lb[t * 64] = (uint8_t)b[t];
+    PomGather16 g;
+    g.load(state, s, ok, lane);
+    g.store(tile, lane);
+}
+
+/* Are the 16 sources of a group (lane l holds the one of column l & 15, `ok`: it is one) the 16 envs of one tile, in order?  The tile's
+ * number, or -1.  Wave-uniform: a ballot.  Such a group is loaded as a tile (load_tile16_x4) instead of gathered. */
+__device__ __forceinline__ int64_t pom_sources_one_tile(int64_t s, bool ok, int lane)
+{
+    const int64_t t0 = __builtin_amdgcn_readfirstlane((int)((ok ? s : 0) >> 4));
+    return __ballot(ok && s == t0 * 16 + (lane & 15)) == ~0ull ? t0 : -1;
+}
+
+/* One tick of Environment::Step for a quad whose record lies in an LDS tile, timeStep included: the moves packed, the tick, and, with
+ * `env`, the bookkeeping whatever the handle's mode (environment.cpp:148-168).  timeStep is looked at here only: read back from the
+ * tile (env column `ec`) and counted there by the owner lane (`member` 0) instead of living in a register through the tick.  L.ub is left
+ * holding the flags this tick raised.  Returns the status byte after the tick. */
+template <class Stepper>
+__device__ __forceinline__ uint32_t pom_tile_env_tick(Stepper& stepper, PomLane& L, int mine, uint32_t* tile, int ec, int member, bool env,
+                                                      int32_t max_steps, uint32_t status)
+{
+    const uint32_t mvp = stepper.pack_moves_quad(mine);
+    L.ub = 0;
+    stepper.step_packed(mvp);
+    if (!env) return status;
+    uint32_t* const ts = tile + ec + POM_REC_TIMESTEP * 16; /* (worked out behind the tick, not carried through it) */
+    const int time_step = (int)*ts + 1;
+    if (member == 0) *ts = (uint32_t)time_step;
+    return pom_env_epilogue(L, time_step, max_steps, status);
 }
 
 template <bool JOBS>
@@ -130,9 +175,8 @@ __global__ __launch_bounds__(64, 4) void pom_rollout_policy_kernel(typename Roll
         valid = s >= 0 && s < p.n;
         e = valid ? s : 0;
         const bool okc = sc >= 0 && sc < p.n;
-        /* wave-uniform: the 16 sources are the 16 envs of one tile, in order */
-        const int64_t t0 = __builtin_amdgcn_readfirstlane((int)((okc ? sc : 0) >> 4));
-        if (__ballot(okc && sc == t0 * 16 + (lane & 15)) == ~0ull) load_tile16_x4(p.state + t0 * POM_TILE_DWORDS, tile, lane);
+        const int64_t t0 = pom_sources_one_tile(sc, okc, lane);
+        if (t0 >= 0) load_tile16_x4(p.state + t0 * POM_TILE_DWORDS, tile, lane);
         else pom_gather_tile16(p.state, sc, okc, tile, lane);
         env_key = (uint32_t)(p.env_offset + e);
     } else {
@@ -229,28 +273,14 @@ __global__ __launch_bounds__(64, 4) void pom_rollout_policy_kernel(typename Roll
             const int ec2 = ln2 >> 2, member2 = ln2 & 3;
             LdsEnv<16, 4> acc2(t2, ec2, member2);
             PomStepper<LdsEnv<16, 4>> stepper2(acc2, L);
-            const uint32_t mvp = stepper2.pack_moves_quad(mine);
-            L.ub = 0;
-            stepper2.step_packed(mvp);
-            /* Environment::Step's bookkeeping whatever the handle's mode (environment.cpp:148-168); timeStep is looked at here only: read
-             * back from the tile instead of living in a register through the tick */
-            uint32_t* const ts = t2 + ec2 + POM_REC_TIMESTEP * 16;
-            const int time_step = (int)*ts + 1;
-            if (member2 == 0) *ts = (uint32_t)time_step;
-            const uint32_t status = pom_env_epilogue(L, time_step, p.max_steps, run & 0xFFu);
+            const uint32_t status = pom_tile_env_tick(stepper2, L, mine, t2, ec2, member2, true, p.max_steps, run & 0xFFu);
             run = status | (run & 0x100u) | (L.ub ? 0x100u : 0u) | ((uint32_t)tk << 16);
         }
     }
 
     /* out: pom_rollout_kernel's word, one dword per env from its owner lane */
     if (valid && member == 0) {
-        uint32_t alive = 0;
-#pragma unroll
-        for (int i = 0; i < 4; i++) alive |= (uint32_t)(ag_dead(L.a0[i]) ^ 1) << i;
-        const uint32_t status = run & 0xFFu;
-        const uint32_t word = alive | ((status & (POM_ST_DONE | POM_ST_DRAW)) << 4) | ((status & POM_ST_TIMEOUT) << 1) |
-                              ((run & 0x100u) ? (uint32_t)POM_RO_UB : 0u) | (((status >> POM_ST_WINNER_SHIFT) & 7u) << POM_RO_WINNER_SHIFT) |
-                              ((run >> 16) << POM_RO_LENGTH_SHIFT);
+        const uint32_t word = pom_rollout_word(L, run & 0xFFu, (run & 0x100u) != 0, run >> 16);
         if constexpr (JOBS) p.result[(int64_t)sample * p.jobs + slot_out] = word;
         else p.result[(int64_t)sample * p.n + e] = word;
     }

@@ -1,0 +1,129 @@
+"""What BatchEnvironment's calls ask of their device tensors (pomcpp_amd/batch.py _device_tensor, _out_tensor): every tensor argument of
+step_device, step_device_many, copy_envs (tensor form), observe(out=), forecast, rollout, rollout_jobs, expand and move_table(others=) is
+refused with a ValueError that names the argument when its element type or its shape is wrong, when it is a non-contiguous view of a
+larger tensor, and when it lives on the CPU — and a refused call has done nothing: state, counters and episode numbers are what they were.
+
+One handle of 20 envs, one whole tile and a short one; nothing is launched by a refused call, so no larger shape can fail differently."""
+import numpy as np
+import pytest
+
+N, M, SAMPLES, HORIZON = 20, 7, 2, 4   # envs; jobs of the list-driven calls; rollout samples and horizon
+
+
+def _handle():
+    import pomcpp_amd as pa
+    from pomcpp_amd.batch import BatchEnvironment, DIST_RANDOM, MODE_ENV
+    env = BatchEnvironment(N, device=0, mode=MODE_ENV, max_steps=800)
+    env.make_game(pa.make_boards(N, seed=5))
+    env.step_random(3, DIST_RANDOM, ticks=5)   # counters that are not zero
+    return env
+
+
+def _table(env, torch):
+    """(call, argument, the text that names it, element type, shape, free: the first dimension is the caller's, the call given a tensor)"""
+    dev = torch.device("cuda", 0)
+    i32, i64, u8 = torch.int32, torch.int64, torch.uint8
+    src = torch.full((M,), -1, dtype=i64, device=dev)   # entries without a job: even a call that went through would change nothing
+    mv = torch.zeros((M, 4), dtype=i32, device=dev)
+    return [
+        ("step_device", "moves", "moves", i32, (N, 4), False, lambda t: env.step_device(t)),
+        ("step_device_many", "moves", "moves", i32, (3, N, 4), True, lambda t: env.step_device_many(t)),
+        ("copy_envs", "src", "src", i64, (N,), True, lambda t: env.copy_envs(t)),
+        ("observe", "out", "out", u8, (N, 16, 11, 11), False, lambda t: env.observe(out=t)),
+        ("forecast", "moves", "moves", i32, (N, 4), False, lambda t: env.forecast(HORIZON, moves=t)),
+        ("forecast", "out[flame_tick]", "flame_tick", u8, (N, 11, 11), False, lambda t: env.forecast(HORIZON, out={"flame_tick": t})),
+        ("forecast", "out[agent_tick]", "agent_tick", i32, (N, 4), False, lambda t: env.forecast(HORIZON, out={"agent_tick": t})),
+        ("forecast", "out[ubflags]", "ubflags", i32, (N,), False, lambda t: env.forecast(HORIZON, out={"ubflags": t}, ubflags=True)),
+        ("rollout", "moves", "moves", i32, (N, 4), False, lambda t: env.rollout(HORIZON, SAMPLES, 1, moves=t)),
+        ("rollout", "out", "out", i32, (SAMPLES, N), False, lambda t: env.rollout(HORIZON, SAMPLES, 1, out=t)),
+        ("rollout(simple=)", "moves", "moves", i32, (N, 4), False, lambda t: env.rollout(HORIZON, SAMPLES, 1, moves=t, simple=[0])),
+        ("rollout_jobs", "src", "src", i64, (M,), True, lambda t: env.rollout_jobs(t, HORIZON, SAMPLES, 1)),
+        ("rollout_jobs", "moves", "moves", i32, (M, 4), False, lambda t: env.rollout_jobs(src, HORIZON, SAMPLES, 1, moves=t)),
+        ("rollout_jobs", "out", "out", i32, (SAMPLES, M), False, lambda t: env.rollout_jobs(src, HORIZON, SAMPLES, 1, out=t)),
+        ("expand", "src", "src", i64, (M,), True, lambda t: env.expand(t, mv)),
+        ("expand", "moves", "moves", i32, (M, 4), False, lambda t: env.expand(src, t)),
+        ("expand", "out", "out", i32, (M,), False, lambda t: env.expand(src, mv, out=t)),
+        ("expand", "codes", "codes", u8, (N, 5, 11, 11), False, lambda t: env.expand(src, mv, codes=t)),
+        ("expand", "planes", "planes", u8, (N, 16, 11, 11), False, lambda t: env.expand(src, mv, planes=t)),
+        ("expand(per_agent)", "planes", "planes", u8, (N, 4, 16, 11, 11), False, lambda t: env.expand(src, mv, planes=t, per_agent=True)),
+        ("move_table", "others", "others", i32, (N, 4), False, lambda t: env.move_table(0, HORIZON, SAMPLES, 1, others=t)),
+    ]
+
+
+def _bad(torch, dtype, shape, free):
+    """the wrong tensors for an argument of `dtype` and `shape`: (what is wrong, tensor)"""
+    dev = torch.device("cuda", 0)
+    other = torch.int32 if dtype != torch.int32 else torch.int64
+    yield "dtype", torch.zeros(shape, dtype=other, device=dev)
+    yield "shape, one dimension more", torch.zeros(shape + (2,), dtype=dtype, device=dev)
+    if not free or len(shape) > 1:
+        yield "shape, last dimension", torch.zeros(shape[:-1] + (shape[-1] + 1,), dtype=dtype, device=dev)
+    if not free:
+        yield "shape, first dimension", torch.zeros((shape[0] + 1,) + shape[1:], dtype=dtype, device=dev)
+    strided = torch.zeros(shape[:-1] + (2 * shape[-1],), dtype=dtype, device=dev)[..., ::2]
+    assert tuple(strided.shape) == shape and not strided.is_contiguous()
+    yield "a strided slice", strided
+    if len(shape) > 1:
+        transposed = torch.zeros(shape[:-2] + (shape[-1], shape[-2]), dtype=dtype, device=dev).transpose(-1, -2)
+        assert tuple(transposed.shape) == shape and not transposed.is_contiguous()
+        yield "a transposed view", transposed
+    yield "on the CPU", torch.zeros(shape, dtype=dtype)
+
+
+class _Duck:
+    """anything with data_ptr / shape / dtype is taken by the step calls and copy_envs: a torch tensor's address under another shape"""
+
+    def __init__(self, t, shape, dtype):
+        self.t, self.shape, self.dtype = t, shape, dtype
+
+    def data_ptr(self):
+        return self.t.data_ptr()
+
+
+@pytest.mark.gpu
+def test_bad_tensors_are_refused_and_nothing_is_done(hip_lib):
+    import torch
+    with _handle() as env:
+        before = env.get_state(), env.counters(), env.episodes()
+        wrong = []
+        rows = 0
+        for call, arg, name, dtype, shape, free, fn in _table(env, torch):
+            for what, t in _bad(torch, dtype, shape, free):
+                rows += 1
+                try:
+                    fn(t)
+                    wrong.append(f"{call} {arg}, {what}: accepted")
+                except ValueError as e:
+                    if name not in str(e):
+                        wrong.append(f"{call} {arg}, {what}: the text does not name {name!r}: {e}")
+                except Exception as e:  # noqa: BLE001 (every row is reported)
+                    wrong.append(f"{call} {arg}, {what}: {type(e).__name__} instead of ValueError: {e}")
+        # the duck-typed form of the older calls
+        good = torch.zeros((N, 4), dtype=torch.int32, device=torch.device("cuda", 0))
+        for what, duck in (("shape", _Duck(good, (N, 3), "int32")), ("dtype", _Duck(good, (N, 4), "int64")), ("no shape", _Duck(good, (), "int32"))):
+            rows += 1
+            try:
+                env.step_device(duck)
+                wrong.append(f"step_device duck-typed moves, {what}: accepted")
+            except ValueError as e:
+                if "moves" not in str(e):
+                    wrong.append(f"step_device duck-typed moves, {what}: the text does not name 'moves': {e}")
+        after = env.get_state(), env.counters(), env.episodes()
+        assert after[0].tobytes() == before[0].tobytes(), "a refused call changed the state"
+        assert np.array_equal(after[1], before[1]) and np.array_equal(after[2], before[2]), (before[1:], after[1:])
+        assert rows > 100
+        assert not wrong, f"{len(wrong)} of {rows} rows:\n" + "\n".join(wrong)
+
+
+@pytest.mark.gpu
+def test_step_device_raw_address_passes_unchecked_and_steps(hip_lib):
+    import torch
+    from pomcpp_amd.batch import CNT_STEPS
+    with _handle() as env:
+        state, cnt, running = env.get_state(), env.counters(), ~env.is_done()
+        assert running.any()
+        moves = torch.zeros((N, 4), dtype=torch.int32, device=torch.device("cuda", 0))
+        torch.cuda.synchronize()   # a raw address is ordered by the caller
+        env.step_device(moves.data_ptr())
+        assert env.counters()[CNT_STEPS] == cnt[CNT_STEPS] + running.sum()
+        assert np.array_equal(env.get_state()["timeStep"], state["timeStep"] + running)   # (a finished game is not stepped)
