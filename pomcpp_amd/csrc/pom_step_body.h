@@ -196,6 +196,27 @@ POM_HD uint32_t pom_zero_bytes(uint32_t x) /* 0x80 in exactly the bytes of x tha
 {
     return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);
 }
+POM_HD uint32_t pom_byte_x4(uint32_t b) /* the byte b in all four bytes (b < 256) */
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(b, b, 0u); /* v_perm_b32: full rate (the multiply by 0x01010101 is a v_mul_lo_u32: four passes) */
+#else
+    return b * 0x01010101u;
+#endif
+}
+/* byte K (0..3) of each of four words, as the four bytes of one */
+template <int K>
+POM_HD uint32_t pom_gather_bytes(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t lo = __builtin_amdgcn_perm(w1, w0, 0x0C0C0400u + K * 0x0101u);
+    const uint32_t hi = __builtin_amdgcn_perm(w3, w2, 0x0C0C0400u + K * 0x0101u);
+    return __builtin_amdgcn_perm(hi, lo, 0x05040100u);
+#else
+    return ((w0 >> (8 * K)) & 0xFFu) | (((w1 >> (8 * K)) & 0xFFu) << 8) | (((w2 >> (8 * K)) & 0xFFu) << 16) |
+           (((w3 >> (8 * K)) & 0xFFu) << 24);
+#endif
+}
 POM_HD int div11(int c) /* c / 11 for a cell index (exact for 0 <= c < 586): one full-rate multiply instead of v_mul_hi_u32's four passes */
 {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -1301,12 +1322,14 @@ struct PomStepper {
                 /* (bitwise & on 0 / 1 values here and below, not &&: on lane-varying operands hipcc turns the short-circuit forms into
                  * nested exec-mask branches — a dozen scalar instructions and two jumps for three compares) */
                 const int wants = live & (int)(mvm == POM_MOVE_BOMB) & (int)(ag_bombcount(av) < ag_max_bombs(a1v));
-                const int w_all = a.gor(wants << m);
-                int slot_off = 0; /* planters visited before me */
-#pragma unroll
-                for (int j = 0; j < 4; j++) slot_off += ((w_all >> j) & 1) & ((int)((rankp >> (4 * j)) & 0xF) < myrank);
+                /* planters visited before me, all four ranks compared at once: the planters' flags travel in bit 3 of their nibbles;
+                 * with that bit set in every nibble of rankp, subtracting my rank from each (ranks are 0..3: no borrow between
+                 * nibbles) leaves it set exactly where the rank is not below mine */
+                const uint32_t w_all = (uint32_t)a.gor(wants << (4 * m + 3));
+                const uint32_t not_before = (rankp | 0x8888u) - (uint32_t)myrank * 0x1111u;
+                const int slot_off = __builtin_popcount(w_all & ~not_before);
                 const int fits = wants & (int)(L.bCnt + slot_off < POM_Q);
-                int ubm = (wants & !fits) ? POM_UB_QUEUE_OVERFLOW : 0;
+                int ubm = (wants & !fits) ? POM_UB_QUEUE_OVERFLOW : 0; /* step.cpp:191 would overrun bombDestinations[20] */
                 int planted_moving = 0; /* PlantBomb leaves the slot's old direction nibble in place: the new bomb may move */
                 if (fits) {
                     const int slot = wrap20(L.bIdx + L.bCnt + slot_off);
@@ -1327,67 +1350,70 @@ struct PomStepper {
                 const int goes = walks & !oob(ddx, ddy);
                 const int dc = ddy * POM_N + ddx, oc = y * POM_N + x;
                 const int vacated = ((on_bomb >> m) & 1) ? POM_C_BOMB : POM_C_PASSAGE;
+                /* HasDPCollision (step_utility.cpp:264-277), asked once of all four destination bytes: who else heads for my
+                 * destination; which of them are alive is looked at in the round (a flame of an earlier round may have killed one) */
+                const uint32_t same_dest = pom_zero_bytes(dstp ^ pom_byte_x4((uint32_t)dkey)) & ~(0x80u << (8 * m));
+                uint32_t dead80 = (((uint32_t)deadmask * 0x00204081u) & 0x01010101u) << 7; /* 0x80 in the bytes of dead agents */
+                /* One round is one straight line.  Every lane reads its destination (a lane that goes nowhere: its own cell, to have
+                 * an address on the board) and its own cell, the outcome of the move (step.cpp:84-184) is worked out as 0 / 1 values —
+                 * a wavefront holds 64 agents and would run every arm of a tree of branches anyway, each behind its own exec-mask
+                 * bracket — and ends in at most two predicated cell writes: the old cell gets `vacated`, the destination the agent.
+                 * Only what few wavefront-ticks need stays behind a branch: ConsumePowerup (three unconditional selects cost more vector
+                 * instructions per wavefront-tick than the skipped branch costs scalar ones: profiles/agent_round_ab.txt) and the queue
+                 * scan of an agent that steps onto a BOMB item. */
+                const int dread = goes ? dc : oc;
+                const int dpos = (ddx | (ddy << 4)) & 0xFF;
                 int died_sum = 0;
+                /* a bomb moves whatever the agents do: one has a direction already — or somebody waits for somebody, and the shortcut
+                 * below is not taken */
+                const int still_moving = (int)(nroots != 4) | ((on_bomb >> 4) & 1);
                 POM_NOUNROLL
                 for (int r = 0; r < rounds; r++) {
                     const int act = goes & (int)(mydepth == r);
-                    int item = 0, collide = 0, shows_me = 0;
-                    if (act) { /* what is there now: everything the earlier rounds did has been written */
-                        item = a.cell(dc);
-                        /* my own cell, asked together with the destination (one round trip): nobody writes it in this round —
-                         * whoever wants it waits for me and moves in a later one */
-                        shows_me = a.cell(oc) == POM_C_AGENT + m;
-#pragma unroll
-                        for (int j = 0; j < 4; j++)
-                            collide |= (j != m) & !((deadmask >> j) & 1) & (((dstp >> (8 * j)) & 0xFF) == (uint32_t)dkey);
+                    /* what is there now: everything the earlier rounds did has been written.  My own cell is asked together with the
+                     * destination (one round trip): nobody writes it in this round — whoever wants it waits for me and moves in a later one */
+                    const int item = a.cell(dread);
+                    const int shows_me = a.cell(oc) == POM_C_AGENT + m;
+                    const int collide = (same_dest & ~dead80) != 0u;
+                    const int flame = pc_is_flame(item), pu = pc_is_powerup(item);
+                    const int died = act & flame;                   /* step.cpp:84-99 */
+                    const int free_way = act & !flame & !collide;   /* (anything but passage, power-up and BOMB blocks as a collision does) */
+                    const int to_passage = free_way & (pu | (int)(item == POM_C_PASSAGE)); /* step.cpp:120-140 */
+                    const int to_bomb = free_way & (int)(item == POM_C_BOMB);              /* step.cpp:147-184 */
+                    const int kicker = ag_kick(av); /* (as it stands before this round's power-up: a BOMB item is none) */
+                    /* Will any bomb move this tick?  One has a direction already, somebody is about to kick one, or a bomb planted
+                     * just now inherited one.  Only a question while nobody waits for anybody (the shortcut below). */
+                    const int bombs_move = a.gor((to_bomb & kicker) | planted_moving | still_moving) & 1;
+                    if (to_passage & pu) { /* ConsumePowerup, step_utility.cpp:247-262 (rare: most wavefronts skip it) */
+                        a1v = item == POM_C_EXTRABOMB ? (a1v & ~0xFFFF) | ((a1v + 1) & 0xFFFF) : a1v;
+                        a1v = item == POM_C_INCRRANGE ? ag_strength_inc(a1v) : a1v;
+                        av |= (int)(item == POM_C_KICK) << 16;
                     }
-                    /* Will any bomb move this tick?  One has a direction already, somebody is about to kick one, or a bomb
-                     * planted just now inherited one.  Only asked when nobody waits for anybody (the shortcut below). */
-                    int bombs_move = 1;
-                    if (nroots == 4) {
-                        const int kicks = act & !pc_is_flame(item) & !collide & (int)(item == POM_C_BOMB) & ag_kick(av);
-                        bombs_move = ((on_bomb >> 4) & 1) | a.gor(kicks | planted_moving);
+                    /* Stepping onto a resting bomb without kicking it while no bomb moves at all: the agent loop would put him there,
+                     * bomb loop A (step.cpp:195-227) would find the bomb blocked by him and bounce him straight back (nobody can have
+                     * entered the cell he left: no dependency edge; no bomb can be heading for it: none moves), restoring both cells
+                     * and his position.  The pair is skipped — provided a queued bomb really sits there (a BOMB item without one bounces
+                     * nobody) and his own cell shows him, so that "restoring" it changes nothing.  A kicker never gets here: his kick
+                     * makes a bomb move.  He needs the same look at the queue for GetBomb: one scan serves both. */
+                    int bounce = 0;
+                    if (to_bomb & (kicker | ((int)(bombs_move == 0) & shows_me))) {
+                        const int bi = bomb_index_alone(dpos); /* the lanes are on different cells */
+                        const int found = bi >= 0;
+                        if (kicker & found) put_bomb_at(bi, pb_set(bomb_at(bi), 0xF00000u, (uint32_t)mvm << 20));
+                        ubm |= (kicker & !found) ? POM_UB_NULL_BOMB : 0; /* step.cpp:167 dereferences nullptr */
+                        bounce = (int)(kicker == 0) & found;
                     }
-                    int died = 0;
-                    if (act) {
-                        if (pc_is_flame(item)) { /* step.cpp:84-99 */
-                            died = 1;
-                            av |= POM_AG_DEAD;
-                            if (shows_me) a.put_cell(oc, vacated);
-                        } else if (!collide) {
-                            if (pc_is_powerup(item)) { /* ConsumePowerup, step_utility.cpp:247-262 */
-                                if (item == POM_C_EXTRABOMB) a1v = (a1v & ~0xFFFF) | ((a1v + 1) & 0xFFFF);
-                                else if (item == POM_C_INCRRANGE) a1v = ag_strength_inc(a1v);
-                                else av |= POM_AG_KICK;
-                                item = POM_C_PASSAGE;
-                            }
-                            if (item == POM_C_PASSAGE) { /* step.cpp:120-140 */
-                                if (shows_me) a.put_cell(oc, vacated);
-                                a.put_cell(dc, POM_C_AGENT + m);
-                                av = ag_setpos(av, ddx, ddy);
-                            } else if (item == POM_C_BOMB) { /* step.cpp:147-184 */
-                                /* Stepping onto a resting bomb without kicking it while no bomb moves at all: the agent loop
-                                 * would put him there, bomb loop A (step.cpp:195-227) would find the bomb blocked by him and
-                                 * bounce him straight back (nobody can have entered the cell he left: no dependency edge; no
-                                 * bomb can be heading for it: none moves), restoring both cells and his position.  The pair
-                                 * is skipped — provided a queued bomb really sits there (a BOMB item without one bounces nobody)
-                                 * and his own cell shows him, so that "restoring" it changes nothing. */
-                                if (!bombs_move && shows_me && bomb_index_alone(ddx | (ddy << 4)) >= 0) {
-                                } else {
-                                    a.put_cell(oc, vacated);
-                                    a.put_cell(dc, POM_C_AGENT + m);
-                                    av = ag_setpos(av, ddx, ddy);
-                                    if (ag_kick(av)) {
-                                        const int bi = bomb_index_alone(ddx | (ddy << 4)); /* GetBomb; the lanes are on different cells */
-                                        if (bi < 0) ubm |= POM_UB_NULL_BOMB; /* step.cpp:167 dereferences nullptr */
-                                        else put_bomb_at(bi, pb_set(bomb_at(bi), 0xF00000u, (uint32_t)mvm << 20));
-                                    }
-                                }
-                            }
-                        }
-                    }
+                    const int steps_on = to_bomb & !bounce; /* writes the old cell whether or not it shows him (step.cpp:147-184) */
+                    const int moves = to_passage | steps_on;
+                    if (((died | to_passage) & shows_me) | steps_on) a.put_cell(oc, vacated);
+                    if (moves) a.put_cell(dc, POM_C_AGENT + m);
+                    av = moves ? (av & ~0xFF) | dpos : av;
+                    av |= died << 17;
                     died_sum += died;
-                    if (r + 1 < rounds) deadmask |= a.gor(died << m); /* HasDPCollision skips the dead, step_utility.cpp:268 */
+                    /* HasDPCollision skips the dead, step_utility.cpp:268.  Kept as the reference has it, though no later round can tell:
+                     * whoever shares the destination of an agent that died in a flame heads for that flame and dies before his
+                     * collision is looked at.  (Only with chains: most wavefronts skip it.) */
+                    if (r + 1 < rounds) dead80 |= (uint32_t)a.gor(died << (8 * m + 7));
                 }
                 /* back to identical registers in all four lanes */
                 L.a0[0] = a.template gbcast<0>(av); L.a0[1] = a.template gbcast<1>(av);
@@ -1522,6 +1548,11 @@ struct PomStepper {
              * nibble, and decremented where the reference does it, after loop B (the cold pass below). */
             int late = 0;
             uint32_t movers = 0; /* queue offsets of the bombs with a direction */
+            /* where the agents stand NOW (after the agent loop), a byte each, and 0x80 in the bytes of the dead (the dead bit is bit 1 of
+             * an agent word's third byte) */
+            const uint32_t nowp = pom_gather_bytes<0>((uint32_t)L.a0[0], (uint32_t)L.a0[1], (uint32_t)L.a0[2], (uint32_t)L.a0[3]);
+            const uint32_t nowflags = pom_gather_bytes<2>((uint32_t)L.a0[0], (uint32_t)L.a0[1], (uint32_t)L.a0[2], (uint32_t)L.a0[3]);
+            const uint32_t nowdead80 = (nowflags << 6) & 0x80808080u;
             POM_NOUNROLL
             for (int k = a.sub(); k < L.bCnt; k += A::G) { /* split: each lane its own slots, combined below */
                 int b = pb_set(bomb_at(k), 0xF000000u, 0);
@@ -1543,13 +1574,14 @@ struct PomStepper {
                 if (idx < POM_CELLS) {
                     const int e = a.cell(idx);
                     ripe |= (e == POM_C_PASSAGE) | pc_is_flame(e);
-                    if (pc_blocks_bomb(e)) {
-                        const int ag = get_agent(pb_x(b), pb_y(b));
-                        const int ag3 = ag & 3; /* (ag == -1: agent 3's fields are read and the answer masked) */
-                        const int m2 = (mvp >> (4 * ag3)) & 0xF;
-                        const int was = (oldp >> (8 * ag3)) & 0xFF;
-                        cand |= (uint32_t)((int)(ag > -1) & (int)(m2 != POM_MOVE_IDLE) & (int)(m2 != POM_MOVE_BOMB) & (int)(pb_pos(b) != was)) << k;
-                    }
+                    /* GetAgent (bboard.cpp:289-299) of the bomb's cell: its position byte against the four agents' at once, the dead masked
+                     * out, the lowest index wins (nobody: agent 3's fields are read and the answer masked) */
+                    const uint32_t hit = pom_zero_bytes(nowp ^ pom_byte_x4((uint32_t)pb_pos(b))) & ~nowdead80;
+                    const int sh = __builtin_ctz(hit | 0x80000000u) - 7; /* 8 * index */
+                    const int m2 = (mvp >> (sh >> 1)) & 0xF;
+                    const int was = (oldp >> sh) & 0xFF;
+                    cand |= (uint32_t)(pc_blocks_bomb(e) & (int)(hit != 0u) & (int)(m2 != POM_MOVE_IDLE) & (int)(m2 != POM_MOVE_BOMB) &
+                                       (int)(pb_pos(b) != was)) << k;
                 }
             }
             if (A::G > 1) {
