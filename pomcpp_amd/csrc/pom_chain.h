@@ -1,7 +1,8 @@
 /*
  * pom_chain.h — chained launches (POM_ISSUE_CHAIN): every launch covers ALL tiles and plays ONE tick, consecutive launches go
  * to DIFFERENT streams, and what orders a tile's ticks is a ticket word per tile (StepParams.tile_seq) instead of the order of
- * the launches (host side; the device side is the CHAIN instantiation of pom_step_kernel, pom_kernels.h).
+ * the launches (host side; the device side is a wavefront's visit of a tile, pom_chain_visit.h, which the CHAIN instantiation
+ * of pom_step_kernel, pom_kernels.h, goes through).
  *
  * Why: at 65,536 envs a launch is ONE round of wavefronts, so it lasts as long as its slowest wavefront (mean 18.5 k cycles,
  * slowest 30 - 39 k: DESIGN.md §4), and the launches of a stream wait for each other — although a tile's next tick depends on

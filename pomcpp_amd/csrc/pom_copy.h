@@ -28,8 +28,8 @@
 #include <cstdint>
 
 #include "pom_batch.h"
-#include "pom_kernels.h" /* store_tile16_x4 */
 #include "pom_packed.h"
+#include "pom_tile.h" /* store_tile16_x4 */
 
 struct CopyParams {
     const int64_t* src;        /* device int64[count] */

@@ -1,7 +1,7 @@
 /*
  * pom_forecast.h — pom_batch_forecast's kernel (include/pom_batch.h PomForecastSpec): where will the fire be, and when?
  *
- * A wavefront takes a tile of 16 envs into LDS exactly as the quad step kernel does (pom_kernels.h: load_tile16_x4, lane_from_tile,
+ * A wavefront takes a tile of 16 envs into LDS exactly as the quad step kernel does (pom_tile.h: load_tile16_x4, lane_from_tile,
  * a quad of lanes per env), plays K ticks of the real tick (PomStepper::step_packed, pom_step_body.h) on that copy and never stores
  * it: after every tick it notes, per cell, the first tick that leaves the cell in flames, per agent the tick it died in, and the
  * tick's POM_UB_* flags.  Nothing of the batch is written — no record, no counter, no ticket word, no restart.

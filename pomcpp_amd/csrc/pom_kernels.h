@@ -4,10 +4,17 @@
  * one wavefront per workgroup, each env's board / bomb queue / flame queue in a column of the wavefront's LDS tile
  * ([row][lane]: every per-lane dynamic index is an LDS address, no shuffles, no scratch).
  *
- * The tick itself is pom_step_body.h; this file is the data movement around it:
+ * The tick itself is pom_step_body.h; the kernels here are the data movement around it:
  *   HBM (packed records in 16-env tiles, pom_packed.h) -> LDS tile + VGPRs -> tick(s) -> HBM,
- * the SimpleAgent policy kernel, the observation export, the board generator and counters.  The pack / unpack between the
- * boundary's 1004-byte States and the tiles and the status extraction are pom_boundary.h, included below.
+ * the SimpleAgent policy kernel, the observation export, the board generator and counters.  This file holds the __global__
+ * kernels and their parameter structs, and is the one to include for "the kernels"; what they are made of lies in parts:
+ *   pom_tile.h         the LDS tile: its rows, LdsEnv, the record's loads and stores, restart_column / column_to_record,
+ *                      lane_from_tile, pom_boardgen_wave, pom_xcd_tile_order
+ *   pom_policy_wave.h  SimpleAgent for a wavefront: PolicyStore, the cooperative searches, pom_policy_wave
+ *   pom_observe.h      the observation export of a tile in LDS: ObserveParams .. pom_observe_tile
+ *   pom_chain_visit.h  the chained launches' hand-off, device side: pom_chain_enter / pom_chain_leave
+ *   pom_boundary.h     the pack / unpack between the boundary's 1004-byte States and the tiles, the one-State call, the status
+ *                      extraction and the snapshot — kernels, included below where they always stood
  */
 #ifndef POM_KERNELS_H_
 #define POM_KERNELS_H_
@@ -23,124 +30,10 @@
 #include "pom_packed.h"
 #include "pom_policy_body.h"
 #include "pom_step_body.h"
-
-/* ---------------------------------------------------------------------------------------------
- * LDS tile of one wavefront, [row][EPW] dwords.  Rows 0..79 mirror the HBM record row for row (pom_packed.h), so the
- * whole record moves in groups of 64/EPW rows; then 5 rows of bomb-destination bytes and 31 rows that hold loop B's per-cell
- * counters while it chooses its bombs and the explosion frames (21 rows) from then on — the counters are read for the last time
- * before the first blast of loop B can push a frame, and a wavefront's envs go through both in step —: 116 rows = 29.7 / 14.8 /
- * 7.4 KB for 64 / 32 / 16 envs per wavefront (137 rows until round 5: 18 wavefronts of 16 envs per CU; now 22).
- * Frame d of column A is the dword at byte (d * EPW + A) * 4 of that region, inside the counters of column ((d * EPW + A) * 4) / 124:
- * the overlay family of tests/tile_mates.py puts a chain that goes off inside loop B in A and a bomb that is selected by its counter
- * alone on that very byte (tests/test_tile_mates.py, the GPU tests), and fails if a frame lands before the mates have read.
- * ------------------------------------------------------------------------------------------- */
-enum {
-    ROW_BOARD = POM_REC_BOARD,    /* 31 rows: four 8-bit cells per dword            */
-    ROW_BOMBS = POM_REC_BOMBS,    /* 20 rows: raw bomb words, physical queue slots  */
-    ROW_FLAMES = POM_REC_FLAMES,  /* 20 rows                                        */
-    ROW_BDEST = POM_REC_DWORDS,   /*  5 rows: 20 bytes, bomb destination snapshot   */
-    ROW_STACK = POM_REC_DWORDS + 5, /* 21 rows: explosion frames                    */
-    ROW_CLAIMS = POM_REC_DWORDS + 5,  /* 31 rows OVER the frames: a byte per cell and env, [env][124] (PomStepper::loop_b_todo) */
-    LDS_ROWS = POM_REC_DWORDS + 36
-};
-static_assert(POM_REC_DWORDS % 2 == 0, "the one-lane shapes move the record in groups of 1 or 2 rows");
-
-/*
- * EPW = envs per wavefront (64, 32 or 16), G = lanes that work on one env during the tick (pom_step_body.h):
- *   G = 1  one lane per env runs the tick; with EPW < 64 the other lanes only help moving the record (each DMA /
- *          store instruction then covers 64/EPW rows), trading idle lanes for more resident wavefronts per SIMD;
- *   G = 4  (EPW = 16) the four ADJACENT lanes 4e..4e+3 run env e's tick in lock-step and split the order-free
- *          parts; their cross-lane traffic is DPP quad permutes (one VALU op, no LDS).
- * The LDS tile is [row][EPW]; bank = (row*EPW + env) mod 32; the G lanes of an env read the same address (broadcast).
- */
-/* Where cell c of the wavefront's env number el lives in the LDS tile, in bytes.  The tile is a copy of 64 / 16 ... EPW / 16 HBM tiles
- * side by side, row for row, and an HBM tile's board is laid out by cell (pom_packed.h): for the shipped 16 envs per wavefront the
- * offset is c * 16 + el — ONE v_lshl_add_u32 per access. */
-template <int EPW>
-__device__ __forceinline__ int tile_cell_byte(int el, int c)
-{
-    return EPW == 16 ? c * 16 + el : (c >> 2) * (4 * EPW) + (c & 3) * 16 + (el >> 4) * 64 + (el & 15);
-}
-
-template <int EPW, int GG>
-struct LdsEnv {
-    static constexpr int G = GG;
-    uint32_t* t; /* &tile[env_in_wave] */
-    int sub_;    /* lane's index within its env's group; 0 = owner */
-    uint8_t* b;  /* the env's cell 0 (tile_cell_byte) */
-    uint32_t* tile0; /* the wavefront's tile (wave-uniform) */
-    __device__ LdsEnv(uint32_t* tile, int el, int sub)
-        : t(tile + el), sub_(sub), b(reinterpret_cast<uint8_t*>(tile) + tile_cell_byte<EPW>(el, 0)), tile0(tile) {}
-    /* the env's cell counters: 124 bytes of its own behind the frames, env after env — worked out where they are needed (loop B of a
-     * tick with moving bombs) instead of living in a register through the whole tick */
-    __device__ uint8_t* claim_map() const { return reinterpret_cast<uint8_t*>(tile0 + ROW_CLAIMS * EPW) + (int)(t - tile0) * 124; }
-    __device__ int sub() const { return G == 1 ? 0 : sub_; }
-    __device__ bool owner() const { return G == 1 || sub_ == 0; }
-    /* quad reductions: lane ^ 1, then lane ^ 2 */
-    __device__ static int dpp_x1(int v) { return __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true); }
-    __device__ static int dpp_x2(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true); }
-    __device__ int gor(int v) const
-    {
-        if (G == 1) return v;
-        v |= dpp_x1(v);
-        return v | dpp_x2(v);
-    }
-    __device__ int gadd(int v) const
-    {
-        if (G == 1) return v;
-        v += dpp_x1(v);
-        return v + dpp_x2(v);
-    }
-    template <int J>
-    __device__ int gbcast(int v) const /* the value held by member J of the quad */
-    {
-        if (G == 1) return v;
-        return __builtin_amdgcn_update_dpp(0, v, J * 0x55, 0xF, 0xF, true);
-    }
-    __device__ int gmin(int v) const
-    {
-        if (G == 1) return v;
-        const int a = dpp_x1(v);
-        v = a < v ? a : v;
-        const int b = dpp_x2(v);
-        return b < v ? b : v;
-    }
-    /* "the other lanes' LDS writes so far are visible from here on": true at every instruction of a wavefront in lock-step, so
-     * nothing to do; the four-lane host model of tests/emul makes its lanes meet here */
-    __device__ void sync() const {}
-    __device__ int cell(int c) const { return b[EPW == 16 ? c * 16 : (c >> 2) * (4 * EPW) + (c & 3) * 16]; }
-    __device__ void put_cell(int c, int v) { b[EPW == 16 ? c * 16 : (c >> 2) * (4 * EPW) + (c & 3) * 16] = (uint8_t)v; }
-    __device__ int bomb(int s) const { return (int)t[(ROW_BOMBS + s) * EPW]; }
-    __device__ void put_bomb(int s, int v) { t[(ROW_BOMBS + s) * EPW] = (uint32_t)v; }
-    __device__ int flame(int s) const { return (int)t[(ROW_FLAMES + s) * EPW]; }
-    __device__ void put_flame(int s, int v) { t[(ROW_FLAMES + s) * EPW] = (uint32_t)v; }
-    __device__ int bdest(int i) const { return reinterpret_cast<const uint8_t*>(t + ROW_BDEST * EPW)[(i >> 2) * (4 * EPW) + (i & 3)]; }
-    __device__ void put_bdest(int i, int v) { reinterpret_cast<uint8_t*>(t + ROW_BDEST * EPW)[(i >> 2) * (4 * EPW) + (i & 3)] = (uint8_t)v; }
-    __device__ int frame(int d) const { return (int)t[(ROW_STACK + d) * EPW]; }
-    __device__ int ag1(int i) const { return (int)t[(POM_REC_AGENTS + 2 * i + 1) * EPW]; }
-    __device__ void put_ag1(int i, int v) { t[(POM_REC_AGENTS + 2 * i + 1) * EPW] = (uint32_t)v; }
-    __device__ void set_ag1(int i, int v) { if (owner()) put_ag1(i, v); }
-    /* (loop_b_todo) cleared by the env's lanes together, a dword each per round; counted up with LDS atomics (two lanes of an env
-     * may count the same cell) */
-    __device__ void claims_clear()
-    {
-        uint32_t* cm = reinterpret_cast<uint32_t*>(claim_map());
-#pragma unroll
-        for (int k = 0; k < (31 + G - 1) / G; k++)
-            if (G * k + G - 1 < 31 || sub() + G * k < 31) cm[sub() + G * k] = 0u;
-    }
-    __device__ void claim(int c)
-    {
-        __hip_atomic_fetch_add(reinterpret_cast<uint32_t*>(claim_map() + (c & ~3)), 1u << (8 * (c & 3)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    __device__ int claims(int c) const { return claim_map()[c]; }
-    /* replicated code: all G lanes get here with the same value, the owner writes */
-    __device__ void set_cell(int c, int v) { if (owner()) put_cell(c, v); }
-    __device__ void set_bomb(int s, int v) { if (owner()) put_bomb(s, v); }
-    __device__ void set_flame(int s, int v) { if (owner()) put_flame(s, v); }
-    __device__ void set_bdest(int i, int v) { if (owner()) put_bdest(i, v); }
-    __device__ void set_frame(int d, int v) { if (owner()) t[(ROW_STACK + d) * EPW] = (uint32_t)v; }
-};
+#include "pom_tile.h"
+#include "pom_policy_wave.h"
+#include "pom_observe.h"
+#include "pom_chain_visit.h"
 
 struct StepParams {
     uint32_t* state;
@@ -186,973 +79,6 @@ struct StepParams {
 #endif
 };
 
-/*
- * One env's start board (pom_boardgen.h), drawn by the whole wavefront into the column of env number `el` of an
- * [row][EPW] tile with ROWS rows.  `key` must be wave-uniform.  Lane l draws cells l and l+64; the two ballots of "wood" are
- * the wood set, so the flag pass runs on uniform values (scalar unit) and only its few cell writes touch a lane.
- */
-template <int EPW, int ROWS>
-__device__ __forceinline__ void pom_boardgen_wave(uint32_t* tile, int el, uint32_t key, int lane)
-{
-    uint32_t* col = tile + el;
-    uint8_t* cells = reinterpret_cast<uint8_t*>(tile);
-    const uint32_t k0 = pom_board_cell_kind(key, lane);
-    cells[tile_cell_byte<EPW>(el, lane)] = (uint8_t)pom_board_cell_code(k0);
-    const int c1 = lane + 64; /* cells 64..123: the three behind the board are 0, as pom_pack_state writes them */
-    uint32_t k1 = 0u;
-    if (c1 < 4 * POM_REC_BOARD_DWORDS) {
-        k1 = c1 < POM_CELLS ? pom_board_cell_kind(key, c1) : 0u;
-        cells[tile_cell_byte<EPW>(el, c1)] = (uint8_t)pom_board_cell_code(k1);
-    }
-    const uint64_t w0 = __ballot(k0 == 2u), w1 = __ballot(k1 == 2u);
-    const int r = POM_REC_TIMESTEP + lane;
-    if (r < ROWS) col[r * EPW] = pom_fresh_row(r);
-    /* the flags (pom_boardgen_body.h, step 2).  Per lane, in parallel: how many woods are still to come at each of my cells
-     * (prefix counts of the ballots) and the selection threshold that follows from it.  Then the countdown, wave-uniform:
-     * one readlane and a compare per wood.  The chosen cells come back as two masks and are rewritten by their lanes. */
-    const int woods = __popcll(w0) + __popcll(w1);
-    const uint64_t below = lane == 0 ? 0ull : (~0ull >> (64 - lane)); /* the lanes before mine */
-    const int t0 = (int)pom_board_threshold(key, lane, woods - __popcll(w0 & below));
-    const int t1 = (int)pom_board_threshold(key, c1 < POM_CELLS ? c1 : 0, woods - __popcll(w0) - __popcll(w1 & below));
-    uint64_t ch0 = 0, ch1 = 0;
-    {
-        int need = (woods + 1) >> 1;
-        uint64_t w = w0;
-        POM_NOUNROLL
-        while (w != 0 && need > 0) {
-            const int l = __builtin_ctzll(w);
-            w &= w - 1;
-            if (__builtin_amdgcn_readlane(t0, l) < need) {
-                ch0 |= 1ull << l;
-                need--;
-            }
-        }
-        w = w1;
-        POM_NOUNROLL
-        while (w != 0 && need > 0) {
-            const int l = __builtin_ctzll(w);
-            w &= w - 1;
-            if (__builtin_amdgcn_readlane(t1, l) < need) {
-                ch1 |= 1ull << l;
-                need--;
-            }
-        }
-    }
-    if ((ch0 >> lane) & 1) cells[tile_cell_byte<EPW>(el, lane)] = (uint8_t)pom_board_flag_code(key, lane);
-    if ((ch1 >> lane) & 1) cells[tile_cell_byte<EPW>(el, c1)] = (uint8_t)pom_board_flag_code(key, c1);
-    if (lane < POM_AGENT_COUNT) cells[tile_cell_byte<EPW>(el, pom_corner_cell(lane))] = (uint8_t)(POM_C_AGENT + lane);
-}
-
-/*
- * HBM -> LDS without touching VGPRs: `global_load_lds_dword` takes a per-lane global address and writes LDS
- * at (wave-uniform base) + 4*lane.  With the [row][EPW] tile one instruction therefore lands 64/EPW
- * consecutive rows (lane l -> row r0 + l/EPW, env l%EPW); all rows are in flight at once, no ds_write.
- * `col` may differ per lane: state column or snapshot column of the lane's env.
- */
-__device__ __forceinline__ void dma_rows(const uint32_t* g, uint32_t* lds_base)
-{
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)lds_base, 4, 0, 0);
-}
-template <int EPW>
-__device__ __forceinline__ void load_tile(const uint32_t* col, int64_t np /* row stride of a column */, uint32_t* tile, int sub)
-{
-    constexpr int GR = 64 / EPW; /* rows per instruction */
-    /* a rolled loop with a running pointer: fully unrolled, hipcc precomputes all per-lane 64-bit addresses first
-     * (200+ VGPRs) */
-    const uint32_t* g = col + (int64_t)sub * np;
-    const int64_t stride = (int64_t)GR * np;
-#pragma unroll 4
-    for (int r0 = 0; r0 < POM_REC_DWORDS; r0 += GR) {
-        dma_rows(g, tile + r0 * EPW);
-        g += stride;
-    }
-}
-template <int EPW>
-__device__ __forceinline__ void store_tile(uint32_t* col, int64_t np, const uint32_t* tile, int sub, int el)
-{
-    constexpr int GR = 64 / EPW;
-    uint32_t* g = col + (int64_t)sub * np;
-    const int64_t stride = (int64_t)GR * np;
-    const uint32_t* l = tile + sub * EPW + el;
-#pragma unroll 8
-    for (int r0 = 0; r0 < POM_REC_DWORDS; r0 += GR) {
-        *g = l[r0 * EPW];
-        g += stride;
-    }
-}
-/* EPW = 16: the same movement in 16-byte pieces (gfx950's global_load_lds_dwordx4 / dwordx4 stores).  A tile row is 16 envs
- * = 64 contiguous bytes in HBM and in LDS, so lane l takes envs 4(l%4)..+3 of row r0 + l/4 and one instruction covers 16 rows:
- * for the 80 rows of a record five whole instructions per direction (a row count that is no multiple of 16 ends with one in which
- * only the lanes of the remaining rows take part).  `base` = the tile's first dword: the buffers are laid out tile by tile (pom_packed.h),
- * a row stride of POM_TILE_ENVS = 16 dwords, and a whole instruction moves 1,024 contiguous bytes. */
-/* AUX: the instruction's cache policy bits (16 = sc1: served by the L2, never by this CU's vector cache) */
-/* Addresses: the tile's first byte is wave-uniform and a lane's piece lies less than 1,024 bytes behind it, so an address is a
- * scalar base plus a 32-bit lane offset plus the instruction's immediate — no 64-bit vector arithmetic per instruction.  The
- * immediate of a load to LDS counts for the LDS address as well (it holds up to 4,095): the rows of a record are reached from two
- * bases, rows 0..63 and 64.. — on both sides — and the instructions of a base follow each other with nothing in between. */
-typedef __attribute__((address_space(3))) char pom_lds_char;
-template <int R0, int ROWS, int AUX>
-__device__ __forceinline__ void load_tile16_x4_from(const char* base, uint32_t off, pom_lds_char* tile) /* the whole row groups from row R0 on */
-{
-    if constexpr (R0 + 16 <= ROWS) {
-        constexpr int B0 = R0 / 64 * 64; /* the base this row group is reached from: 64 rows = 4,096 bytes */
-        const char* b = base + B0 * 64;
-        if (B0 != 0) asm("" : "+s"(b)); /* (a second scalar base — not the first with the 4,096 added per lane in 64 bits) */
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(b + off),
-                                         (__attribute__((address_space(3))) void*)(tile + B0 * 64), 16, (R0 - B0) * 64, AUX);
-        load_tile16_x4_from<R0 + 16, ROWS, AUX>(base, off, tile);
-    }
-}
-template <int ROWS = POM_REC_DWORDS, int AUX = 0>
-__device__ __forceinline__ void load_tile16_x4(const uint32_t* base, uint32_t* tile, int lane)
-{
-    static_assert(ROWS <= POM_REC_DWORDS, "inside the record");
-    static_assert(POM_TILE_ENVS == 16, "a row is 64 contiguous bytes on both sides: what the immediates say");
-    const char* const b = reinterpret_cast<const char*>(base);
-    const uint32_t off = 16u * (uint32_t)lane;
-    pom_lds_char* const t = (pom_lds_char*)tile; /* (as an LDS address first, the offsets added to that) */
-    load_tile16_x4_from<0, ROWS, AUX>(b, off, t);
-    if (ROWS % 16 != 0 && (lane >> 2) < ROWS % 16) /* the last rows: the lanes beyond them sit this one out */
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((b + (ROWS / 16) * 16 * 64) + off),
-                                         (__attribute__((address_space(3))) void*)(t + (ROWS / 16) * 16 * 64), 16, 0, AUX);
-}
-template <bool NT = false>
-__device__ __forceinline__ void store_tile16_x4(uint32_t* base, const uint32_t* tile, int lane)
-{
-    constexpr int ROWS = POM_REC_DWORDS;
-    static_assert(POM_TILE_ENVS == 16, "a row is 64 contiguous bytes on both sides, as in load_tile16_x4");
-    const uint32_t off = 16u * (uint32_t)lane; /* bytes */
-    char* const b = reinterpret_cast<char*>(base);
-    constexpr int stride = 1024; /* bytes between row groups */
-    const uint4* l = reinterpret_cast<const uint4*>(tile) + lane;
-    typedef uint32_t pom_u32x4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-    for (int r0 = 0; r0 + 16 <= ROWS; r0 += 16) {
-        uint4* g = reinterpret_cast<uint4*>((b + (r0 / 16) * stride) + off); /* scalar base + lane offset */
-        if (NT) {
-            const uint4 v = l[r0 * 4];
-            __builtin_nontemporal_store(pom_u32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<pom_u32x4*>(g));
-        } else *g = l[r0 * 4];
-    }
-    if (ROWS % 16 != 0 && (lane >> 2) < ROWS % 16) {
-        uint4* g = reinterpret_cast<uint4*>((b + (ROWS / 16) * stride) + off);
-        if (NT) {
-            const uint4 v = l[(ROWS / 16) * 16 * 4];
-            __builtin_nontemporal_store(pom_u32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<pom_u32x4*>(g));
-        } else *g = l[(ROWS / 16) * 16 * 4];
-    }
-}
-/*
- * The restart snapshot is kept array-of-structs: env e's record is the 320 contiguous bytes snap[e * 80 .. e * 80 + 79].
- * A restart needs ONE env's whole record, and in the column layout of the state buffer that is 80 dwords in 80
- * different 64-byte sectors (4 useful bytes each: 18 MB of HBM fetch per step at 65,536 envs for the 3.8 % of envs that
- * restart, a fifth of the kernel's whole traffic; profiles/r02a_head1_summary.txt).  Here the whole wavefront fetches the
- * record of one restarting env — lane l takes dwords l and l + 64, whole sectors — and writes it into that env's
- * tile column.  `src` = &snap[e * POM_REC_DWORDS]; ROWS = how many leading rows the caller needs.
- */
-template <int EPW, int ROWS = POM_REC_DWORDS>
-__device__ __forceinline__ void restart_column(uint32_t* tile, int el, const uint32_t* src, int lane)
-{
-    const uint32_t v0 = src[lane];
-    const uint32_t v1 = lane + 64 < ROWS ? src[lane + 64] : 0u;
-    if (lane < POM_REC_BOARD_DWORDS) { /* a dense record holds four cells per dword, the tile lays the board out by cell */
-        uint8_t* cells = reinterpret_cast<uint8_t*>(tile);
-#pragma unroll
-        for (int j = 0; j < 4; j++) cells[tile_cell_byte<EPW>(el, 4 * lane + j)] = (uint8_t)(v0 >> (8 * j));
-    } else tile[lane * EPW + el] = v0;
-    if (lane + 64 < ROWS) tile[(lane + 64) * EPW + el] = v1;
-}
-/* the other way: env number el's column of the tile as a dense record (terminal buffer, snapshot) */
-template <int EPW>
-__device__ __forceinline__ void column_to_record(const uint32_t* tile, int el, uint32_t* dst, int lane)
-{
-    if (lane < POM_REC_BOARD_DWORDS) {
-        const uint8_t* cells = reinterpret_cast<const uint8_t*>(tile);
-        uint32_t v = 0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) v |= (uint32_t)cells[tile_cell_byte<EPW>(el, 4 * lane + j)] << (8 * j);
-        dst[lane] = v;
-    } else dst[lane] = tile[lane * EPW + el];
-    if (lane + 64 < POM_REC_DWORDS) dst[lane + 64] = tile[(lane + 64) * EPW + el];
-}
-
-/* the register-resident rows (timeStep, meta, agents) of one env, out of / into its tile column */
-__device__ __forceinline__ void lane_from_tile(PomLane& L, int& time_step, uint32_t& status, const uint32_t* t, int epw)
-{
-    uint32_t ag[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) ag[k] = t[(POM_REC_AGENTS + k) * epw];
-    pom_lane_load(L, ag, status);
-    time_step = (int)t[POM_REC_TIMESTEP * epw];
-}
-
-/* the diagnostic builds' fields of a lane, for a kernel that takes no part in them: the phase clocks at zero, and no cut (990 lies
- * beyond every POM_CUT number of pom_step_body.h) — the diagnostic truncation is the step kernels' business.  Empty in a normal build */
-__device__ __forceinline__ void pom_lane_diag_off(PomLane& L)
-{
-#if defined(POM_DIAG)
-    for (int k = 0; k < POM_PH_N; k++) L.t_acc[k] = 0;
-    L.t_last = 0;
-#endif
-#if defined(POM_TRUNC)
-    L.trunc = 990;
-#endif
-    (void)L;
-}
-
-/* the four lanes of an env as the SimpleAgent policy sees them (pom_policy_body.h): lane = agent, 16 envs per wavefront */
-struct PolicyStore {
-    const uint32_t* tile0; /* the wavefront's tile */
-    const uint32_t* t; /* &tile[env_in_wave], row stride 16 dwords */
-    uint8_t* dcol;     /* &danger[env_in_wave], a byte per cell, row stride 16 */
-    uint32_t* scol;    /* &sets[env_in_wave], row stride 16 */
-    int who;           /* lane % 4 */
-#if defined(POM_TRUNC)
-    int trunc = 990;
-#endif
-    __device__ int member() const { return who; }
-    __device__ int danger(int c) const { return dcol[c * 16]; }
-    __device__ void danger_init(int c) { dcol[c * 16] = (uint8_t)POM_DANGER_NONE; }
-    __device__ void danger_put(int c, int tm) { dcol[c * 16] = (uint8_t)tm; }
-    __device__ uint32_t setw(int k) const { return scol[k * 16]; }
-    __device__ void set_put(int k, uint32_t bits) { scol[k * 16] = bits; }
-    /* (t = tile + env: the env's cell c is the tile's byte c * 16 + env, pom_packed.h) */
-    __device__ int cell(int c) const { return reinterpret_cast<const uint8_t*>(t)[c * 16 - 3 * (int)(t - tile0)]; }
-    __device__ uint32_t cells4(int k) const /* the codes of cells 4k .. 4k+3, a byte each */
-    {
-        const uint8_t* b = reinterpret_cast<const uint8_t*>(tile0) + (t - tile0) + 64 * k;
-        return (uint32_t)b[0] | ((uint32_t)b[16] << 8) | ((uint32_t)b[32] << 16) | ((uint32_t)b[48] << 24);
-    }
-    __device__ int bomb(int s) const { return (int)t[(POM_REC_BOMBS + s) * 16]; }
-};
-
-/* ---------------------------------------------------------------------------------------------
- * SimpleAgent's two searches, run for all agents of a wavefront TOGETHER (round 3).  With a lane per agent and the 121-bit sets
- * in four registers of that lane, a wavefront pays its LONGEST flood (23.5 + 15.9 levels where the average act() runs 2.9 + 2.0,
- * tests/emul/flood_levels.sh) at ~70 VALU per level, while 80 % (forward) / 60 % (backward) of its lanes have no flood to run.
- * Here the wavefront's flood jobs — whoever's they are — are dealt to its 16 quads, 16 at a time: job i of a round goes to quad i,
- * whose four lanes hold the job's sets one 32-cell word each (pom_quad_*_level, pom_policy_body.h: two DPP word exchanges and a
- * dozen logic ops per level).  A round lasts as long as its longest job, at a third of the price per level.  No LDS memory is
- * used for the hand-over (the fused kernel has none to spare): a job's inputs are pulled from its owner lane and its answer is
- * pulled back by the owner with ds_bpermute; which lane owns job i comes from one ds_permute of the lanes' ranks.
- * ------------------------------------------------------------------------------------------- */
-struct PomQuadLanes {
-    typedef uint32_t W;
-    int k;
-    uint32_t c0_, c10_, valid_, not_first_, not_last_;
-    __device__ explicit PomQuadLanes(int k_) : k(k_)
-    {
-        const uint32_t a[4] = {0x00400801u, 0x00801002u, 0x01002004u, 0x00004008u};
-        const uint32_t b[4] = {0x00200400u, 0x00400801u, 0x00801002u, 0x01002004u};
-        c0_ = pick4(k, a);
-        c10_ = pick4(k, b);
-        valid_ = k == 3 ? 0x01FFFFFFu : ~0u;
-        not_first_ = k == 0 ? 0u : ~0u;
-        not_last_ = k == 3 ? 0u : ~0u;
-    }
-    __device__ static int qor(int v)
-    {
-        v |= __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true);
-        return v | __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true);
-    }
-    /* quad_perm [0,0,1,2]: lane j reads lane j-1; [1,2,3,3]: lane j reads lane j+1 */
-    __device__ W prev(W w) const { return (W)__builtin_amdgcn_update_dpp(0, (int)w, 0x90, 0xF, 0xF, true) & not_first_; }
-    __device__ W next(W w) const { return (W)__builtin_amdgcn_update_dpp(0, (int)w, 0xF9, 0xF, 0xF, true) & not_last_; }
-    __device__ bool any(W w) const { return qor((int)w) != 0; }
-    __device__ W bit(int c) const { return (c >> 5) == k ? 1u << (c & 31) : 0u; }
-    __device__ W col0() const { return c0_; }
-    __device__ W col10() const { return c10_; }
-    __device__ W valid() const { return valid_; }
-    __device__ int lowest(W w) const
-    {
-        int r = w ? 32 * k + __builtin_ctz(w) : 999;
-        const int a = __builtin_amdgcn_update_dpp(0, r, 0xB1, 0xF, 0xF, true);
-        r = a < r ? a : r;
-        const int b = __builtin_amdgcn_update_dpp(0, r, 0x4E, 0xF, 0xF, true);
-        return b < r ? b : r;
-    }
-    __device__ int gates_hit(W hit, uint32_t g8) const
-    {
-        int m = 0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int g = (int)((g8 >> (8 * j)) & 0xFF); /* 0xFF (no gate): word 7, nobody's */
-            m |= (int)(((g >> 5) == k) & ((hit >> (g & 31)) & 1u)) << j;
-        }
-        return qor(m);
-    }
-};
-
-/* which lane owns job i (for i < the number of jobs), in lane i: every lane sends its id to a slot of its own — the job lanes to
- * their rank, the others behind them — one ds_permute */
-__device__ __forceinline__ int pom_job_owners(uint64_t jobs, bool need, int lane, int& rank, int& njobs)
-{
-    njobs = __popcll(jobs);
-    rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(jobs >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)jobs, 0u));
-    const int slot = need ? rank : njobs + (lane - rank);
-    return __builtin_amdgcn_ds_permute(slot << 2, lane);
-}
-
-/* FillRMap's reach + MoveTowardsSafePlace's choice for every lane with `need`: the lowest cell of (window & reachable & safe) or
- * -1.  src: the agent's cell; radius: of the scan window (the danger value; the worker lanes build the window word by word,
- * pom_window_word); sets: the wavefront's prepared cell sets, rows [word][16 envs] (0..3 walkable, 4..7 agents, 8..11 safe).
- * Every lane of the wavefront calls this. */
-__device__ __forceinline__ int pom_coop_forward(bool need, int src, int radius, const uint32_t* sets, int lane)
-{
-    const uint64_t jobs = __ballot(need);
-    int result = -1;
-    if (jobs == 0) return result;
-    int rank, njobs;
-    const int owner_tab = pom_job_owners(jobs, need, lane, rank, njobs);
-    const int k = lane & 3, q = lane >> 2;
-    const PomQuadLanes Q(k);
-    POM_NOUNROLL
-    for (int base = 0; base < njobs; base += 16) {
-        const int j = base + q;
-        const bool has = j < njobs;
-        const int ow = __builtin_amdgcn_ds_bpermute((has ? j : lane) << 2, owner_tab);
-        const int owner = has ? ow : lane;
-        const int desc = __builtin_amdgcn_ds_bpermute(owner << 2, src | (radius << 8));
-        const int jsrc = desc & 0xFF, jrad = desc >> 8;
-        const int env = owner >> 2;
-        const uint32_t me = ~Q.bit(jsrc); /* FillRMap never re-enters its source */
-        const uint32_t walk = sets[k * 16 + env] & me, agents = sets[(4 + k) * 16 + env] & me, safe = sets[(8 + k) * 16 + env];
-        uint32_t front = has ? Q.bit(jsrc) : 0u, all = 0u;
-        bool live = has;
-        POM_NOUNROLL
-        while (__any(live)) {
-            if (live) live = pom_quad_forward_level(Q, walk, agents, front, all);
-        }
-        const int jy = div11(jsrc);
-        const int low = Q.lowest(pom_window_word(k, jsrc - jy * POM_N, jy, jrad) & all & safe);
-        const int got = __builtin_amdgcn_ds_bpermute((rank & 15) << 4, low); /* lane 0 of the quad that worked on my job */
-        if (need && (rank >> 4) == (base >> 4)) result = got == 999 ? -1 : got;
-    }
-    return result;
-}
-
-/* MoveTowardsPosition's backward flood for every lane with `need`: which of its gates (g8: a cell per byte, DOWN UP RIGHT LEFT of
- * the agent's cell, 0xFF = none) the first level that reaches any of them reaches, as a 4-bit mask (0: the target is out of
- * reach).  Every lane of the wavefront calls this. */
-__device__ __forceinline__ int pom_coop_backward(bool need, int src, int target, uint32_t g8, const uint32_t* sets, int lane)
-{
-    const uint64_t jobs = __ballot(need);
-    int result = 0;
-    if (jobs == 0) return result;
-    int rank, njobs;
-    const int owner_tab = pom_job_owners(jobs, need, lane, rank, njobs);
-    const int k = lane & 3, q = lane >> 2;
-    const PomQuadLanes Q(k);
-    POM_NOUNROLL
-    for (int base = 0; base < njobs; base += 16) {
-        const int j = base + q;
-        const bool has = j < njobs;
-        const int ow = __builtin_amdgcn_ds_bpermute((has ? j : lane) << 2, owner_tab);
-        const int owner = has ? ow : lane;
-        const int jsrc = __builtin_amdgcn_ds_bpermute(owner << 2, src);
-        const int jt = __builtin_amdgcn_ds_bpermute(owner << 2, target);
-        const uint32_t jg = (uint32_t)__builtin_amdgcn_ds_bpermute(owner << 2, (int)g8);
-        const int env = owner >> 2;
-        const uint32_t walk = sets[k * 16 + env] & ~Q.bit(jsrc);
-        const uint32_t gates = Q.bit((int)(jg & 0xFF)) | Q.bit((int)((jg >> 8) & 0xFF)) | Q.bit((int)((jg >> 16) & 0xFF)) | Q.bit((int)(jg >> 24));
-        uint32_t front = has ? Q.bit(jt) : 0u, seen = front;
-        int r = has ? -1 : 0;
-        POM_NOUNROLL
-        while (__any(r < 0)) {
-            if (r < 0) r = pom_quad_backward_level(Q, walk, gates, jg, front, seen);
-        }
-        const int got = __builtin_amdgcn_ds_bpermute((rank & 15) << 4, r);
-        if (need && (rank >> 4) == (base >> 4)) result = got;
-    }
-    return result;
-}
-
-/* SimpleAgent::act for the 64 agents of a wavefront (lane = agent, quad = env): the per-agent pieces of _Decide
- * (pom_policy_body.h) with the two searches run cooperatively in between.  actor: this lane's agent is asked for a move (a live
- * agent of an env that plays this tick).  Every lane of the wavefront calls this; returns the lane's Move (IDLE if not an actor). */
-template <class Store>
-__device__ __forceinline__ int pom_policy_wave(Store& st, const PomPolicyEnv& E, int member, uint32_t& m0, uint32_t& m1, bool actor, int draw,
-                                               const uint32_t* sets, int lane
-#if defined(POM_DIAG)
-                                               , long long& t_last, long long* t_acc
-#endif
-)
-{
-    PomSimplePolicy<Store> pol(st, E, member, m0, m1);
-#if defined(POM_DIAG)
-    pol.t_last = t_last;
-    for (int k = 0; k < POM_PP_N; k++) pol.t_acc[k] = 0;
-#endif
-    int in_danger = 0;
-    if (actor) in_danger = pol.begin();
-    int mv = POM_MOVE_IDLE;
-#if defined(POM_TRUNC)
-    if (st.trunc <= 1) return actor ? (pol.danger_ | pol.adj1_ | pol.near_ | pol.looping_ | pol.can_bomb_) & 1 : mv; /* diagnostic build: keep the predicates alive */
-#endif
-    __builtin_amdgcn_wave_barrier(); /* the sets of all 16 envs were written by their own lanes: no read of them may be scheduled earlier */
-    const int safe_cell = pom_coop_forward(actor && in_danger, pol.src_cell(), pol.danger_, sets, lane);
-    int target = -1, found = POM_MOVE_IDLE, flood = 0;
-    uint32_t g8 = 0xFFFFFFFFu;
-    if (actor) {
-        target = pol.pick_target(safe_cell);
-#if defined(POM_DIAG)
-        { const long long now_ = (long long)clock64(); pol.t_acc[POM_PP_TARGET] += now_ - pol.t_last; pol.t_last = now_; }
-#endif
-        flood = pol.path_begin(target, found, g8);
-    }
-#if defined(POM_TRUNC)
-    if (st.trunc <= 2) return target & 1;
-#endif
-    const int hit = pom_coop_backward(actor && flood, pol.src_cell(), target, g8, sets, lane);
-    if (actor) {
-        const int step = pol.path_end(target, found, hit);
-#if defined(POM_TRUNC)
-        if (st.trunc <= 3) return step;
-#endif
-        mv = pol.finish(step, draw);
-        m0 = pol.m0;
-        m1 = pol.m1;
-    }
-#if defined(POM_DIAG)
-    t_last = pol.t_last;
-    for (int k = POM_PP_PREDICATES; k <= POM_PP_TAIL; k++) t_acc[k] = pol.t_acc[k];
-#endif
-    return mv;
-}
-
-/* ------------------------------------------------------------------------------------------------
- * Observation export (row f4, pom_batch.h pom_batch_observe).  A wavefront takes a tile of 16 envs into LDS as the tick does,
- * then env by env: zero a 1936-byte staging area, scatter one byte per cell / bomb (each cell sets exactly one
- * of the planes 0..11), and stream the area out — for uint8 global views a straight 16-byte copy, fully coalesced; other
- * element types and the per-agent plane order take runs of 4 bytes through a byte funnel, convert and store 4 elements.  HBM-write-bound: 1936 B x elements per env.
- * ------------------------------------------------------------------------------------------- */
-/* Envs staged at a time for the 16 planes (template parameter PE below): the export kernel stages two (9 KB of LDS per wavefront, 18 per
- * CU; 992 + 544 + 279 instructions per wavefront against 1,248 + 738 + 385 with one, alone 23.7 -> 23.1 us: a pass's fixed work — the
- * queue slots' phases keep 20 lanes busy per env — is paid half as often), the step kernel's fused export one (two cost it 0.5 us:
- * it sits at its register and LDS limits); four needed 15 KB and ran 25 % slower. */
-enum { OBS_ENV_BYTES = POM_OBS_PLANES * POM_CELLS, OBS_PASS_ENVS_ALONE = 2, OBS_PASS_ENVS_FUSED = 1 };
-static_assert(OBS_ENV_BYTES % 16 == 0, "an env's planes are a whole number of 16-byte stores");
-
-struct ObserveParams {
-    const uint32_t* state;
-    int64_t n, n_pad, block0;
-    void* planes;
-    int32_t* agent_attrs;
-    int32_t* env_attrs;
-    int32_t dtype, per_agent;
-    /* the fogged views (VIEW instantiations only: pom_batch.h PomViewSpec) */
-    int32_t* viewer_attrs;
-    int32_t view_radius;
-};
-
-/* four staged bytes starting at byte offset `b` of the staging area (any alignment): two aligned dwords and a byte funnel */
-__device__ __forceinline__ uint32_t obs_bytes4(const uint32_t* stage_w, int b)
-{
-    const uint32_t lo = stage_w[b >> 2], hi = stage_w[(b >> 2) + 1];
-    return __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)(b & 3));
-}
-template <class T>
-__device__ __forceinline__ void obs_store4(T* dst, uint32_t bytes);
-template <>
-__device__ __forceinline__ void obs_store4<uint8_t>(uint8_t* dst, uint32_t bytes) { *reinterpret_cast<uint32_t*>(dst) = bytes; }
-template <>
-__device__ __forceinline__ void obs_store4<_Float16>(_Float16* dst, uint32_t bytes)
-{
-    typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-    *reinterpret_cast<half4*>(dst) = half4{(_Float16)(float)(bytes & 0xFF), (_Float16)(float)((bytes >> 8) & 0xFF),
-                                           (_Float16)(float)((bytes >> 16) & 0xFF), (_Float16)(float)(bytes >> 24)};
-}
-template <>
-__device__ __forceinline__ void obs_store4<float>(float* dst, uint32_t bytes)
-{
-    *reinterpret_cast<float4*>(dst) = make_float4((float)(bytes & 0xFF), (float)((bytes >> 8) & 0xFF), (float)((bytes >> 16) & 0xFF),
-                                                  (float)(bytes >> 24));
-}
-
-/* the generic way out of the staging area: element type T, `views` plane orders per env.  A lane takes 4 consecutive output
- * elements per round (one aligned 4 / 8 / 16-byte store): their source bytes are consecutive in the staging area unless the
- * group crosses a plane boundary (planes are 121 bytes, and the four agent planes are permuted per view), so it fetches the
- * run starting at its first element and the run ending at its last one and splices them at the boundary.  Plane and offset
- * advance incrementally (64 lanes x 4 elements = 2 planes + 14 per round): no division in the loop. */
-template <class T, int PE>
-__device__ __forceinline__ void obs_gather_out(const ObserveParams& p, const uint32_t* stage_w, int64_t e0, int lane)
-{
-    const int views = p.per_agent ? 4 : 1;
-    T* out = reinterpret_cast<T*>(p.planes);
-    for (int ei = 0; ei < PE && e0 + ei < p.n; ei++) {
-        for (int a = 0; a < views; a++) {
-            T* dst = out + ((e0 + ei) * views + a) * (int64_t)OBS_ENV_BYTES;
-            int pl = (4 * lane) / POM_CELLS, off = 4 * lane - pl * POM_CELLS; /* of the group's first element */
-            POM_NOUNROLL
-            for (int el = 4 * lane; el < OBS_ENV_BYTES; el += 256) {
-                const int src0 = (pl >= 8 && pl < 12) ? 8 + ((pl - 8 + a) & 3) : pl;
-                const int pn = pl + 1, src1 = (pn >= 8 && pn < 12) ? 8 + ((pn - 8 + a) & 3) : pn;
-                const int room = POM_CELLS - off; /* elements left in this plane, >= 1 */
-                const uint32_t head = obs_bytes4(stage_w, ei * OBS_ENV_BYTES + src0 * POM_CELLS + off);
-                /* the next plane's first bytes, placed where they belong in the group (only read when the group crosses) */
-                const uint32_t tail = obs_bytes4(stage_w, ei * OBS_ENV_BYTES + (room < 4 ? src1 * POM_CELLS - room : src0 * POM_CELLS + off));
-                const uint32_t keep = room >= 4 ? 0xFFFFFFFFu : (1u << (8 * room)) - 1u;
-                obs_store4<T>(dst + el, (head & keep) | (tail & ~keep));
-                off += 256 - 2 * POM_CELLS; /* 256 = 2 x 121 + 14 */
-                pl += 2;
-                if (off >= POM_CELLS) {
-                    off -= POM_CELLS;
-                    pl++;
-                }
-            }
-        }
-    }
-}
-
-/* Fogged views (pom_batch.h PomViewSpec).  What agent `id` of env column `ec` sees, as two bit sets in one word: bits 0..10 the
- * columns x with |x - x_v| <= r, bits 16..26 the rows likewise — the window is their product, and the board clips it (the shifts
- * drop what lies outside 0..10, whatever position the record holds).  No table in LDS: the staging area has no room for one. */
-__device__ __forceinline__ uint32_t obs_window(const uint32_t* tile, int ec, int id, int r)
-{
-    const int a0 = (int)tile[(POM_REC_AGENTS + 2 * id) * 16 + ec];
-    const uint32_t span = (2u << (2 * r)) - 1u; /* 2 r + 1 ones */
-    const int sx = ag_x(a0) - r, sy = ag_y(a0) - r;
-    const uint32_t cols = (sx >= 0 ? span << sx : span >> -sx) & 0x7FFu, rows = (sy >= 0 ? span << sy : span >> -sy) & 0x7FFu;
-    return cols | (rows << 16);
-}
-/* 0xFF in the bytes of four consecutive cells c .. c + 3 of a plane that window `w` shows; cells past the plane's last one are the
- * first cells of what follows it, seen through `w_next` (the next plane of the same view, or the first one of the next view).  The
- * four cells lie in at most two rows: those rows' column sets side by side, shifted down to the first cell. */
-__device__ __forceinline__ uint32_t obs_keep4(uint32_t w, uint32_t w_next, int c)
-{
-    const int y = (c * 745) >> 13, x = c - POM_N * y; /* c / 11 for c < 121 */
-    const bool last = y == POM_N - 1;
-    const uint32_t below = last ? w_next : w >> (y + 1);
-    const uint32_t row0 = ((w >> (16 + y)) & 1u) ? w & 0x7FFu : 0u, row1 = ((below >> 16) & 1u) ? (last ? w_next : w) & 0x7FFu : 0u;
-    const uint32_t bits = ((row0 | (row1 << POM_N)) >> x) & 15u;
-    return ((bits * 0x00204081u) & 0x01010101u) * 0xFFu; /* bit j -> byte j */
-}
-
-/* obs_gather_out for the fogged views: the same groups of 4 elements, the cells outside view a's window zeroed (planes 0..11 are
- * one-hot on every real cell: an all-zero cell is fog) */
-template <class T, int PE>
-__device__ __forceinline__ void obs_gather_out_view(const ObserveParams& p, const uint32_t* tile, const uint32_t* stage_w, int64_t e0, int ec0, int lane)
-{
-    T* out = reinterpret_cast<T*>(p.planes);
-    for (int ei = 0; ei < PE && e0 + ei < p.n; ei++) {
-        for (int a = 0; a < 4; a++) {
-            const uint32_t w = obs_window(tile, ec0 + ei, a, p.view_radius);
-            T* dst = out + ((e0 + ei) * 4 + a) * (int64_t)OBS_ENV_BYTES;
-            int pl = (4 * lane) / POM_CELLS, off = 4 * lane - pl * POM_CELLS; /* of the group's first element */
-            POM_NOUNROLL
-            for (int el = 4 * lane; el < OBS_ENV_BYTES; el += 256) {
-                const int src0 = (pl >= 8 && pl < 12) ? 8 + ((pl - 8 + a) & 3) : pl;
-                const int pn = pl + 1, src1 = (pn >= 8 && pn < 12) ? 8 + ((pn - 8 + a) & 3) : pn;
-                const int room = POM_CELLS - off; /* elements left in this plane, >= 1 */
-                const uint32_t head = obs_bytes4(stage_w, ei * OBS_ENV_BYTES + src0 * POM_CELLS + off);
-                const uint32_t tail = obs_bytes4(stage_w, ei * OBS_ENV_BYTES + (room < 4 ? src1 * POM_CELLS - room : src0 * POM_CELLS + off));
-                const uint32_t keep = room >= 4 ? 0xFFFFFFFFu : (1u << (8 * room)) - 1u;
-                obs_store4<T>(dst + el, ((head & keep) | (tail & ~keep)) & obs_keep4(w, w, off));
-                off += 256 - 2 * POM_CELLS; /* 256 = 2 x 121 + 14 */
-                pl += 2;
-                if (off >= POM_CELLS) {
-                    off -= POM_CELLS;
-                    pl++;
-                }
-            }
-        }
-    }
-}
-
-/* the planes and attributes of one tile's 16 envs, from the tile as it lies in LDS ([row][16] dwords); `stage`: obs_stage_vecs(PE)
- * uint4 of LDS.  Called by the whole wavefront (one wavefront per workgroup: the barriers only order its own LDS traffic). */
-enum {
-    OBS_CODE_PLANES = 5,                              /* POM_OBS_CODES: board codes, bomb strength / life / direction, flame life */
-    OBS_CODE_ENV_BYTES = OBS_CODE_PLANES * POM_CELLS, /* 605 */
-    OBS_CODE_PASS_ENVS = 4,                           /* 4 x 605 B = 605 dwords: a pass's output starts on a dword */
-    OBS_CODE_SHIFT_MAX = 12,                          /* a pass is staged 0 / 4 / 8 / 12 bytes into the area: where its output lies relative to a 16-byte line */
-    OBS_CODE_STAGE_VECS = (OBS_CODE_PASS_ENVS * OBS_CODE_ENV_BYTES + OBS_CODE_SHIFT_MAX + 8 + 15) / 16,
-};
-/* uint4s of LDS the export needs with PE envs of planes per pass (+ 16 B: the byte funnel reads one dword past a run) */
-constexpr int obs_stage_vecs(int pe)
-{
-    return pe * OBS_ENV_BYTES / 16 + 1 > OBS_CODE_STAGE_VECS ? pe * OBS_ENV_BYTES / 16 + 1 : (int)OBS_CODE_STAGE_VECS;
-}
-static_assert(POM_OBS_CODE_PLANES == OBS_CODE_PLANES, "pom_batch.h");
-
-/* One pass of the export: E envs of the tile (q-th group of E) into the staging area — the 16 planes of an env (CODES = false,
- * E = 1) or the five code planes of four envs (CODES = true).  "The first live bomb on a cell speaks for it" and "the first live
- * flame spawned at a flame cell's FLAME_ID" (State::GetBomb's order, bboard.cpp:277-287; bboard.hpp:98-101) are answered without
- * searching the queues per cell: a lane per queue slot writes its key (offset in the queue + 1) to its cell in a plane of the
- * staging area that is not needed yet — the bombs into the strength plane, the flames into the bomb-direction plane — and lowers
- * it until the smallest key of a cell has won; a flame cell then reads its flame with one look-up, a bomb slot that finds its own
- * key is the first on its cell.  The flames' keys are wiped before the bombs write their three planes.  (Round 4; until then every
- * flame cell walked the flame queue — a wavefront paid its longest queue on nearly every group of 64 cells, three quarters of the
- * kernel's instructions.) */
-/* Between the phases of the export: "the other lanes' LDS writes so far are visible from here on".  One wavefront per workgroup and
- * the LDS serves a wavefront's instructions in order, so the hardware has nothing to wait for; the compiler must not move LDS
- * accesses across.  (Until round 4 this was __syncthreads(), whose s_waitcnt vmcnt(0) made every pass wait for its own global
- * stores to be acknowledged: 16 passes x the store latency — three quarters of the wavefront's life, profiles/r04_observe_pmc.txt.) */
-__device__ __forceinline__ void obs_lds_order() { asm volatile("" ::: "memory"); }
-
-template <bool CODES, int PE>
-__device__ __forceinline__ void pom_observe_stage(const uint32_t* tile, uint4* stage, int q, int lane, int shift = 0)
-{
-    constexpr int E = CODES ? (int)OBS_CODE_PASS_ENVS : PE, EB = CODES ? (int)OBS_CODE_ENV_BYTES : (int)OBS_ENV_BYTES;
-    constexpr int P_STRENGTH = CODES ? 1 : 12, P_DIR = P_STRENGTH + 2, P_FLAME = P_STRENGTH + 3;
-    constexpr int VECS = (E * EB + (CODES ? (int)OBS_CODE_SHIFT_MAX + 8 : 0) + 15) / 16, SLOT_IT = (E * POM_Q + 63) / 64;
-    static_assert((E & (E - 1)) == 0, "lanes per env");
-    static_assert(obs_stage_vecs(PE) * 16 >= E * EB + 8 + (CODES ? (int)OBS_CODE_SHIFT_MAX : 0), "eight bytes behind the planes take the writes of lanes that have nothing to write");
-    /* The phases below are written without branches where a lane-varying `if` would do (hipcc makes exec-mask forests of those, and
-     * the kernel is bound by the instructions it issues, scalar ones included): a lane with nothing to write writes to `dump`. */
-    const int dump = E * EB + (lane & 7);
-    uint8_t* stage_b = reinterpret_cast<uint8_t*>(stage) + shift;
-#pragma unroll
-    for (int i = 0; i < (VECS + 63) / 64; i++)
-        if (64 * i + 63 < VECS || lane + 64 * i < VECS) stage[lane + 64 * i] = make_uint4(0, 0, 0, 0);
-    obs_lds_order();
-    /* the queue slots' keys.  Code planes: lane -> (env lane / 16, slot lane % 16) of the pass's four envs; the slots 16 .. 19 get a second
-     * round only if some queue of the pass is that long (round 5; until then two full rounds over 80 slots every pass) */
-    constexpr int SLOT_ROUNDS = CODES ? 2 : 1;
-    static_assert(!CODES || (E == 4 && POM_Q == 20), "the slot rounds of the code planes");
-    static_assert(CODES || SLOT_IT == 1, "an env's slots are one round");
-    auto slot = [&](int i, int& ei, int& k, int& ok) {
-        if (CODES) {
-            ei = i == 0 ? lane >> 4 : (lane >> 2) & 3;
-            k = i == 0 ? lane & 15 : 16 + (lane & 3);
-            ok = i == 0 ? 1 : (int)(lane < 16);
-        } else {
-            ei = E == 1 ? 0 : (lane * 3277) >> 16; /* lane / 20 */
-            k = lane - ei * POM_Q;
-            ok = (int)(lane < E * POM_Q);
-            ei = ok ? ei : 0;
-        }
-    };
-    int key_f[SLOT_ROUNDS], key_b[SLOT_ROUNDS], bomb[SLOT_ROUNDS]; /* where a live slot's key goes (byte offset in the staging area; `dump`: not live) */
-    bool tail = false; /* the second round is needed */
-#pragma unroll
-    for (int i = 0; i < SLOT_ROUNDS; i++) {
-        key_f[i] = key_b[i] = dump;
-        bomb[i] = 0;
-        if (i == 0 || tail) {
-            int ei, k, ok;
-            slot(i, ei, k, ok);
-            const int ec = q * E + ei, kk = ok ? k : 0;
-            /* the queues' indices and counts: the top bytes of four agent words (pom_packed.h) */
-            const int bIdx = (int)(tile[(POM_REC_AGENTS + 2) * 16 + ec] >> 24), bCnt = (int)(tile[(POM_REC_AGENTS + 4) * 16 + ec] >> 24),
-                      fIdx = (int)(tile[(POM_REC_AGENTS + 6) * 16 + ec] >> 24), fCnt = (int)(tile[(POM_REC_AGENTS + 1) * 16 + ec] >> 24);
-            if (CODES && i == 0) tail = __any((int)(bCnt > 16) | (int)(fCnt > 16)) != 0;
-            const uint32_t f = tile[(POM_REC_FLAMES + wrap20(fIdx + kk)) * 16 + ec];
-            const int b = (int)tile[(POM_REC_BOMBS + wrap20(bIdx + kk)) * 16 + ec];
-            bomb[i] = b;
-            const int fc = (int)(f & 0xFF) + POM_N * (int)((f >> 8) & 0xFF);
-            key_f[i] = (ok & (int)(k < fCnt) & (int)(fc < POM_CELLS)) ? ei * EB + P_DIR * POM_CELLS + fc : dump;
-            key_b[i] = (ok & (int)(k < bCnt) & (int)(pb_x(b) < POM_N) & (int)(pb_y(b) < POM_N)) ? ei * EB + P_STRENGTH * POM_CELLS + pb_y(b) * POM_N + pb_x(b) : dump;
-            stage_b[key_f[i]] = (uint8_t)(k + 1);
-            stage_b[key_b[i]] = (uint8_t)(k + 1);
-        }
-    }
-    POM_NOUNROLL
-    for (;;) { /* several slots on one cell: one of their writes landed — the smaller keys write again until the smallest stands */
-        obs_lds_order();
-        int low_f[SLOT_ROUNDS], low_b[SLOT_ROUNDS], again = 0;
-#pragma unroll
-        for (int i = 0; i < SLOT_ROUNDS; i++) {
-            low_f[i] = low_b[i] = 0;
-            if (i == 0 || tail) {
-                int ei, k, ok;
-                slot(i, ei, k, ok);
-                low_f[i] = (int)(key_f[i] != dump) & (int)(stage_b[key_f[i]] > k + 1);
-                low_b[i] = (int)(key_b[i] != dump) & (int)(stage_b[key_b[i]] > k + 1);
-                again |= low_f[i] | low_b[i];
-            }
-        }
-        if (!__any(again)) break; /* (the usual case: no two live slots on one cell) */
-        for (int i = 0; i < SLOT_ROUNDS; i++) { /* (one or two rounds: unrolled without being asked) */
-            if (i == 0 || tail) {
-                int ei, k, ok;
-                slot(i, ei, k, ok);
-                stage_b[low_f[i] ? key_f[i] : dump] = (uint8_t)(k + 1);
-                stage_b[low_b[i] ? key_b[i] : dump] = (uint8_t)(k + 1);
-            }
-        }
-    }
-    obs_lds_order();
-    if constexpr (CODES) {
-        /* The code planes, a pass = four envs: with the board laid out by cell the four envs' codes of cell c ARE one dword of the tile
-         * (bytes 4q .. 4q + 3 of the cell's 16), so a lane takes a cell and turns four codes into four Item numbers at once (round 5;
-         * until then a lane took two cells of one env, ~22 instructions per cell): the 16-entry table (0 passage, 1 rigid, 3 Item::BOMB,
-         * 6 / 7 / 8 the power-ups, 2 wood with any flag, 10 + i agent i — the small numbers of the reference's Item enum, bboard.hpp:54-71)
-         * is two byte permutes on the codes' low three bits, chosen between by bit 3; every code from 15 up is a flame (4). */
-        static_assert(E == 4, "a pass of the code planes is the four envs that share a dword of every cell");
-        const int q4 = 4 * q;
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            const int c = lane + 64 * i;
-            if (i == 0 || c < POM_CELLS) {
-                const uint32_t d = tile[c * 4 + q];
-                const uint32_t flame = (((d & 0x7F7F7F7Fu) + 0x71717171u) | d) & 0x80808080u; /* the bytes >= 15 */
-                const uint32_t lo3 = d & 0x07070707u;
-                const uint32_t t_lo = __builtin_amdgcn_perm(0x02020807u, 0x06030100u, lo3); /* codes 0 .. 7 */
-                const uint32_t t_hi = __builtin_amdgcn_perm(0x040D0C0Bu, 0x0A020202u, lo3); /* codes 8 .. 14 */
-                const uint32_t b3 = (d >> 3) & 0x01010101u, m3 = (b3 << 8) - b3;            /* 0xFF in the bytes with bit 3 */
-                const uint32_t f1 = flame >> 7, mf = (f1 << 8) - f1;
-                uint32_t v = (t_hi & m3) | (t_lo & ~m3);
-                v = (0x04040404u & mf) | (v & ~mf);
-                stage_b[c] = (uint8_t)v;
-                stage_b[EB + c] = (uint8_t)(v >> 8);
-                stage_b[2 * EB + c] = (uint8_t)(v >> 16);
-                stage_b[3 * EB + c] = (uint8_t)(v >> 24);
-                /* the flame cells among the four: the life of the first live flame spawned at the cell's FLAME_ID (key table above) */
-                uint32_t todo = flame;
-                POM_NOUNROLL
-                while (todo) {
-                    const int ei = __builtin_ctz(todo) >> 3, ec = q4 + ei;
-                    todo &= todo - 1u;
-                    const int code = (int)((d >> (8 * ei)) & 0xFFu);
-                    int origin = code - POM_C_FLAME;
-                    if (code >= POM_C_FLAGGED) origin = pom_flame_origin(code, c); /* (a burnt wood with a power-up under it: rare) */
-                    const int key = stage_b[ei * EB + P_DIR * POM_CELLS + origin];
-                    const int fIdx = (int)(tile[(POM_REC_AGENTS + 6) * 16 + ec] >> 24); /* flames.index: the top byte of agent 3's first word */
-                    const int tl = pom_sext8(tile[(POM_REC_FLAMES + wrap20(fIdx + (key ? key - 1 : 0))) * 16 + ec] >> 16);
-                    stage_b[ei * EB + P_FLAME * POM_CELLS + c] = (uint8_t)((int)(key != 0) & (int)(tl > 0) ? tl : 0);
-                }
-            }
-        }
-    } else
-    /* cells: a byte each into the plane its code names (or its Item number into the board plane); flame cells look their flame up.  A lane
-     * takes half a dword of the board — two cells — of one env per round: lane -> (env of the pass, unit of two cells), so that every
-     * address is a base plus a constant */
-    {
-        constexpr int UNITS = (POM_CELLS + 1) / 2; /* 61 */
-        constexpr int LPE = 64 / E, ROW_IT = (UNITS + LPE - 1) / LPE; /* lanes per env; rounds over the 61 two-cell units */
-        const int ei = E == 1 ? 0 : lane & (E - 1), j = E == 1 ? lane : lane / E, ec = q * E + ei;
-        const int fIdx = (int)(tile[(POM_REC_AGENTS + 6) * 16 + ec] >> 24); /* flames.index: the top byte of agent 3's first word */
-        auto put = [&](int code, int c, int ok) { /* the cell's byte; returns whether the cell is a flame */
-            /* What the cell's code (pom_packed.h: 0 passage, 1 rigid, 2 bomb, 3..5 power-ups, 6..10 wood, 11..14 agents, 15.. flames) sets.
-             * The 16 planes: passage 0, rigid 1, wood (any flag) 2, Item::BOMB 3, flames 4, the three power-ups 5, 6, 7, agent i 8 + i.
-             * POM_OBS_CODES: the small numbers of the reference's Item enum (bboard.hpp:54-71; the Python Pommerman board uses the same
-             * ones) — 0 passage, 1 rigid, 2 wood, 3 bomb, 4 flames, 6 extra-bomb, 7 incr-range, 8 kick, 10 + i agent i.  One table, a
-             * nibble per code, every flame code reading entry 15. */
-            const int k = code < 15 ? code : 15;
-            const int v = (int)(((CODES ? 0x4DCBA22222876310ull : 0x4BA9822222765310ull) >> (4 * k)) & 15u);
-            if (CODES) stage_b[ok ? ei * EB + c : dump] = (uint8_t)v;
-            else stage_b[ok ? ei * EB + v * POM_CELLS + c : dump] = 1;
-            return ok & pc_is_flame(code);
-        };
-        auto life = [&](int code, int c, int is_flame) { /* unconditional: a cell that is no flame looks at its own (zero) byte */
-            int origin = code - POM_C_FLAME; /* FLAME_ID: the cell the flame was spawned at */
-            if (code >= POM_C_FLAGGED) origin = pom_flame_origin(code, c); /* (a burnt wood with a power-up under it: rare) */
-            const int key = stage_b[is_flame ? ei * EB + P_DIR * POM_CELLS + origin : ei * EB + P_FLAME * POM_CELLS + c];
-            const int tl = pom_sext8(tile[(POM_REC_FLAMES + wrap20(fIdx + (key ? key - 1 : 0))) * 16 + ec] >> 16);
-            stage_b[is_flame ? ei * EB + P_FLAME * POM_CELLS + c : dump] = (uint8_t)((int)(key != 0) & (int)(tl > 0) ? tl : 0);
-        };
-#pragma unroll
-        for (int i = 0; i < ROW_IT; i++) {
-            const int r = j + LPE * i;
-            const int ok = (LPE * i + LPE - 1 < UNITS) | (int)(r < UNITS); /* (a lane past the board reads some other row of the tile) */
-            const uint8_t* tile_b = reinterpret_cast<const uint8_t*>(tile); /* the board by cell: cell c of env ec at byte c * 16 + ec */
-            const int lo = tile_b[(2 * r) * 16 + ec], hi = tile_b[(2 * r + 1) * 16 + ec];
-            const int f0 = put(lo, 2 * r, ok);
-            const int f1 = put(hi, 2 * r + 1, ok & (int)(r < UNITS - 1)); /* the board's last unit holds one cell */
-            if (f0 | f1) {
-                life(lo, 2 * r, f0);
-                life(hi, 2 * r + 1, f1);
-            }
-        }
-    }
-    int first[SLOT_ROUNDS];
-#pragma unroll
-    for (int i = 0; i < SLOT_ROUNDS; i++) {
-        first[i] = 0;
-        if (i == 0 || tail) {
-            int ei, k, ok;
-            slot(i, ei, k, ok);
-            first[i] = (int)(key_b[i] != dump) & (int)(stage_b[key_b[i]] == k + 1);
-        }
-    }
-    obs_lds_order();
-#pragma unroll
-    for (int i = 0; i < SLOT_ROUNDS; i++)
-        if (i == 0 || tail) stage_b[key_f[i]] = 0; /* the direction plane is the bombs' again */
-    obs_lds_order();
-#pragma unroll
-    for (int i = 0; i < SLOT_ROUNDS; i++) {
-        if (i == 0 || tail) {
-            stage_b[first[i] ? key_b[i] : dump] = (uint8_t)pb_strength(bomb[i]);
-            stage_b[first[i] ? key_b[i] + 1 * POM_CELLS : dump] = (uint8_t)pb_time(bomb[i]);
-            stage_b[first[i] ? key_b[i] + 2 * POM_CELLS : dump] = (uint8_t)pb_dir(bomb[i]);
-        }
-    }
-    obs_lds_order();
-}
-
-/* The compact layout (POM_OBS_CODES): uint8 [n][5][11][11] — 605 bytes per env instead of 1,936, for training loops that expand
- * the board codes themselves (an embedding look-up).  Four envs are staged at a time (2,420 B, a whole number of dwords) and leave
- * as dword stores; the batch's last bytes, where n is no multiple of 4, leave byte by byte. */
-__device__ __forceinline__ void pom_observe_tile_codes(const ObserveParams& p, const uint32_t* tile, uint4* stage, int64_t tile_id, int lane)
-{
-    /* A tile's 16 x 605 bytes start on a 16-byte line if the array does, and pass q's 2,420 bytes 4 q bytes into one: staged that many
-     * bytes into the area, the pass leaves as 16-byte stores of aligned LDS reads (round 5; until then 10 rounds of dword stores), the
-     * up to three dwords before the first and after the last whole line one by one */
-    const bool lines = ((reinterpret_cast<uintptr_t>(p.planes) + (uintptr_t)(tile_id * 16 * OBS_CODE_ENV_BYTES)) & 15u) == 0u;
-    for (int q = 0; q < 16 / OBS_CODE_PASS_ENVS; q++) {
-        const int64_t e0 = tile_id * 16 + q * OBS_CODE_PASS_ENVS;
-        if (e0 >= p.n) break;
-        const int64_t left = p.n - e0;
-        const bool fast = lines && left >= OBS_CODE_PASS_ENVS;
-        const int shift = fast ? 4 * q : 0;
-        pom_observe_stage<true, 1>(tile, stage, q, lane, shift);
-        uint8_t* out_b = reinterpret_cast<uint8_t*>(p.planes) + e0 * OBS_CODE_ENV_BYTES; /* e0 is a multiple of 4: on a dword */
-        const uint32_t* stage_w = reinterpret_cast<const uint32_t*>(stage);
-        if (fast) {
-            constexpr int DW = OBS_CODE_PASS_ENVS * OBS_CODE_ENV_BYTES / 4; /* 605 */
-            uint4* out_v = reinterpret_cast<uint4*>(out_b - shift);
-            uint32_t* out_w = reinterpret_cast<uint32_t*>(out_b - shift);
-            const int beg = q, end = q + DW, v0 = (beg + 3) >> 2, v1 = end >> 2; /* dwords of the area; whole lines [v0, v1) */
-#pragma unroll
-            for (int i = 0; i < (DW / 4 + 1 + 63) / 64; i++) {
-                const int v = lane + 64 * i;
-                if (v >= v0 && v < v1) out_v[v] = stage[v];
-            }
-            const int dw = lane < 4 ? lane : 4 * v1 + lane - 4;
-            if (lane < 4 ? (dw >= beg && dw < 4 * v0) : (lane < 8 && dw < end)) out_w[dw] = stage_w[dw];
-        } else {
-            const uint8_t* stage_b = reinterpret_cast<const uint8_t*>(stage);
-            const int bytes = (int)(left < OBS_CODE_PASS_ENVS ? left : OBS_CODE_PASS_ENVS) * OBS_CODE_ENV_BYTES;
-            uint32_t* out_w = reinterpret_cast<uint32_t*>(out_b);
-#pragma unroll
-            for (int i = 0; i < (OBS_CODE_PASS_ENVS * OBS_CODE_ENV_BYTES / 4 + 63) / 64; i++) {
-                const int idx = lane + 64 * i;
-                if (idx < (bytes >> 2)) out_w[idx] = stage_w[idx];
-            }
-            if (lane < (bytes & 3)) out_b[(bytes & ~3) + lane] = stage_b[(bytes & ~3) + lane];
-        }
-        obs_lds_order();
-    }
-}
-
-/* The code planes as four fogged views per env: uint8 [n][4][5][11][11].  The same passes of four envs, staged once; an env's four
- * views are 4 x 605 B = 605 dwords, so every env starts on a dword and leaves as dword stores, 64 consecutive ones per round.  Output
- * dword i of an env holds bytes 4 i .. 4 i + 3 of (view, plane, cell) in that order: view and plane are the same five staged planes
- * read round and round (a dword that ends a view begins the next one with the env's first staged bytes), the cells outside the
- * viewer's window read Item::FOG in the board plane and 0 in the others.  View, plane and cell advance incrementally (64 lanes x 4 bytes
- * = 2 planes + 14 cells per round): no division in the loop. */
-__device__ __forceinline__ void pom_observe_tile_codes_view(const ObserveParams& p, const uint32_t* tile, uint4* stage, int64_t tile_id, int lane)
-{
-    constexpr int DW = OBS_CODE_ENV_BYTES; /* dwords of an env's four views */
-    for (int q = 0; q < 16 / OBS_CODE_PASS_ENVS; q++) {
-        const int64_t e0 = tile_id * 16 + q * OBS_CODE_PASS_ENVS;
-        if (e0 >= p.n) break;
-        pom_observe_stage<true, 1>(tile, stage, q, lane);
-        const uint32_t* stage_w = reinterpret_cast<const uint32_t*>(stage);
-        for (int ei = 0; ei < OBS_CODE_PASS_ENVS && e0 + ei < p.n; ei++) {
-            const int ec = q * OBS_CODE_PASS_ENVS + ei;
-            const uint32_t w0 = obs_window(tile, ec, 0, p.view_radius), w1 = obs_window(tile, ec, 1, p.view_radius),
-                           w2 = obs_window(tile, ec, 2, p.view_radius), w3 = obs_window(tile, ec, 3, p.view_radius);
-            uint32_t* out_w = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(p.planes) + (e0 + ei) * (int64_t)(4 * OBS_CODE_ENV_BYTES));
-            const uint32_t first4 = obs_bytes4(stage_w, ei * OBS_CODE_ENV_BYTES); /* what follows a view's last byte */
-            int v = 0, pl = (4 * lane) / POM_CELLS, off = 4 * lane - pl * POM_CELLS; /* of the dword's first byte */
-            POM_NOUNROLL
-            for (int i = lane; i < DW; i += 64) {
-                const uint32_t w = v == 0 ? w0 : v == 1 ? w1 : v == 2 ? w2 : w3, w_after = v == 0 ? w1 : v == 1 ? w2 : w3;
-                const bool ends_view = pl == OBS_CODE_PLANES - 1;
-                const int room = POM_CELLS - off; /* bytes left in this plane, >= 1 */
-                const uint32_t low = room >= 4 ? 0xFFFFFFFFu : (1u << (8 * room)) - 1u; /* the bytes of this plane */
-                const uint32_t head = obs_bytes4(stage_w, ei * OBS_CODE_ENV_BYTES + pl * POM_CELLS + off);
-                const uint32_t bytes = ends_view ? (head & low) | ((first4 << (8 * (room & 3))) & ~low) : head;
-                const uint32_t keep = obs_keep4(w, ends_view ? w_after : w, off);
-                const uint32_t board = pl == 0 ? low : ends_view ? ~low : 0u; /* the bytes that belong to a board plane */
-                out_w[i] = (bytes & keep) | (0x05050505u & board & ~keep);
-                off += 256 - 2 * POM_CELLS; /* 256 = 2 x 121 + 14 */
-                pl += 2;
-                if (off >= POM_CELLS) {
-                    off -= POM_CELLS;
-                    pl++;
-                }
-                if (pl >= OBS_CODE_PLANES) {
-                    pl -= OBS_CODE_PLANES;
-                    v++;
-                }
-            }
-        }
-        obs_lds_order();
-    }
-}
-
-template <int PE, bool VIEW = false>
-__device__ __forceinline__ void pom_observe_tile(const ObserveParams& p, const uint32_t* tile, uint4* stage, int64_t tile_id, int lane)
-{
-    static_assert(PE * POM_Q <= 64 && 16 % PE == 0, "a pass's queue slots are one round of lanes");
-    if (VIEW) {
-        /* the four agents' fogged views (PomViewSpec): staged as below, masked on the way out */
-        if (p.dtype == POM_OBS_CODES) pom_observe_tile_codes_view(p, tile, stage, tile_id, lane);
-        else
-        for (int q = 0; q < 16 / PE; q++) {
-            const int64_t e0 = tile_id * 16 + q * PE;
-            if (e0 >= p.n) break;
-            pom_observe_stage<false, PE>(tile, stage, q, lane);
-            if (p.dtype == POM_OBS_U8) obs_gather_out_view<uint8_t, PE>(p, tile, reinterpret_cast<const uint32_t*>(stage), e0, q * PE, lane);
-            else if (p.dtype == POM_OBS_F16) obs_gather_out_view<_Float16, PE>(p, tile, reinterpret_cast<const uint32_t*>(stage), e0, q * PE, lane);
-            else obs_gather_out_view<float, PE>(p, tile, reinterpret_cast<const uint32_t*>(stage), e0, q * PE, lane);
-            obs_lds_order();
-        }
-        /* viewer_attrs: lane -> (env lane/4, viewer lane%4), 48 contiguous bytes each: the viewer's own row of agent_attrs, who else is
-         * alive — the three others in the order of the rotated agent planes — and the time step */
-        const int ec = lane >> 2, id = lane & 3;
-        const int64_t e = tile_id * 16 + ec;
-        if (e < p.n && p.viewer_attrs) {
-            const uint32_t a0 = tile[(POM_REC_AGENTS + 2 * id) * 16 + ec], a1 = tile[(POM_REC_AGENTS + 2 * id + 1) * 16 + ec];
-            const int bc = ag_bombcount((int)a0), mx = ag_max_bombs((int)a1);
-            int alive[3];
-#pragma unroll
-            for (int k = 1; k < 4; k++) alive[k - 1] = !ag_dead((int)tile[(POM_REC_AGENTS + 2 * ((id + k) & 3)) * 16 + ec]);
-            int4* o = reinterpret_cast<int4*>(p.viewer_attrs + (e * 4 + id) * POM_OBS_VIEWER_ATTRS);
-            o[0] = make_int4(ag_x((int)a0), ag_y((int)a0), !ag_dead((int)a0), mx - bc);
-            o[1] = make_int4(bc, mx, ag_strength((int)a1), ag_kick((int)a0));
-            o[2] = make_int4(alive[0], alive[1], alive[2], (int)tile[POM_REC_TIMESTEP * 16 + ec]);
-        }
-    } else
-    if (p.dtype == POM_OBS_CODES) pom_observe_tile_codes(p, tile, stage, tile_id, lane);
-    else
-    for (int q = 0; q < 16 / PE; q++) {
-        const int64_t e0 = tile_id * 16 + q * PE;
-        if (e0 >= p.n) break;
-        const int64_t left = p.n - e0;
-        const int VECS = (int)(left < PE ? left : PE) * (OBS_ENV_BYTES / 16); /* 121 per env */
-        constexpr int VECS_MAX = PE * OBS_ENV_BYTES / 16;
-        pom_observe_stage<false, PE>(tile, stage, q, lane);
-        if (p.dtype == POM_OBS_U8 && !p.per_agent) {
-            uint4* out = reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(p.planes) + e0 * OBS_ENV_BYTES);
-#pragma unroll
-            for (int i = 0; i < (VECS_MAX + 63) / 64; i++) {
-                const int idx = lane + 64 * i;
-                if (idx < VECS) out[idx] = stage[idx]; /* (non-temporal stores: 45 us against 40 fused) */
-            }
-        } else if (p.dtype == POM_OBS_U8) {
-            obs_gather_out<uint8_t, PE>(p, reinterpret_cast<const uint32_t*>(stage), e0, lane);
-        } else if (p.dtype == POM_OBS_F16) {
-            obs_gather_out<_Float16, PE>(p, reinterpret_cast<const uint32_t*>(stage), e0, lane);
-        } else {
-            obs_gather_out<float, PE>(p, reinterpret_cast<const uint32_t*>(stage), e0, lane);
-        }
-        obs_lds_order();
-    }
-    /* attributes: lane -> (env lane/4, agent lane%4), 32 contiguous bytes each */
-    const int ec = lane >> 2, id = lane & 3;
-    const int64_t e = tile_id * 16 + ec;
-    if (!VIEW && e < p.n && p.agent_attrs) {
-        const uint32_t a0 = tile[(POM_REC_AGENTS + 2 * id) * 16 + ec], a1 = tile[(POM_REC_AGENTS + 2 * id + 1) * 16 + ec];
-        const int bc = ag_bombcount((int)a0), mx = ag_max_bombs((int)a1);
-        int4* o = reinterpret_cast<int4*>(p.agent_attrs + (e * 4 + id) * POM_OBS_AGENT_ATTRS);
-        o[0] = make_int4(ag_x((int)a0), ag_y((int)a0), !ag_dead((int)a0), mx - bc);
-        o[1] = make_int4(bc, mx, ag_strength((int)a1), ag_kick((int)a0));
-    }
-    if (lane < 16 && tile_id * 16 + lane < p.n && p.env_attrs) {
-        const uint32_t m = pom_rec_meta(tile + lane, 16), st = (pom_rec_meta2(tile + lane, 16) >> 8) & 0xFF;
-        const int status = (int)((st & POM_ST_DONE) ? 1 : 0) | (int)((st & POM_ST_DRAW) ? 2 : 0) | (int)((st & POM_ST_TIMEOUT) ? 4 : 0) |
-                           (int)((st & POM_ST_RESTARTED) ? 8 : 0);
-        reinterpret_cast<int4*>(p.env_attrs)[tile_id * 16 + lane] =
-            make_int4((int)tile[POM_REC_TIMESTEP * 16 + lane], pom_sext8(m), status, (int)((st >> POM_ST_WINNER_SHIFT) & 7) - 1);
-    }
-}
-
 /* occupancy target of the quad kernel: 4 wavefronts per SIMD = 16 per CU = every one of 65,536 envs' wavefronts resident at
  * once.  The kernel needs 120-128 VGPRs; the target keeps the compiler from drifting past 128 (which would drop a whole
  * round's worth of wavefronts to a second round) — at the price of a spill or two if it ever has to.  History: an early
@@ -1176,124 +102,6 @@ __device__ __forceinline__ void pom_observe_tile(const ObserveParams& p, const u
  * its own stores have arrived.  A launch then no longer lasts as long as its slowest wavefront: the next launch's
  * wavefronts start on the tiles that are ready. */
 extern "C" __device__ uint64_t pom_dispatch_id(void) __asm("llvm.amdgcn.dispatch.id"); /* the AQL packet's index in its queue */
-/* how long a wavefront waits for the visit before its own before it gives up (it must never hang the device): wall-clock time, so
- * that a holder descheduled for a while (several processes time-slicing one GPU, a debugger) is waited for; a give-up poisons the
- * tile and the host replays its ticks after the next join — slow, never wrong (pom_runtime.h chain_settle) */
-enum { POM_CHAIN_WAIT_LIMIT_US = 2000000 };
-#ifndef POM_CHAIN_WORD_STRIDE
-#define POM_CHAIN_WORD_STRIDE 16 /* 64-bit words between the ticket words of neighbouring tiles: a 128-byte line each (10.28 - 10.30 us
-                                    per step against 10.41 - 10.48 with the words packed: atomics of neighbouring tiles do not queue on one line) */
-#endif
-
-/* ---- a chained launch's visit of a tile (pom_chain.h): the hand-off both the CHAIN instantiations of pom_step_kernel and the
- * hand-off litmus (pom_chain_litmus_kernel) go through ------------------------------------------------------------------------- */
-struct PomChainVisit {
-    int32_t dist = 0;            /* how many visits after the launch's chain_seq0 this one is: picks the tick (and the tape's tick) */
-    unsigned long long done = 0; /* what the wavefront adds to the tile's word when its stores have arrived */
-#if defined(POM_CHAIN_DIAG)
-    long long t0 = 0, t1 = 0, t2 = 0, rt0 = 0;
-    int polls = 0;
-    uint32_t visit = 0;
-#endif
-};
-/* which XCD this workgroup runs on (0..7; >= 8: not the machine this was written for) */
-__device__ __forceinline__ uint32_t pom_chain_xcd()
-{
-    uint32_t x;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(x));
-    return x & 0xFu;
-}
-/* Take a ticket for the tile's word and wait for the visit before it.  true: the tile is this wavefront's to play — its record, as
- * the previous visit stored it, may be loaded NOW (past the vector cache: sc1).  false: nothing may be touched (the tile is, or
- * has just been, poisoned; the flag word says why). */
-__device__ __forceinline__ bool pom_chain_enter(unsigned long long* word, uint32_t chain_xcd, uint32_t chain_seq0, uint32_t tape_len, uint64_t wait_limit,
-                                                uint32_t* err, int lane, PomChainVisit& v)
-{
-    const uint32_t xcd = chain_xcd + 1u;
-#if defined(POM_CHAIN_DIAG)
-    v.t0 = (long long)__builtin_readcyclecounter();
-    v.rt0 = (long long)wall_clock64();
-#endif
-    /* take a ticket: the old value says which visit of the tile this is — and, mostly, that the visit before it is stored */
-    unsigned long long w = 0;
-    if (lane == 0) w = __hip_atomic_fetch_add(word, 1ull << POM_CHAIN_TICKET_SHIFT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    w = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(w >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)w);
-    const uint32_t visit = (uint32_t)(w >> POM_CHAIN_TICKET_SHIFT);
-    /* which tick: the call's first tick + how far this visit is from the call's first visit — a signed distance: launches of
-     * two calls may be in flight together, and a wavefront of the later call can draw a ticket of the earlier one */
-    v.dist = (int32_t)pom_chain_visit_distance(visit, chain_seq0);
-#if defined(POM_CHAIN_DIAG)
-    v.t1 = (long long)__builtin_readcyclecounter();
-#endif
-    /* stored visits == this visit's number: its turn.  Until then poll — for as long as the wall clock allows; a poisoned tile
-     * (somebody before this visit could not play) is nobody's turn any more */
-    int polls = 0;
-    bool timed_out = false;
-    if (!((uint32_t)w & POM_CHAIN_POISON) && (int32_t)pom_chain_visit_distance((uint32_t)w & POM_CHAIN_COUNT_MASK, visit) < 0) { /* wave-uniform */
-        const uint64_t t_wait0 = wall_clock64();
-        for (;;) {
-            __builtin_amdgcn_s_sleep(1);
-            w = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            w = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(w >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)w);
-            polls++;
-            if (((uint32_t)w & POM_CHAIN_POISON) || (int32_t)pom_chain_visit_distance((uint32_t)w & POM_CHAIN_COUNT_MASK, visit) >= 0) break;
-            if (wall_clock64() - t_wait0 >= wait_limit) {
-                timed_out = true;
-                break;
-            }
-        }
-    }
-    (void)polls;
-    const uint32_t was_on = (uint32_t)(w >> 32) & 0xFu;
-    const bool poisoned = ((uint32_t)w & POM_CHAIN_POISON) != 0;
-    const bool wrong_xcd = was_on != 0u && was_on != xcd;
-    const bool off_tape = tape_len != 0u && (uint32_t)v.dist >= tape_len;
-    if (poisoned || timed_out || wrong_xcd || off_tape) {
-        /* The visit before this one never arrived in time, or it was stored through another XCD's L2 (what this L2 holds of
-         * the tile may be stale), or the ticket lies outside the move tape (launches of two tape calls in flight together:
-         * the host joins between them, so never).  Nothing is stepped and NOTHING IS COUNTED: the tile is poisoned, every
-         * later visitor leaves it alone, its stored count stays at the ticks it really played, and the host — which finds
-         * the flag after the next join — replays the rest with ordinary launches (chain_settle, pom_runtime.h). */
-        if (lane == 0 && !poisoned) {
-            __hip_atomic_fetch_or(word, (unsigned long long)POM_CHAIN_POISON, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_or(err, (uint32_t)(timed_out ? POM_CHAIN_E_TIMEOUT : wrong_xcd ? POM_CHAIN_E_XCD : POM_CHAIN_E_TAPE), __ATOMIC_RELAXED,
-                                  __HIP_MEMORY_SCOPE_AGENT);
-        }
-        return false;
-    }
-#if defined(POM_CHAIN_DIAG)
-    v.t2 = (long long)__builtin_readcyclecounter();
-    v.polls = polls;
-    v.visit = visit;
-#endif
-    v.done = 1ull + ((unsigned long long)(xcd - was_on) << 32);
-    return true;
-}
-/* Hand the tile on: called after the record's stores have been ISSUED; waits until the L2 has acknowledged them, then counts the
- * visit as stored (which is what the next visitor polls for). */
-__device__ __forceinline__ void pom_chain_leave(unsigned long long* word, int lane, const PomChainVisit& v)
-{
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0) __hip_atomic_fetch_add(word, v.done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-/* XCD-aware tile order — the tile that workgroup b of a grid of nb takes: workgroups are dealt round-robin over the 8 XCDs (b
- * and b+8 share one, each XCD has its own L2).  Neighbouring tiles are given to workgroups of the SAME XCD (bijective for any
- * grid size): with the buffers laid out row-major over all envs (rounds 1-2) neighbouring tiles shared the 128-B lines of every
- * record row and the second touch of a line became an L2 hit instead of a second HBM fetch; with a tile contiguous in memory
- * (round 3) it keeps an XCD's traffic in one region of memory. */
-__device__ __forceinline__ int64_t pom_xcd_tile_order(int64_t b, int64_t nb)
-{
-    const int64_t q = nb / 8, r = nb % 8, x = b % 8;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
-}
-
-/* a dword that a wavefront of an earlier, still unfinished launch may have written (chained launches): past this CU's vector cache */
-template <bool CHAIN>
-__device__ __forceinline__ uint32_t pom_load_shared(const uint32_t* ptr)
-{
-    return CHAIN ? __hip_atomic_load(ptr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *ptr;
-}
 
 /* pom_rng_pick (pom_rng.h; the same values) where `dist` is wave-uniform: the stress distribution's compare chain behind a BRANCH —
  * as a select (what the compiler makes of the host's form) every tick of every distribution pays for both picks.  The quad step
@@ -1672,20 +480,8 @@ __global__ __launch_bounds__(64 * POM_WPB, (POLICY ? 4 : G == 4 ? POM_QUAD_WAVES
         /* the observation of what the tick left in the tile, while the record's stores are on their way (they have been read out
          * of LDS into registers; the staging area lies behind the record rows) */
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        ObserveParams op;
-        op.state = nullptr;
-        op.n = p.n;
-        op.n_pad = p.n_pad;
-        op.block0 = 0;
-        op.planes = p.obs_planes;
-        op.agent_attrs = p.obs_agent_attrs;
-        op.env_attrs = p.obs_env_attrs;
-        op.dtype = p.obs_dtype;
-        op.per_agent = p.obs_per_agent;
-        if (VIEW) {
-            op.viewer_attrs = p.obs_viewer_attrs;
-            op.view_radius = p.obs_view_radius;
-        }
+        const ObserveParams op{nullptr, p.n, p.n_pad, 0, p.obs_planes, p.obs_agent_attrs, p.obs_env_attrs, p.obs_dtype, p.obs_per_agent,
+                               VIEW ? p.obs_viewer_attrs : nullptr, VIEW ? p.obs_view_radius : 0};
         pom_observe_tile<OBS_PASS_ENVS_FUSED, VIEW>(op, tile, reinterpret_cast<uint4*>(tile + POM_REC_DWORDS * EPW), tile_id, lane);
     }
     if (CHAIN) { /* the record's stores have been acknowledged by the L2 before the word that hands the tile on is written */
@@ -1784,9 +580,8 @@ __global__ __launch_bounds__(64) void pom_chain_litmus_kernel(LitmusParams p)
  * round-robin over eight XCDs the tile choice assumes — a partitioned device, or another chip, is not) */
 __global__ void pom_chain_probe_kernel(uint32_t* xcd_of_block)
 {
-    uint32_t x;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(x));
-    if (threadIdx.x == 0) xcd_of_block[blockIdx.x] = x & 0xFu;
+    const uint32_t x = pom_chain_xcd();
+    if (threadIdx.x == 0) xcd_of_block[blockIdx.x] = x;
 }
 
 /* chained launches, after a join: every tile must have drawn exactly `visits` tickets, and have stored as many visits — or be
@@ -1931,7 +726,10 @@ __global__ __launch_bounds__(64) void pom_policy_kernel(PolicyParams p)
 #endif
 }
 
-__global__ __launch_bounds__(64) void pom_observe_kernel(ObserveParams p)
+/* the stand-alone export (pom_batch_observe; VIEW: pom_batch_observe_view, the same with the fogged views of PomViewSpec on the
+ * way out): a tile into LDS, then pom_observe_tile */
+template <bool VIEW>
+__device__ __forceinline__ void pom_observe_alone(const ObserveParams& p)
 {
     __shared__ __attribute__((aligned(16))) uint32_t tile[POM_REC_DWORDS * 16];
     __shared__ uint4 stage[obs_stage_vecs(OBS_PASS_ENVS_ALONE)];
@@ -1945,22 +743,10 @@ __global__ __launch_bounds__(64) void pom_observe_kernel(ObserveParams p)
      * 31 of a wavefront's 58 k cycles, profiles/r04_observe_pmc.txt.  0x0F70: vmcnt(0), the other counters left alone. */
     __builtin_amdgcn_s_waitcnt(0x0F70);
     asm volatile("" ::: "memory");
-    pom_observe_tile<OBS_PASS_ENVS_ALONE>(p, tile, stage, tile_id, lane);
+    pom_observe_tile<OBS_PASS_ENVS_ALONE, VIEW>(p, tile, stage, tile_id, lane);
 }
-
-/* pom_batch_observe_view: the same export with the fogged views (PomViewSpec) on the way out */
-__global__ __launch_bounds__(64) void pom_observe_view_kernel(ObserveParams p)
-{
-    __shared__ __attribute__((aligned(16))) uint32_t tile[POM_REC_DWORDS * 16];
-    __shared__ uint4 stage[obs_stage_vecs(OBS_PASS_ENVS_ALONE)];
-    const int lane = threadIdx.x;
-    const int64_t tile_local = pom_xcd_tile_order(blockIdx.x, gridDim.x);
-    const int64_t tile_id = p.block0 + tile_local;
-    load_tile16_x4(p.state + tile_id * POM_TILE_DWORDS, tile, lane);
-    __builtin_amdgcn_s_waitcnt(0x0F70); /* (as in pom_observe_kernel: the compiler must see that the rows have landed) */
-    asm volatile("" ::: "memory");
-    pom_observe_tile<OBS_PASS_ENVS_ALONE, true>(p, tile, stage, tile_id, lane);
-}
+__global__ __launch_bounds__(64) void pom_observe_kernel(ObserveParams p) { pom_observe_alone<false>(p); }
+__global__ __launch_bounds__(64) void pom_observe_view_kernel(ObserveParams p) { pom_observe_alone<true>(p); }
 
 /* every env's first board (episode 0) into its state and snapshot columns, through an LDS tile so that the records leave in
  * the tick's coalesced row groups */

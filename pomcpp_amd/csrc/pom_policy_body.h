@@ -20,7 +20,7 @@
  * traffic; (b) sits at one program point for both branches that need it.  On the device the floods of all agents of a wavefront are
  * run TOGETHER (round 3): the wavefront's flood jobs are dealt to its 16 quads, a quad holds one job's sets one 32-cell word per
  * lane (pom_quad_*_level below, ~25 VALU per level instead of ~70), so a wavefront pays for its longest flood at a third of the
- * price (pom_kernels.h: pom_coop_forward / pom_coop_backward).
+ * price (pom_policy_wave.h: pom_coop_forward / pom_coop_backward).
  *
  * Agent memory, 2 dwords: m0 = recentPositions.queue[0..3], a byte each: x:4 | y:4 two's-complement nibbles (-1 .. 11);
  *                         m1 = recentPositions.index:2 | count:3 @2 | moveQueue.queue[0..3] 3 bits each @5 | moveQueue.count:3 @17
@@ -232,8 +232,8 @@ struct PomCells {
 /* ---- a 121-bit cell set spread over the four lanes of a quad ------------------------------------------------------------------
  * One 32-cell word per lane: lane k of the quad holds cells 32k .. 32k+31.  A dilation then costs each lane two word exchanges
  * with its neighbours in the quad and a dozen logic ops instead of the ~50 that four words in one lane's registers take — what
- * the wave-cooperative floods of pom_kernels.h are made of.  Q says what "one word per lane" is: on the device a uint32_t per
- * lane with DPP quad permutes for prev / next (PomQuadLanes, pom_kernels.h); in tests/emul four words at once (PomQuadHost), so
+ * the wave-cooperative floods of pom_policy_wave.h are made of.  Q says what "one word per lane" is: on the device a uint32_t per
+ * lane with DPP quad permutes for prev / next (PomQuadLanes, pom_policy_wave.h); in tests/emul four words at once (PomQuadHost), so
  * that the very same level functions are fuzzed against the four-register floods below without a GPU.
  *   Q::W                     the word type;  & | ~ << >> work lane-wise
  *   q.prev(w) / q.next(w)    the word of lane k-1 / k+1 (0 at the ends)
@@ -571,7 +571,7 @@ struct PomSimplePolicy {
     }
 
     /* ---- _Decide (simple_agent.cpp:51-122) in the pieces between which its two searches sit.  The kernels run the searches for
-     * all agents of a wavefront together (pom_kernels.h: pom_coop_forward / pom_coop_backward); act() below strings the pieces
+     * all agents of a wavefront together (pom_policy_wave.h: pom_coop_forward / pom_coop_backward); act() below strings the pieces
      * together with the one-lane searches. ---- */
     /* the predicates; returns whether the agent is in danger, i.e. needs FillRMap's reach and a safe place in it */
     POM_HD int begin()

@@ -4,7 +4,7 @@
  * the batch untouched.
  *
  * It joins pom_rollout_kernel (pom_rollout.h: the K-tick loop on a tile that never leaves LDS, the ballot exit, Environment::Step's
- * bookkeeping, the result word) with the policy of pom_step_kernel<POLICY> (pom_kernels.h: pom_policy_prepare_*, pom_policy_wave, the
+ * bookkeeping, the result word) with the policy of pom_step_kernel<POLICY> (pom_policy_body.h, pom_policy_wave.h: pom_policy_prepare_*, pom_policy_wave, the
  * danger map and the cell sets laid over the tick's scratch rows).  One wavefront per (tile of 16 envs, sample); lane m of an env's
  * quad is agent m.  The agents' memory is two dwords per lane, loaded once and never stored to global memory: every sample plays on
  * with its own copy.

@@ -24,7 +24,7 @@ struct PolicyArrays {
     int bomb(int s) const { return bombs[s]; }
 };
 
-/* the four lanes of a quad at once: what PomQuadLanes (pom_kernels.h) is on the device, for the level functions of
+/* the four lanes of a quad at once: what PomQuadLanes (pom_policy_wave.h) is on the device, for the level functions of
  * pom_policy_body.h that the wave-cooperative floods are made of */
 struct QW {
     uint32_t v[4];

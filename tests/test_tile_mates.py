@@ -1,7 +1,7 @@
 """An env's tick must not depend on the envs that share its wavefront (actors and compositions: tests/tile_mates.py).
 
 The kernels share a great deal across the 16 (32, 64) envs of a wavefront, most of it resting on "the wavefront runs in lock-step":
-loop B's per-cell counters [env][124 bytes] lie over the explosion frames [row][EPW] (pom_kernels.h ROW_CLAIMS == ROW_STACK), a
+loop B's per-cell counters [env][124 bytes] lie over the explosion frames [row][EPW] (pom_tile.h ROW_CLAIMS == ROW_STACK), a
 restarting env's column is rewritten by the whole wavefront, the policy's maps and the observation's staging area lie over the tick's
 scratch rows, and the bomb / blast / bounce loops run as long as the worst mate needs.  Every other parity test compares an env with
 the oracle in whatever company it happens to keep; here the company is chosen.

@@ -1,7 +1,7 @@
 """Actors and compositions for the wavefront-mates tests (tests/test_tile_mates.py) — test infrastructure.
 
 On the device the 16 (32, 64) envs of a wavefront share one LDS tile, one instruction stream and several loops whose trip count
-is the maximum over the envs (pomcpp_amd/csrc/pom_kernels.h).  An ACTOR is one env and a script (edge_states.Entry) that pushes
+is the maximum over the envs (pomcpp_amd/csrc/pom_tile.h, pom_kernels.h).  An ACTOR is one env and a script (edge_states.Entry) that pushes
 one of the shared resources to its limit, or is as sensitive as possible to a mate doing so:
 
   deep_b_rest_dN / deep_b_push_dN   a chain of N + 1 strength-1 bombs on a boustrophedon path over the inner cells, each setting off
@@ -46,7 +46,7 @@ ENV_CAP = 6          # the step cap of the restart family; quiet_late_K counts b
 # ------------------------------------------------------------------------------------------------------------ the layout
 def layout():
     """what the overlay family was derived from, read out of the headers"""
-    k = open(os.path.join(ROOT, "pomcpp_amd", "csrc", "pom_kernels.h")).read()
+    k = open(os.path.join(ROOT, "pomcpp_amd", "csrc", "pom_tile.h")).read()
     b = open(os.path.join(ROOT, "pomcpp_amd", "csrc", "pom_step_body.h")).read()
     row = lambda name: re.search(name + r" = POM_REC_DWORDS \+ (\d+)", k).group(1)  # noqa: E731
     return dict(row_stack=int(row("ROW_STACK")), row_claims=int(row("ROW_CLAIMS")),
