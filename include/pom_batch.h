@@ -629,6 +629,60 @@ typedef struct PomExpandSpec {
 } PomExpandSpec;
 int pom_batch_expand(PomBatch* h, const PomExpandSpec* spec);
 
+/*
+ * MOVE SAFETY: an action mask — which of an agent's six moves does it survive, and from which is there somewhere to walk to?  All six
+ * candidates of every asked agent of every env in ONE launch, without touching the batch.  The six-forecast recipe
+ * gives the first answer at 6 launches per agent and a flame plane per call that a mask never reads; and its rule, "do m, then stand
+ * still", calls BOMB fatal for every horizon >= 11 (the planted bomb goes off under the agent in tick 11), which is true of an agent
+ * that stands still and useless for one that can walk.  Hence two answers per candidate: the exact one under that rule, and a stated
+ * heuristic for "is there a way out".
+ * Semantics: for every env e < n, agent a of agent_mask and candidate m in 0 .. 5 (IDLE, UP, DOWN, LEFT, RIGHT, BOMB): S_0 = a
+ *          private copy of the env's current State; the moves of tick 1 are moves_dev[e] (IDLE x 4 if moves_dev is NULL) with entry a
+ *          replaced by m — all four entries are read, dead agents' included, as pom_batch_step_device reads them
+ *          (step_utility.cpp:138-170); S_1 = bboard::Step(S_0, those moves) and S_t = bboard::Step(S_{t-1}, IDLE x 4) for t = 2 .. K =
+ *          horizon (include/bboard.hpp:668, src/bboard/step.cpp:9-284).  Bare Step as in POM_MODE_RAW whatever the handle's mode,
+ *          exactly as pom_batch_forecast: no timeStep++, no done / max_steps logic, no restart; a finished env is played like any other.
+ * death_tick[e][a][m] (nullable; int8 [n][4][6]), the exact answer: -1 if agent a is dead in S_0 (AgentInfo::dead, bboard.hpp:239);
+ *          otherwise the smallest t with S_t.agents[a].dead; 0 if it is alive in S_K.  By definition the agent_tick[e][a] that
+ *          pom_batch_forecast returns for the same horizon and those tick-1 moves.
+ * escape_tick[e][a][m] (nullable; int8 [n][4][6]), "is there a way out", a heuristic defined exactly: Free_t = the cells whose
+ *          S_t.board value is PASSAGE or IS_POWERUP (IS_WALKABLE, bboard.hpp:77-84), plus agent a's own cell while a is alive in S_t;
+ *          flames, walls, wood, bombs and other agents are not free.  R_1 = {a's position in S_1} if a is alive in S_1, else {};
+ *          R_t = (R_{t-1} and its four neighbours on the board) intersected with Free_t for t >= 2 — the cells a walker that makes at
+ *          most one step per tick onto free cells can stand on after tick t.  The output is -1 if a is dead in S_0; otherwise the
+ *          smallest t with R_t = {}; 0 if R_K is not empty: the agent can still be somewhere when the horizon ends.
+ *          What the heuristic leaves out: a walker does not push the simulation — it picks nothing up, kicks nothing, collides with
+ *          nobody, and the flames, bombs and other agents it walks among are those of the play in which the agent stood still.  It may
+ *          step back onto a cell whose bomb it left (the cell is a bomb's only once the agent has gone; here the agent never goes).
+ *          Consequences: death_tick == 0 implies escape_tick == 0 (the agent's own cell is free while it lives, so it is in every
+ *          R_t); when both are > 0, escape_tick >= death_tick (R is empty only once the agent is dead).
+ * Rows: the rows [e][a][*] of agents outside agent_mask are not written.  At least one of the two outputs is given.
+ * Nothing else changes: after the call nothing this API can read differs from before — records, snapshots and terminal records,
+ *          status and the envs' own ubflags, POM_CNT_* (these ticks are not steps), episode counters, the handle's tick, agent
+ *          memory, chain statistics.
+ * Ordering: exactly as pom_batch_forecast — chained launches are settled and the sub-streams joined first, then ONE launch on the
+ *          handle's stream; moves_dev is read and the outputs are written in stream order.  Every launch shape of the handle gives
+ *          the same bytes (the device buffers are 16-env tiles whatever the shape).
+ * POM_E_ARG (with a pom_last_error text naming pom_batch_move_safety; nothing is written): a null handle or spec, struct_size !=
+ *          sizeof(PomMoveSafetySpec) (POM_MOVE_SAFETY_SPEC_SIZE), horizon outside 1 .. POM_FORECAST_MAX_TICKS, agent_mask outside
+ *          1 .. 15, nonzero reserved_ or reserved2_, both outputs null, an output not 8-byte aligned, moves_dev not 4-byte aligned; and
+ *          a batch so large that variants (6 per agent of the mask) x tiles of 16 envs (rounded up to 8) does not fit one grid.
+ * Not here: per-variant ubflags, flame planes (pom_batch_forecast has both), a job list, the others playing SimpleAgent
+ *          (pom_batch_rollout_jobs has both), a walker that pushes the simulation.
+ */
+enum { POM_MOVE_SAFETY_SPEC_SIZE = 48 };
+typedef struct PomMoveSafetySpec {
+    int32_t struct_size;      /*  0  = sizeof(PomMoveSafetySpec) */
+    int32_t horizon;          /*  4  K, 1..POM_FORECAST_MAX_TICKS */
+    int32_t agent_mask;       /*  8  bit a: judge agent a's moves; 1..15 */
+    int32_t reserved_;        /* 12  must be 0 */
+    const int32_t* moves_dev; /* 16  nullable: int32 [n][4], the OTHERS' moves of tick 1 (row e, entry a is replaced by the candidate); NULL = IDLE */
+    int8_t* death_tick_dev;   /* 24  nullable: int8 [n][4][6], 8-byte aligned */
+    int8_t* escape_tick_dev;  /* 32  nullable: int8 [n][4][6], 8-byte aligned; at least one of the two outputs is given */
+    int64_t reserved2_;       /* 40  must be 0 */
+} PomMoveSafetySpec;
+int pom_batch_move_safety(PomBatch* h, const PomMoveSafetySpec* spec);
+
 /* A stand-in for a learned policy in measurements and tests of the closed loop (NOT part of the stepper): one launch on `stream`
  * that writes Move[4] of the envs [first, first + count) into moves_dev (int32 [n][4]).  codes_dev != NULL: the POM_OBS_CODES
  * observation of the batch (uint8 [n][5][11][11]) — every byte of the range's observations is read and the moves depend on them;

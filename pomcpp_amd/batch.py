@@ -81,6 +81,14 @@ def _forecast_spec(horizon: int, moves, flame_tick, agent_tick=None, ubflags=Non
                          _ptr(ubflags))
 
 
+class _MoveSafetySpec(C.Structure):
+    """PomMoveSafetySpec (include/pom_batch.h): the horizon, whose moves are judged, the others' first-tick moves and the two outputs"""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("horizon", C.c_int32), ("agent_mask", C.c_int32), ("reserved_", C.c_int32),
+        ("moves_dev", C.c_void_p), ("death_tick_dev", C.c_void_p), ("escape_tick_dev", C.c_void_p), ("reserved2_", C.c_int64),
+    ]
+
+
 class _RolloutSpec(C.Structure):
     """PomRolloutSpec (include/pom_batch.h): the rollout's horizon, samples, move stream, first-tick moves and result"""
     _fields_ = [
@@ -214,6 +222,7 @@ def load_library() -> C.CDLL:
         ("pom_batch_rollout_policy", [P, C.POINTER(_RolloutPolicySpec)], None),
         ("pom_batch_rollout_jobs", [P, C.POINTER(_RolloutJobsSpec)], None),
         ("pom_batch_expand", [P, C.POINTER(_ExpandSpec)], None),
+        ("pom_batch_move_safety", [P, C.POINTER(_MoveSafetySpec)], None),
         ("pom_batch_step_device_range", [P, I64, I64, VP, VP, VP, I32, I32, VP, VP], None),
         ("pom_bench_policy", [VP, VP, I64, I64, C.c_uint32, VP], None),
         ("pom_batch_stream", [P, C.POINTER(C.c_void_p)], None),
@@ -663,6 +672,46 @@ class BatchEnvironment:
             spec = _forecast_spec(horizon, moves, res["flame_tick"], res.get("agent_tick"), res.get("ubflags"))
             _check(self._lib, self._lib.pom_batch_forecast(self._h, C.byref(spec)))
         return res
+
+    # ---- move safety: every agent's six moves judged in one launch (pom_batch_move_safety) ------------------
+    def move_safety(self, horizon: int, agents=None, moves=None, out=None, death: bool = True, escape: bool = True) -> dict:
+        """An action mask's raw material: each of the six moves (IDLE, UP, DOWN, LEFT, RIGHT, BOMB) of every agent of `agents` (a mask
+        int 1..15 or an iterable of agent ids; None: all four) played as tick 1, then `horizon` - 1 (horizon 1..32) ticks standing
+        still, on a scratch copy of every env by one kernel on the handle's stream; the batch itself is left exactly as it is
+        (pom_batch_move_safety, include/pom_batch.h).  `moves`: a device int32 tensor [n, 4], the OTHER agents' moves of tick 1 (an
+        agent's own entry is replaced by its candidate; None: IDLE).  Returns a dict of int8 [n, 4, 6] tensors on the handle's device:
+        with `death` `death_tick` (-1 dead already, t the tick the agent dies in if it stands still after the move, 0 alive at the
+        end — forecast()'s agent_tick for those moves), with `escape` `escape_tick` (-1 dead already, t the first tick after which a
+        walker that started with the move has no free cell left to stand on, 0 there still is one when the horizon ends: the header
+        defines it exactly).  `out`: a dict with tensors of an earlier call under the same names, written in place of new ones.  The
+        rows of agents not asked for are -1 in a tensor this call allocates and left as they were in a caller's."""
+        import torch
+        if not 1 <= int(horizon) <= 32:
+            raise ValueError("horizon must be 1..32")
+        mask = 0xF if agents is None else _agent_mask(agents, "agents")
+        if mask == 0:
+            raise ValueError("agents names nobody")
+        names = [name for name, wanted in (("death_tick", death), ("escape_tick", escape)) if wanted]
+        if not names:
+            raise ValueError("death and escape are both False: nothing to compute")
+        res = {}
+        for name in names:
+            given = None if out is None else out.get(name)
+            res[name] = self._out_tensor(given, (self.n, 4, 6), torch.int8, f"out[{name!r}]")
+            if given is None and mask != 0xF:
+                res[name].fill_(-1)
+        if moves is not None:
+            self._device_tensor(moves, "moves", "int32", (self.n, 4))
+        with self._ordered():
+            spec = _MoveSafetySpec(C.sizeof(_MoveSafetySpec), int(horizon), mask, 0, _ptr(moves), _ptr(res.get("death_tick")),
+                                   _ptr(res.get("escape_tick")), 0)
+            _check(self._lib, self._lib.pom_batch_move_safety(self._h, C.byref(spec)))
+        return res
+
+    def safe_moves(self, horizon: int, agents=None, moves=None):
+        """The action mask: bool [n, 4, 6], True where move_safety()'s escape_tick is 0 — the agent is alive and, having made the
+        move, still has somewhere to be when the horizon ends.  Rows of dead agents and of agents not asked for are all False."""
+        return self.move_safety(horizon, agents, moves, death=False)["escape_tick"] == 0
 
     # ---- rollout: R random playouts of every env (pom_batch_rollout) ---------------------------------------
     def rollout(self, horizon: int, samples: int, seed: int, dist: int = DIST_RANDOM, moves=None, out=None, *, simple=None, first=None,

@@ -1543,3 +1543,44 @@ extern "C" int pom_batch_expand(PomBatch* h, const PomExpandSpec* s)
     HIPCHK(hipGetLastError());
     return POM_OK;
 }
+
+/* ---- the move safety (pom_batch.h PomMoveSafetySpec): every asked agent's six candidate moves played K ticks ahead on scratch copies
+ * of its tile, one launch.  Its kernel comes after the expansion's, so that every kernel before it is emitted as it was without it ---- */
+#include "pom_move_safety.h"
+
+static_assert(sizeof(PomMoveSafetySpec) == POM_MOVE_SAFETY_SPEC_SIZE, "pom_batch.h states the size");
+
+extern "C" int pom_batch_move_safety(PomBatch* h, const PomMoveSafetySpec* s)
+{
+    static const char who[] = "pom_batch_move_safety";
+    const char* what = !h ? "the handle is NULL" : SPEC_HEAD(PomMoveSafetySpec, s);
+    /* tiles of 16 envs, rounded up to a multiple of 8 as the rollouts' grid (rollout_begin); 6 variants per agent of the mask */
+    const int64_t tiles = h ? (h->n + 15) / 16 : 0, tiles8 = (tiles + 7) / 8 * 8;
+    const int variants = what ? 0 : 6 * __builtin_popcount((unsigned)s->agent_mask & 15u);
+    if (what) {}
+    else if (s->reserved2_ != 0) what = "reserved2_ must be 0";
+    else if (s->horizon < 1 || s->horizon > POM_FORECAST_MAX_TICKS) what = "horizon must be 1..32";
+    else if (s->agent_mask < 1 || s->agent_mask > 15) what = "agent_mask must be 1..15";
+    else if (!s->death_tick_dev && !s->escape_tick_dev) what = "death_tick_dev and escape_tick_dev are both NULL";
+    else if (((uintptr_t)s->death_tick_dev & 7) || ((uintptr_t)s->escape_tick_dev & 7)) what = "death_tick_dev and escape_tick_dev must be 8-byte aligned";
+    else if ((uintptr_t)s->moves_dev & 3) what = "moves_dev must be 4-byte aligned";
+    else if (tiles8 * variants > (int64_t)INT_MAX) what = "variants x tiles of 16 envs exceed one grid: call with fewer agents";
+    if (what) return rollout_bad_arg(who, what);
+    HIPCHK(hipSetDevice(h->device));
+    /* quiesce, not only join (as pom_batch_forecast): after chained launches a tile left behind is caught up first — the candidates
+     * are played from the state a download returns */
+    if (int jr = quiesce(h)) return jr;
+    MoveSafetyParams p;
+    p.state = h->state;
+    p.moves = s->moves_dev;
+    p.death_tick = s->death_tick_dev;
+    p.escape_tick = s->escape_tick_dev;
+    p.n = h->n;
+    p.horizon = s->horizon;
+    p.agent_mask = s->agent_mask;
+    p.tiles = (uint32_t)tiles;
+    p.tiles8 = (uint32_t)tiles8;
+    pom_move_safety_kernel<<<dim3((unsigned)(tiles8 * variants)), dim3(64), 0, h->stream>>>(p);
+    HIPCHK(hipGetLastError());
+    return POM_OK;
+}
