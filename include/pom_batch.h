@@ -34,7 +34,7 @@ extern "C" {
 
 typedef enum PomError {
     POM_OK = 0,
-    POM_E_ARG = 1,             /* null handle, range outside [0, n_envs), bad option */
+    POM_E_ARG = 1,             /* null handle, range outside [0, n_envs), bad option; pom_last_error() names the refusing call: "<call>: <what>" */
     POM_E_HIP = 2,             /* HIP runtime error or no device; pom_last_error() has the text */
     POM_E_UNREPRESENTABLE = 3, /* an uploaded State holds a value no reachable game state has (pom_packed.h) */
     POM_E_NOMEM = 4
@@ -84,7 +84,7 @@ typedef struct PomBatchOptions {
  * envs, 20-tick call from an idle device / 500-tick call: CHAIN 11.4 - 12.3 / 9.2 us (profiles/r03y_*); with the batch as
  * three sub-batches on parallel streams: THREADS 16.2 - 17.0 / 14.5 us, DIRECT and GRAPH behind that (measured earlier in the
  * round, 18.0 / 15.5 for THREADS then: DIRECT 17.2 .. 26.4 (host-dependent) / 15.6 - 16.0 us; GRAPH 21.4 .. 23.5 / 16.1 us;
- * pomcpp_amd/csrc/pom_runtime.h, profiles/r03_issue_modes.txt) */
+ * pomcpp_amd/csrc/pom_issue.h, profiles/r03_issue_modes.txt) */
 enum {
     POM_ISSUE_AUTO = 0,
     POM_ISSUE_DIRECT = 1,  /* the calling thread issues every launch; the library owns no thread */

@@ -31,7 +31,7 @@
  *    no launch can hang the device.
  * Either way the wavefront POISONS the tile (a bit in its word) instead of stepping it: every later visitor leaves a poisoned
  * tile alone, so its record stays exactly what its last stored tick made it and its word says how many ticks that was.  The
- * host keeps a log of the chained calls since the last check (what each was launched with); chain_settle (pom_runtime.h) —
+ * host keeps a log of the chained calls since the last check (what each was launched with); chain_settle (pom_chain_host.h) —
  * run by every API call that reads or changes the batch other than another chained call — joins the streams, lets a small
  * kernel list the poisoned tiles, and REPLAYS their missing ticks with ordinary one-tile launches from that log: a give-up
  * costs time, never correctness (tests/test_gpu_chain.py forces it with a wait limit of zero).  Uneven ticket counts

@@ -14,7 +14,7 @@
 
 /* how long a wavefront waits for the visit before its own before it gives up (it must never hang the device): wall-clock time, so
  * that a holder descheduled for a while (several processes time-slicing one GPU, a debugger) is waited for; a give-up poisons the
- * tile and the host replays its ticks after the next join — slow, never wrong (pom_runtime.h chain_settle) */
+ * tile and the host replays its ticks after the next join — slow, never wrong (pom_chain_host.h chain_settle) */
 enum { POM_CHAIN_WAIT_LIMIT_US = 2000000 };
 #ifndef POM_CHAIN_WORD_STRIDE
 #define POM_CHAIN_WORD_STRIDE 16 /* 64-bit words between the ticket words of neighbouring tiles: a 128-byte line each (10.28 - 10.30 us
@@ -87,7 +87,7 @@ __device__ __forceinline__ bool pom_chain_enter(unsigned long long* word, uint32
          * the tile may be stale), or the ticket lies outside the move tape (launches of two tape calls in flight together:
          * the host joins between them, so never).  Nothing is stepped and NOTHING IS COUNTED: the tile is poisoned, every
          * later visitor leaves it alone, its stored count stays at the ticks it really played, and the host — which finds
-         * the flag after the next join — replays the rest with ordinary launches (chain_settle, pom_runtime.h). */
+         * the flag after the next join — replays the rest with ordinary launches (chain_settle, pom_chain_host.h). */
         if (lane == 0 && !poisoned) {
             __hip_atomic_fetch_or(word, (unsigned long long)POM_CHAIN_POISON, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_fetch_or(err, (uint32_t)(timed_out ? POM_CHAIN_E_TIMEOUT : wrong_xcd ? POM_CHAIN_E_XCD : POM_CHAIN_E_TAPE), __ATOMIC_RELAXED,

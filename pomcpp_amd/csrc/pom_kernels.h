@@ -1,6 +1,6 @@
 /*
  * pom_kernels.h — the gfx950 kernels of the batched Pommerman stepper (device side only; the host runtime that launches
- * them is pom_runtime.h, the C-ABI of include/pom_batch.h is pom_batch.hip).  Written for MI355X only: 64-lane wavefronts,
+ * them is pom_issue.h, the C-ABI of include/pom_batch.h is pom_batch.hip).  Written for MI355X only: 64-lane wavefronts,
  * one wavefront per workgroup, each env's board / bomb queue / flame queue in a column of the wavefront's LDS tile
  * ([row][lane]: every per-lane dynamic index is an LDS address, no shuffles, no scratch).
  *
@@ -43,7 +43,7 @@ struct StepParams {
     int64_t n, n_pad, env_offset;
     uint64_t seed;
     uint32_t tick0;            /* the launch's first tick is tick0 + *tick_base */
-    const uint32_t* tick_base; /* a device word: 0 for a launch of its own, the chunk's first tick for a node of a replayed graph (pom_runtime.h) */
+    const uint32_t* tick_base; /* a device word: 0 for a launch of its own, the chunk's first tick for a node of a replayed graph (pom_issue.h) */
     int32_t dist, ticks, mode, auto_reset, max_steps;
     int64_t block0, block_end; /* this launch covers tiles block0 .. block_end - 1 (sub-batch of a split step) */
     uint32_t* terminal;  /* auto_reset == POM_RESET_AT_END: the last finished episode's final record per env, array of structs */

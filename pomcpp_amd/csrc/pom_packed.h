@@ -401,7 +401,7 @@ POM_HD void pom_unpack_lane(const uint32_t* tile, int32_t* st, int lane)
  * launches of two calls can be in flight together, and a wavefront of the later call may draw a ticket of the earlier one.
  * Bit 28 (POM_CHAIN_POISON): a visitor could not play its tick (it waited out its time limit for the visit before it, or found
  * the tile stored through another XCD's L2).  Nobody steps a poisoned tile: its stored count stays at the number of ticks it
- * really played, and the host replays the rest after the next join (pom_runtime.h chain_settle). */
+ * really played, and the host replays the rest after the next join (pom_chain_host.h chain_settle). */
 enum { POM_CHAIN_TICKET_SHIFT = 36, POM_CHAIN_COUNT_MASK = 0x0FFFFFFF, POM_CHAIN_POISON = 0x10000000 };
 /* failure flags of chained launches (a device word, read back by chain_settle) */
 enum { POM_CHAIN_E_TIMEOUT = 1, POM_CHAIN_E_XCD = 2, POM_CHAIN_E_UNEVEN = 4, POM_CHAIN_E_TAPE = 8 };

@@ -59,6 +59,72 @@ def test_no_cpu_fallback_without_a_gpu(hip_lib):
         step_one(new_states(1), np.zeros(4, dtype=np.int32))
 
 
+def _fail_another_call(lib):
+    """leaves another call's text in pom_last_error"""
+    assert lib.pom_batch_create(None, 0, None) == 1 and lib.pom_last_error().decode().startswith("pom_batch_create: ")
+
+
+def test_every_refusing_call_names_itself(hip_lib):
+    """Every call of the header but the three that cannot refuse, made with a NULL handle and zero / NULL for everything else right after
+    ANOTHER call has failed: POM_E_ARG, and pom_last_error() names the call that refused, not the one before it.  No device needed."""
+    lib = hip_lib
+    syms = [s for s in _declared_symbols() if s not in ("pom_last_error", "pom_device_count", "pom_batch_size")]
+    assert len(syms) >= 52
+    wrong = []
+    for s in syms:
+        fn = getattr(lib, s)
+        assert fn.argtypes, f"{s}: pomcpp_amd.batch.load_library declares no argument types for it"
+        args = [0 if t in (ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint64) else None for t in fn.argtypes]
+        _fail_another_call(lib)
+        if s == "pom_batch_create":   # (the other call must be another one)
+            assert lib.pom_batch_destroy(None) == 1 and lib.pom_last_error().decode().startswith("pom_batch_destroy: ")
+        rc, text = fn(*args), lib.pom_last_error().decode()
+        if rc != 1 or not text.startswith(s + ": "):
+            wrong.append((s, rc, text))
+    assert not wrong, f"{len(wrong)} of {len(syms)}:\n" + "\n".join(map(str, wrong))
+
+
+def test_create_refuses_bad_options_by_name_before_it_needs_a_device(hip_lib):
+    """pom_batch_create checks its arguments and options before its first runtime call: each of these is POM_E_ARG with a text of its
+    own, with or without a device"""
+    from pomcpp_amd.batch import _Options
+    lib, size = hip_lib, ctypes.sizeof(_Options)
+    out = ctypes.c_void_p()
+
+    def opts(**kw):
+        o = _Options(struct_size=size, mode=1)
+        for k, v in kw.items():
+            setattr(o, k, v)
+        return o
+
+    assert lib.pom_batch_create(ctypes.byref(out), 64, ctypes.byref(opts(device=1 << 20))) == 2   # good options get as far as the device
+    table = [
+        ("out is NULL", None, 64, opts()),
+        ("n = 0", out, 0, opts()),
+        ("n = 2^30 + 1", out, (1 << 30) + 1, opts()),
+        ("struct_size 0", out, 64, opts(struct_size=0)),
+        ("struct_size sizeof + 8", out, 64, opts(struct_size=size + 8)),
+        ("mode 2", out, 64, opts(mode=2)),
+        ("auto_reset 3", out, 64, opts(auto_reset=3)),
+        ("lanes_per_env 2", out, 64, opts(lanes_per_env=2)),
+        ("envs_per_wave 8", out, 64, opts(envs_per_wave=8)),
+        ("lanes_per_env 4 with envs_per_wave 32", out, 64, opts(lanes_per_env=4, envs_per_wave=32)),
+        ("streams -1", out, 64, opts(streams=-1)),
+        ("streams 9", out, 64, opts(streams=9)),
+        ("issue_mode 5", out, 64, opts(issue_mode=5)),
+        ("RESET_AT_END with lanes_per_env 1", out, 64, opts(auto_reset=2, lanes_per_env=1)),
+    ]
+    texts = set()
+    for what, o, n, op in table:
+        assert lib.pom_batch_destroy(None) == 1   # another call's text
+        rc = lib.pom_batch_create(None if o is None else ctypes.byref(o), n, ctypes.byref(op))
+        text = lib.pom_last_error().decode()
+        assert rc == 1 and text.startswith("pom_batch_create: "), (what, rc, text)
+        assert not out.value, what
+        texts.add(text)
+    assert len(texts) >= 10, texts   # (the three bad arguments share a text, the two struct sizes differ in the number only)
+
+
 def test_product_never_touches_the_oracle():
     """No file of the product (package sources, public headers) includes, links, loads or imports the checker."""
     needles = ("pom_oracle", "libpom_oracle", "oracle_lib", "from tests", "import tests", "oracle/", "_ref")
