@@ -495,36 +495,59 @@ class BatchEnvironment:
             _check(self._lib, self._lib.pom_batch_step_device_many(self._h, _ptr(moves), int(ticks)))
 
     def step_device_range(self, first: int, count: int, moves, stream=None, codes=None, planes=None, view_radius: Optional[int] = None,
-                          viewer_attrs=None, env_attrs=None) -> None:
+                          viewer_attrs=None, env_attrs=None, *, per_agent: Optional[bool] = None, agent_attrs=None) -> None:
         """Closed-loop stepping (pom_batch_step_device_range): one tick for the envs [first, first + count) — whole tiles of 16 — as ONE
         launch on `stream` (a raw hipStream_t / torch stream; None: the handle's stream), Move[4] from `moves` (int32[n, 4] device tensor
-        or address, indexed by env).  `codes` (uint8[n, 5, 11, 11]) or `planes` (uint8[n, 16, 11, 11]): the observation of those envs after
-        the tick, written by the same launch.  Nothing is forked or joined: the stream orders the call; sync() the handle once before a loop
-        of these (and before capturing them into a graph).  `view_radius`: the four agents' fogged views instead
+        or address, indexed by env).  `codes` (uint8[n, 5, 11, 11]) or `planes` ([n, 16, 11, 11] or, with `per_agent`, [n, 4, 16, 11, 11] of
+        uint8 / float16 / float32, the element type is the tensor's): the observation of those envs after the tick, written by the same
+        launch, and with it optionally `agent_attrs` int32[n, 4, 8] and `env_attrs` int32[n, 4].  Every array is sized for the WHOLE batch
+        and indexed by env; only the range's rows are written.  Nothing is forked or joined: the stream orders the call; sync() the handle
+        once before a loop of these (and before capturing them into a graph).  `view_radius`: the four agents' fogged views instead
         (pom_batch_step_device_range_view) — `codes` uint8[n, 4, 5, 11, 11] or `planes` [n, 4, 16, 11, 11] of uint8 / float16 / float32, and
-        optionally `viewer_attrs` int32[n, 4, 12] and `env_attrs` int32[n, 4]."""
-        st = getattr(stream, "cuda_stream", stream)
-        mv = moves.data_ptr() if hasattr(moves, "data_ptr") else int(moves)
-        out, code = (codes, 3) if codes is not None else (planes, 0)
-        if view_radius is None and (viewer_attrs is not None or env_attrs is not None):
-            raise ValueError("viewer_attrs / env_attrs are written with the fogged views only: pass view_radius")
-        if view_radius is not None:
-            if out is None:
-                raise ValueError("view_radius needs `codes` or `planes` to write the views to")
-            if not 0 <= int(view_radius) <= 10:
-                raise ValueError("view_radius must be 0..10")
+        optionally `viewer_attrs` int32[n, 4, 12] and `env_attrs` int32[n, 4].
+        Every tensor (anything with data_ptr / shape / dtype) is checked — element type, shape, contiguity, device — and a range outside
+        the batch, `codes` together with `planes`, `per_agent` with `codes` and attribute arrays that nothing would write are refused,
+        all with a ValueError before anything is launched; a raw device address passes unchecked (planes then are uint8).  The checks
+        make no runtime call."""
+        first, count, view = int(first), int(count), view_radius is not None
+        if first < 0 or count < 0 or first + count > self.n:
+            raise ValueError(f"the range [{first}, {first + count}) lies outside the batch of {self.n} envs")
+        if codes is not None and planes is not None:
+            raise ValueError("codes and planes are two forms of one observation: pass one")
+        if per_agent and codes is not None and not view:
+            raise ValueError("the codes layout has no per-agent view (but for the fogged ones: view_radius)")
+        if view and per_agent is not None and not per_agent:
+            raise ValueError("view_radius gives every agent its own view: per_agent=False contradicts it")
+        if view and not 0 <= int(view_radius) <= 10:
+            raise ValueError("view_radius must be 0..10")
+        if viewer_attrs is not None and not view:
+            raise ValueError("viewer_attrs are written with the fogged views only: pass view_radius")
+        if agent_attrs is not None and view:
+            raise ValueError("agent_attrs are written with the plain observation only: the fogged views have viewer_attrs")
+        out, name, code = (codes, "codes", 3) if codes is not None else (planes, "planes", 0)
+        if out is None and (view or per_agent or agent_attrs is not None or env_attrs is not None):
+            raise ValueError("view_radius, per_agent, agent_attrs and env_attrs belong to an observation: pass `codes` or `planes`")
+        per_agent = bool(per_agent) or view
+        if hasattr(moves, "data_ptr"):
+            self._device_tensor(moves, "moves", "int32", (self.n, 4))
+        if hasattr(out, "data_ptr"):
+            dtype = "uint8"
             if codes is None:
-                code = {"torch.uint8": 0, "torch.float16": 1, "torch.float32": 2}.get(str(getattr(planes, "dtype", "torch.uint8")))
+                dtype = str(getattr(planes, "dtype", "")).rsplit(".", 1)[-1]
+                code = {"uint8": 0, "float16": 1, "float32": 2}.get(dtype)
                 if code is None:
-                    raise ValueError("planes must be uint8, float16 or float32")
-            for t, shape in ((out, (self.n, 4, 5 if codes is not None else 16, 11, 11)), (viewer_attrs, (self.n, 4, 12)), (env_attrs, (self.n, 4))):
-                if hasattr(t, "shape") and (tuple(t.shape) != shape or not t.is_contiguous()):
-                    raise ValueError(f"expected a contiguous tensor of shape {shape}, got {tuple(t.shape)}")
+                    raise ValueError(f"planes must be uint8, float16 or float32, got {getattr(planes, 'dtype', None)}")
+            self._device_tensor(out, name, dtype, (self.n,) + ((4,) if per_agent else ()) + (5 if codes is not None else 16, 11, 11))
+        for t, what, width in ((viewer_attrs, "viewer_attrs", 12), (agent_attrs, "agent_attrs", 8), (env_attrs, "env_attrs", None)):
+            if hasattr(t, "data_ptr"):
+                self._device_tensor(t, what, "int32", (self.n, 4) + (() if width is None else (width,)))
+        st = getattr(stream, "cuda_stream", stream)
+        if view:
             spec = _view_spec(code, view_radius, out, viewer_attrs, env_attrs)
-            _check(self._lib, self._lib.pom_batch_step_device_range_view(self._h, int(first), int(count), mv, st, C.byref(spec)))
+            _check(self._lib, self._lib.pom_batch_step_device_range_view(self._h, first, count, _ptr(moves), st, C.byref(spec)))
             return
-        _check(self._lib, self._lib.pom_batch_step_device_range(self._h, int(first), int(count), mv, st, out.data_ptr() if out is not None else None,
-                                                                code, 0, None, None))
+        _check(self._lib, self._lib.pom_batch_step_device_range(self._h, first, count, _ptr(moves), st, _ptr(out), code, int(per_agent), _ptr(agent_attrs),
+                                                                _ptr(env_attrs)))
 
     def chain_stats(self) -> dict:
         """chained launches since creation: launches issued, checks run, tiles found left behind, ticks replayed for them"""

@@ -1,5 +1,6 @@
 """What BatchEnvironment's calls ask of their device tensors (pomcpp_amd/batch.py _device_tensor, _out_tensor): every tensor argument of
-step_device, step_device_many, copy_envs (tensor form), observe(out=), forecast, rollout, rollout_jobs, expand and move_table(others=) is
+step_device, step_device_many, step_device_range (plain, per-agent and fogged-view forms), copy_envs (tensor form), observe(out=),
+forecast, rollout, rollout_jobs, expand and move_table(others=) is
 refused with a ValueError that names the argument when its element type or its shape is wrong, when it is a non-contiguous view of a
 larger tensor, and when it lives on the CPU — and a refused call has done nothing: state, counters and episode numbers are what they were.
 
@@ -19,13 +20,34 @@ def _handle():
     return env
 
 
+def range_rows(env, i32, u8, good):
+    """_table's rows of step_device_range, the one tensor-taking call that makes no runtime call: tests/test_wrapper_args_host.py drives
+    them without a GPU.  good(shape, dtype): a right tensor for the arguments that are not the row's; the range is the first tile."""
+    mv = good((N, 4), i32)
+    planes, views = good((N, 16, 11, 11), u8), good((N, 4, 16, 11, 11), u8)
+    step = lambda **kw: env.step_device_range(0, 16, mv, **kw)  # noqa: E731
+    return [
+        ("step_device_range", "moves", "moves", i32, (N, 4), False, lambda t: env.step_device_range(0, 16, t)),
+        ("step_device_range", "codes", "codes", u8, (N, 5, 11, 11), False, lambda t: step(codes=t)),
+        ("step_device_range", "planes", "planes", u8, (N, 16, 11, 11), False, lambda t: step(planes=t)),
+        ("step_device_range(per_agent)", "planes", "planes", u8, (N, 4, 16, 11, 11), False, lambda t: step(planes=t, per_agent=True)),
+        ("step_device_range", "agent_attrs", "agent_attrs", i32, (N, 4, 8), False, lambda t: step(planes=planes, agent_attrs=t)),
+        ("step_device_range", "env_attrs", "env_attrs", i32, (N, 4), False, lambda t: step(planes=planes, env_attrs=t)),
+        ("step_device_range(view_radius)", "codes", "codes", u8, (N, 4, 5, 11, 11), False, lambda t: step(codes=t, view_radius=4)),
+        ("step_device_range(view_radius)", "planes", "planes", u8, (N, 4, 16, 11, 11), False, lambda t: step(planes=t, view_radius=4)),
+        ("step_device_range(view_radius)", "viewer_attrs", "viewer_attrs", i32, (N, 4, 12), False,
+         lambda t: step(planes=views, view_radius=4, viewer_attrs=t)),
+        ("step_device_range(view_radius)", "env_attrs", "env_attrs", i32, (N, 4), False, lambda t: step(planes=views, view_radius=4, env_attrs=t)),
+    ]
+
+
 def _table(env, torch):
     """(call, argument, the text that names it, element type, shape, free: the first dimension is the caller's, the call given a tensor)"""
     dev = torch.device("cuda", 0)
     i32, i64, u8 = torch.int32, torch.int64, torch.uint8
     src = torch.full((M,), -1, dtype=i64, device=dev)   # entries without a job: even a call that went through would change nothing
     mv = torch.zeros((M, 4), dtype=i32, device=dev)
-    return [
+    return range_rows(env, i32, u8, lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=dev)) + [
         ("step_device", "moves", "moves", i32, (N, 4), False, lambda t: env.step_device(t)),
         ("step_device_many", "moves", "moves", i32, (3, N, 4), True, lambda t: env.step_device_many(t)),
         ("copy_envs", "src", "src", i64, (N,), True, lambda t: env.copy_envs(t)),
