@@ -1,4 +1,4 @@
-"""ctypes binding of libpom_batch.so (include/pom_batch.h) and `BatchEnvironment`.
+"""`BatchEnvironment` over the ctypes binding of libpom_batch.so (pomcpp_amd/_abi.py mirrors include/pom_batch.h).
 
 `BatchEnvironment` mirrors `bboard::Environment` (/root/reference/include/bboard.hpp:541-644,
 src/bboard/environment.cpp:48-213) for n concurrent games on one MI355X:
@@ -16,116 +16,50 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
-import os
 import sys
 import weakref
 from typing import Optional
 
 import numpy as np
 
+from ._abi import (  # noqa: F401 (the binding's names are this module's too: callers import them from here)
+    MODE_RAW, MODE_ENV, RESET_OFF, RESET_AT_START, RESET_AT_END, DIST_HARMLESS, DIST_RANDOM, DIST_STRESS,
+    CNT_STEPS, CNT_EPISODES, CNT_RESETS, CNT_UB_TICKS, ISSUE_AUTO, ISSUE_DIRECT, ISSUE_THREADS, ISSUE_GRAPH, ISSUE_CHAIN,
+    COPY_FROM_SNAPSHOT, COPY_SET_SNAPSHOT, UB_LOST_AGENT, UB_NULL_BOMB, UB_QUEUE_OVERFLOW, UB_REVERT_LOOP, UB_BAD_INDEX,
+    UB_FLAME_QUEUE_RANGE, ROLLOUT_FRESH_AGENTS, RO_NONE, RO_ALIVE, RO_DONE, RO_DRAW, RO_TIMEOUT, RO_UB, RO_WINNER_SHIFT,
+    RO_WINNER_MASK, RO_LENGTH_SHIFT, PomError, _Options, _ViewSpec, _ForecastSpec, _MoveSafetySpec, _RolloutSpec,
+    _RolloutPolicySpec, _RolloutJobsSpec, _ExpandSpec, _ptr, _spec, _view_spec, _forecast_spec, library_path, load_library, _check)
 from .state import STATE_DTYPE
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-MODE_RAW, MODE_ENV = 0, 1
-RESET_OFF, RESET_AT_START, RESET_AT_END = 0, 1, 2  # PomBatchOptions.auto_reset (True = RESET_AT_START)
-DIST_HARMLESS, DIST_RANDOM, DIST_STRESS = 0, 1, 2
-CNT_STEPS, CNT_EPISODES, CNT_RESETS, CNT_UB_TICKS = 0, 1, 2, 3
-ISSUE_AUTO, ISSUE_DIRECT, ISSUE_THREADS, ISSUE_GRAPH, ISSUE_CHAIN = 0, 1, 2, 3, 4  # PomBatchOptions.issue_mode
-COPY_FROM_SNAPSHOT, COPY_SET_SNAPSHOT = 1, 2  # pom_batch_copy_envs flags
-UB_LOST_AGENT, UB_NULL_BOMB, UB_QUEUE_OVERFLOW, UB_REVERT_LOOP, UB_BAD_INDEX, UB_FLAME_QUEUE_RANGE = 1, 2, 4, 8, 16, 32
+
+def _bounded(v, name: str, lo: int, hi: int) -> int:
+    """`v` as an int of lo..hi"""
+    if not lo <= int(v) <= hi:
+        raise ValueError(f"{name} must be {lo}..{hi}")
+    return int(v)
 
 
-class PomError(RuntimeError):
-    def __init__(self, code: int, text: str):
-        super().__init__(f"pom_batch error {code}: {text}")
-        self.code = code
+def _lookahead(horizon) -> int:
+    """the horizon of forecast() and move_safety(), which play every tick of it on a scratch copy"""
+    return _bounded(horizon, "horizon", 1, 32)
 
 
-class _Options(C.Structure):
-    _fields_ = [
-        ("struct_size", C.c_int32), ("device", C.c_int32), ("stream", C.c_void_p),
-        ("mode", C.c_int32), ("auto_reset", C.c_int32), ("max_steps", C.c_int32),
-        ("env_offset", C.c_int64), ("envs_per_wave", C.c_int32), ("streams", C.c_int32),
-        ("lanes_per_env", C.c_int32), ("fresh_boards", C.c_int32), ("board_seed", C.c_uint64),
-        ("issue_mode", C.c_int32), ("reserved_", C.c_int32),
-    ]
+def _u64(seed) -> int:
+    """a seed as the uint64 a spec carries"""
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
 
 
-class _ViewSpec(C.Structure):
-    """PomViewSpec (include/pom_batch.h): where the fogged per-agent views go"""
-    _fields_ = [
-        ("struct_size", C.c_int32), ("dtype", C.c_int32), ("view_radius", C.c_int32), ("reserved_", C.c_int32),
-        ("planes_dev", C.c_void_p), ("viewer_attrs_dev", C.c_void_p), ("env_attrs_dev", C.c_void_p),
-    ]
+def _job_ptrs(m: int, *tensors):
+    """the addresses of a job list's arrays; no jobs: NULL pointers (an empty tensor has no address worth passing)"""
+    return tuple(_ptr(t) if m else None for t in tensors)
 
 
-def _ptr(t):
-    """what a spec's pointer field takes: None, a tensor's device address, or a raw address"""
-    return None if t is None else t.data_ptr() if hasattr(t, "data_ptr") else int(t)
+def _dtype_name(dtype) -> str:
+    """an element type by name: "uint8" for torch.uint8 as for the string"""
+    return str(dtype).rsplit(".", 1)[-1]
 
 
-def _view_spec(code: int, radius: int, planes, viewer_attrs=None, env_attrs=None) -> _ViewSpec:
-    return _ViewSpec(C.sizeof(_ViewSpec), code, int(radius), 0, _ptr(planes), _ptr(viewer_attrs), _ptr(env_attrs))
-
-
-class _ForecastSpec(C.Structure):
-    """PomForecastSpec (include/pom_batch.h): the forecast's horizon, first-tick moves and outputs"""
-    _fields_ = [
-        ("struct_size", C.c_int32), ("horizon", C.c_int32), ("reserved_", C.c_int32 * 2),
-        ("moves_dev", C.c_void_p), ("flame_tick_dev", C.c_void_p), ("agent_tick_dev", C.c_void_p), ("ubflags_dev", C.c_void_p),
-    ]
-
-
-def _forecast_spec(horizon: int, moves, flame_tick, agent_tick=None, ubflags=None) -> _ForecastSpec:
-    return _ForecastSpec(C.sizeof(_ForecastSpec), int(horizon), (C.c_int32 * 2)(0, 0), _ptr(moves), _ptr(flame_tick), _ptr(agent_tick),
-                         _ptr(ubflags))
-
-
-class _MoveSafetySpec(C.Structure):
-    """PomMoveSafetySpec (include/pom_batch.h): the horizon, whose moves are judged, the others' first-tick moves and the two outputs"""
-    _fields_ = [
-        ("struct_size", C.c_int32), ("horizon", C.c_int32), ("agent_mask", C.c_int32), ("reserved_", C.c_int32),
-        ("moves_dev", C.c_void_p), ("death_tick_dev", C.c_void_p), ("escape_tick_dev", C.c_void_p), ("reserved2_", C.c_int64),
-    ]
-
-
-class _RolloutSpec(C.Structure):
-    """PomRolloutSpec (include/pom_batch.h): the rollout's horizon, samples, move stream, first-tick moves and result"""
-    _fields_ = [
-        ("struct_size", C.c_int32), ("horizon", C.c_int32), ("samples", C.c_int32), ("dist", C.c_int32), ("seed", C.c_uint64),
-        ("moves_dev", C.c_void_p), ("result_dev", C.c_void_p), ("reserved_", C.c_int64),
-    ]
-
-
-class _RolloutPolicySpec(C.Structure):
-    """PomRolloutPolicySpec (include/pom_batch.h): the rollout's spec plus who plays SimpleAgent, whose first move is fixed, and flags"""
-    _fields_ = [
-        ("struct_size", C.c_int32), ("horizon", C.c_int32), ("samples", C.c_int32), ("dist", C.c_int32), ("seed", C.c_uint64),
-        ("moves_dev", C.c_void_p), ("result_dev", C.c_void_p), ("simple_mask", C.c_int32), ("first_mask", C.c_int32),
-        ("flags", C.c_int32), ("reserved_", C.c_int32),
-    ]
-
-
-class _RolloutJobsSpec(C.Structure):
-    """PomRolloutJobsSpec (include/pom_batch.h): the policy rollout's spec for a device-side list of (source env, tick-1 moves)"""
-    _fields_ = [
-        ("struct_size", C.c_int32), ("horizon", C.c_int32), ("samples", C.c_int32), ("dist", C.c_int32), ("seed", C.c_uint64),
-        ("jobs", C.c_int64), ("src_dev", C.c_void_p), ("moves_dev", C.c_void_p), ("result_dev", C.c_void_p),
-        ("simple_mask", C.c_int32), ("first_mask", C.c_int32), ("flags", C.c_int32), ("reserved_", C.c_int32),
-    ]
-
-
-class _ExpandSpec(C.Structure):
-    """PomExpandSpec (include/pom_batch.h): env first + j becomes the successor of env src[j] under moves[j]"""
-    _fields_ = [
-        ("struct_size", C.c_int32), ("flags", C.c_int32), ("first", C.c_int64), ("count", C.c_int64), ("src_dev", C.c_void_p),
-        ("moves_dev", C.c_void_p), ("result_dev", C.c_void_p), ("planes_dev", C.c_void_p), ("dtype", C.c_int32), ("per_agent", C.c_int32),
-        ("agent_attrs_dev", C.c_void_p), ("env_attrs_dev", C.c_void_p), ("reserved_", C.c_int64),
-    ]
-
-
-ROLLOUT_FRESH_AGENTS = 1  # POM_ROLLOUT_FRESH_AGENTS
-RO_NONE = 0  # POM_RO_NONE: rollout_jobs' word of an entry without a job
+_PLANE_CODES = {"uint8": 0, "float16": 1, "float32": 2}  # POM_OBS_U8 / F16 / F32; 3 = POM_OBS_CODES
 
 
 def _agent_mask(v, name: str) -> int:
@@ -147,10 +81,7 @@ def _agent_mask(v, name: str) -> int:
 def _rollout_args(horizon, samples, dist, moves, simple, first, fresh_agents, policy: bool = True):
     """rollout()'s and rollout_jobs()'s arguments checked: (horizon, samples, dist, simple_mask, first_mask, flags); without `policy`
     (pom_batch_rollout's playouts) the masks are 0"""
-    if not 1 <= int(horizon) <= 1024:
-        raise ValueError("horizon must be 1..1024")
-    if not 1 <= int(samples) <= 256:
-        raise ValueError("samples must be 1..256")
+    horizon, samples = _bounded(horizon, "horizon", 1, 1024), _bounded(samples, "samples", 1, 256)
     if dist not in (DIST_HARMLESS, DIST_RANDOM, DIST_STRESS):
         raise ValueError("dist must be DIST_HARMLESS, DIST_RANDOM or DIST_STRESS")
     simple_mask = first_mask = 0
@@ -159,11 +90,7 @@ def _rollout_args(horizon, samples, dist, moves, simple, first, fresh_agents, po
         first_mask = (0 if moves is None else 0xF) if first is None else _agent_mask(first, "first")
         if first_mask and moves is None:
             raise ValueError("first names agents but moves is None")
-    return int(horizon), int(samples), int(dist), simple_mask, first_mask, ROLLOUT_FRESH_AGENTS if fresh_agents else 0
-
-
-# the result word of a rollout (the header's POM_RO_*)
-RO_ALIVE, RO_DONE, RO_DRAW, RO_TIMEOUT, RO_UB, RO_WINNER_SHIFT, RO_WINNER_MASK, RO_LENGTH_SHIFT = 0xF, 0x10, 0x20, 0x40, 0x80, 8, 0x700, 16
+    return horizon, samples, int(dist), simple_mask, first_mask, ROLLOUT_FRESH_AGENTS if fresh_agents else 0
 
 
 def decode_rollout(result) -> dict:
@@ -182,91 +109,6 @@ def decode_rollout(result) -> dict:
             "ub": (w & RO_UB) != 0, "winner": i32(((w & RO_WINNER_MASK) >> RO_WINNER_SHIFT) - 1), "length": i32(w >> RO_LENGTH_SHIFT)}
 
 
-def library_path() -> str:
-    return os.environ.get("POM_LIB") or os.path.join(_HERE, "libpom_batch.so")  # POM_LIB: experimental builds only
-
-
-_lib = None
-
-
-def load_library() -> C.CDLL:
-    """Load the HIP extension built in-tree by `__graft_entry__.build()`; fail loudly if absent."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    # torch-ROCm wheels carry their own HIP runtime.  A process that is going to use both (observe(), bench.py) must load
-    # torch's first so that this library binds to the same runtime; the other order leaves torch without a device.
-    if "torch" not in sys.modules and not os.environ.get("POM_NO_TORCH"):
-        try:
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-    path = library_path()
-    if not os.path.exists(path):
-        raise ImportError(
-            f"{path} is missing: build the gfx950 extension first (python -c 'import __graft_entry__ as g; g.build()'). "
-            "pomcpp_amd has no CPU stepper to fall back to.")
-    lib = C.CDLL(path)
-    P, I32, I64, U64, VP = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_void_p
-    table = (  # (name, argtypes or None: undeclared, restype or None: int)
-        ("pom_last_error", None, C.c_char_p), ("pom_device_count", None, C.c_int),
-        ("pom_batch_create", [C.POINTER(P), I64, C.POINTER(_Options)], None), ("pom_batch_destroy", [P], None),
-        ("pom_batch_size", [P], I64),
-        ("pom_batch_observe", [P, VP, I32, I32, VP, VP], None),
-        ("pom_batch_step_device_observe", [P, VP, VP, I32, I32, VP, VP], None),
-        ("pom_batch_observe_view", [P, C.POINTER(_ViewSpec)], None),
-        ("pom_batch_step_device_observe_view", [P, VP, C.POINTER(_ViewSpec)], None),
-        ("pom_batch_step_device_range_view", [P, I64, I64, VP, VP, C.POINTER(_ViewSpec)], None),
-        ("pom_batch_forecast", [P, C.POINTER(_ForecastSpec)], None),
-        ("pom_batch_rollout", [P, C.POINTER(_RolloutSpec)], None),
-        ("pom_batch_rollout_policy", [P, C.POINTER(_RolloutPolicySpec)], None),
-        ("pom_batch_rollout_jobs", [P, C.POINTER(_RolloutJobsSpec)], None),
-        ("pom_batch_expand", [P, C.POINTER(_ExpandSpec)], None),
-        ("pom_batch_move_safety", [P, C.POINTER(_MoveSafetySpec)], None),
-        ("pom_batch_step_device_range", [P, I64, I64, VP, VP, VP, I32, I32, VP, VP], None),
-        ("pom_bench_policy", [VP, VP, I64, I64, C.c_uint32, VP], None),
-        ("pom_batch_stream", [P, C.POINTER(C.c_void_p)], None),
-        ("pom_batch_moves_device", [P, C.POINTER(C.POINTER(C.c_int32))], None),
-        ("pom_batch_generate", [P, U64], None), ("pom_batch_episodes", [P, I64, I64, VP], None),
-        ("pom_batch_upload", [P, VP, I64, I64], None), ("pom_batch_download", [P, VP, I64, I64], None),
-        ("pom_batch_snapshot", [P], None),
-        ("pom_batch_copy_envs", [P, VP, I64, I64, I32], None), ("pom_batch_copy_envs_device", [P, VP, I64, I64, I32], None),
-        ("pom_batch_step", [P, VP], None), ("pom_batch_step_device", [P, VP], None),
-        ("pom_batch_step_device_many", [P, VP, I32], None), ("pom_batch_chain_stats", [P, VP], None),
-        ("pom_batch_step_random", [P, U64, I32, I32, I32], None), ("pom_batch_set_tick", [P, I64], None),
-        ("pom_batch_policy_simple", [P, U64, VP], None), ("pom_batch_step_policy", [P], None),
-        ("pom_batch_step_simple", [P, U64, I32], None), ("pom_batch_policy_memory", [P, I64, I64, VP], None),
-        ("pom_batch_status", [P, I64, I64, VP, VP, VP, VP, VP, VP], None),
-        ("pom_batch_last_results", [P, I64, I64, VP, VP, VP, VP, VP], None),
-        ("pom_batch_download_terminal", [P, VP, I64, I64], None),
-        ("pom_batch_counters", [P, VP], None), ("pom_batch_counters_device", [P, VP], None),
-        ("pom_batch_reset_counters", [P], None), ("pom_batch_sync", [P], None), ("pom_batch_flush", [P], None),
-        ("pom_batch_fork", [P], None), ("pom_batch_set_streams", [P, I32], None), ("pom_batch_profile", [P, C.c_int], None),
-        ("pom_batch_profile_read", [P, C.POINTER(C.c_double), C.POINTER(I64)], None),
-        ("pom_batch_launch_shape", [P, C.POINTER(I32), C.POINTER(I32), C.POINTER(I32)], None),
-        ("pom_batch_issue_info", [P, C.POINTER(I32), C.POINTER(I32)], None),
-        ("pom_batch_device_view", [P, C.POINTER(VP), C.POINTER(I64), C.POINTER(I32)], None),
-        ("pom_chain_litmus", [I32, I64, I32, I32, VP], None),
-        ("pom_step", [VP, VP], None), ("pom_env_step", [VP, VP, I32, VP, VP, VP, VP], None),
-    )
-    lenient = bool(os.environ.get("POM_LIB"))  # an older experimental build may lack the newer calls: a missing symbol is skipped
-    for name, argtypes, restype in table:
-        if lenient and not hasattr(lib, name):
-            continue
-        fn = getattr(lib, name)  # (the project's own library: a missing symbol raises)
-        if argtypes is not None:
-            fn.argtypes = argtypes
-        if restype is not None:
-            fn.restype = restype
-    _lib = lib
-    return lib
-
-
-def _check(lib, rc: int) -> None:
-    if rc != 0:
-        raise PomError(rc, lib.pom_last_error().decode(errors="replace"))
-
-
 def chain_litmus(tiles: int, launches: int, streams: int, device: int = 0) -> dict:
     """pom_chain_litmus: the hand-off of chained launches tested by itself (every visit checks the whole record the visit before
     left)"""
@@ -276,13 +118,18 @@ def chain_litmus(tiles: int, launches: int, streams: int, device: int = 0) -> di
     return dict(zip(("bad_records", "bad_dwords", "visits", "visits_expected", "tiles_wrong", "flags"), (int(v) for v in out)))
 
 
-def step_one(state: np.ndarray, moves) -> None:
-    """`bboard::Step(State*, Move*)` on one host State, executed on the GPU (pom_step)."""
-    lib = load_library()
+def _one_state(state: np.ndarray, moves):
+    """step_one's and env_step_one's arguments as the buffers the library takes"""
     assert state.dtype == STATE_DTYPE and state.size == 1
     mv = np.ascontiguousarray(moves, dtype=np.int32)
     assert mv.shape == (4,)
-    buf = np.ascontiguousarray(state).reshape(1)
+    return np.ascontiguousarray(state).reshape(1), mv
+
+
+def step_one(state: np.ndarray, moves) -> None:
+    """`bboard::Step(State*, Move*)` on one host State, executed on the GPU (pom_step)."""
+    lib = load_library()
+    buf, mv = _one_state(state, moves)
     _check(lib, lib.pom_step(buf.ctypes.data, mv.ctypes.data))
     state[...] = buf.reshape(state.shape)
 
@@ -291,10 +138,7 @@ def env_step_one(state: np.ndarray, moves, max_steps: int = 0) -> dict:
     """`Environment::Step`'s tick + bookkeeping on one host State (pom_env_step): timeStep++, done / winner / draw of this
     tick.  The caller does not step a finished game (environment.cpp:125)."""
     lib = load_library()
-    assert state.dtype == STATE_DTYPE and state.size == 1
-    mv = np.ascontiguousarray(moves, dtype=np.int32)
-    assert mv.shape == (4,)
-    buf = np.ascontiguousarray(state).reshape(1)
+    buf, mv = _one_state(state, moves)
     out = np.zeros(4, dtype=np.int32)
     _check(lib, lib.pom_env_step(buf.ctypes.data, mv.ctypes.data, int(max_steps), out[0:].ctypes.data, out[1:].ctypes.data,
                                  out[2:].ctypes.data, out[3:].ctypes.data))
@@ -313,8 +157,8 @@ class BatchEnvironment:
         self._tapes = []  # move tapes handed to step_device_many, kept alive until the handle has been synchronised
         self.n = int(n_envs)
         self.device = int(device)
-        o = _Options(C.sizeof(_Options), device, stream, mode, int(auto_reset), max_steps, env_offset, envs_per_wave, streams,
-                     lanes_per_env, int(fresh_boards), board_seed, issue_mode, 0)
+        o = _spec(_Options, device, stream, mode, int(auto_reset), max_steps, env_offset, envs_per_wave, streams, lanes_per_env,
+                  int(fresh_boards), board_seed, issue_mode, 0)
         _check(self._lib, self._lib.pom_batch_create(C.byref(self._h), self.n, C.byref(o)))
 
     def close(self) -> None:
@@ -338,19 +182,34 @@ class BatchEnvironment:
     def __exit__(self, *exc):
         self.close()
 
-    # ---- what the calls that take device tensors share -----------------------------------------------
+    # ---- what the calls share --------------------------------------------------------------------------
+    def _call(self, name: str, *args) -> None:
+        """the library's `name` on this handle; anything but POM_OK raises PomError with the library's text"""
+        rc = getattr(self._lib, name)(self._h, *args)
+        if rc:
+            _check(self._lib, rc)
+
+    def _span(self, first, count):
+        """(first, count) of the calls that read a range of envs: no count means all from `first` on"""
+        return first, self.n - first if count is None else count
+
+    def _in_batch(self, first, count):
+        """the range [first, first + count) as ints, refused unless it lies in the batch"""
+        first, count = int(first), int(count)
+        if first < 0 or count < 0 or first + count > self.n:
+            raise ValueError(f"the range [{first}, {first + count}) lies outside the batch of {self.n} envs")
+        return first, count
+
     def _device_tensor(self, t, what: str, dtype, shape):
         """`t` as an argument that a kernel reads or writes through its address: anything with data_ptr / shape / dtype (e.g. a torch
-        tensor) of element type `dtype` (a name such as "int32", or a torch dtype) and of `shape` (None: a free dimension), contiguous
+        tensor) of the element type named `dtype` (such as "int32") and of `shape` (None: a free dimension), contiguous
         and on this handle's device; contiguity and device are checked where the object tells them.  Returns `t`."""
-        dtype = str(dtype).rsplit(".", 1)[-1]
-        want = f"{dtype}[{', '.join('*' if w is None else str(w) for w in shape)}]"
         if not hasattr(t, "data_ptr"):
-            raise ValueError(f"{what} must be a device tensor {want}, got {type(t).__name__}")
+            raise ValueError(f"{what} must be a device tensor {self._want(dtype, shape)}, got {type(t).__name__}")
         got = tuple(getattr(t, "shape", ()))
         if len(got) != len(shape) or any(w is not None and w != g for w, g in zip(shape, got)):
-            raise ValueError(f"{what} must be {want}, got shape {got}")
-        if str(getattr(t, "dtype", "")).rsplit(".", 1)[-1] != dtype:
+            raise ValueError(f"{what} must be {self._want(dtype, shape)}, got shape {got}")
+        if _dtype_name(getattr(t, "dtype", "")) != dtype:
             raise ValueError(f"{what} must be {dtype}, got {getattr(t, 'dtype', None)}")
         if hasattr(t, "is_contiguous") and not t.is_contiguous():
             raise ValueError(f"{what} must be contiguous")
@@ -359,12 +218,92 @@ class BatchEnvironment:
             raise ValueError(f"{what} lives on {dev}, the batch on device {self.device}")
         return t
 
+    @staticmethod
+    def _want(dtype: str, shape) -> str:
+        return f"{dtype}[{', '.join('*' if w is None else str(w) for w in shape)}]"
+
+    def _moves(self, moves, raw: bool = False, shape=None):
+        """the moves argument, int32 of `shape` ([n, 4] unless given), checked; returns its address (None: NULL).  With `raw` anything
+        that is no tensor is a device address the caller vouches for."""
+        if moves is None:
+            return None
+        if raw and not hasattr(moves, "data_ptr"):
+            return int(moves)
+        return self._device_tensor(moves, "moves", "int32", shape or (self.n, 4)).data_ptr()
+
+    def _torch_device(self):
+        """(torch, this handle's device as torch names it)"""
+        import torch
+        return torch, torch.device("cuda", self.device)
+
+    def _new(self, shape, dtype: str):
+        """a new tensor of the element type named `dtype` on the handle's device: the one place a call's result is allocated"""
+        torch, dev = self._torch_device()
+        return torch.empty(shape, dtype=getattr(torch, dtype), device=dev)
+
+    def _new_attrs(self, width: int):
+        """new (agent_attrs or viewer_attrs, env_attrs) for an observation"""
+        return self._new((self.n, 4, width), "int32"), self._new((self.n, 4), "int32")
+
     def _out_tensor(self, out, shape, dtype, what: str = "out"):
         """the tensor a call writes its result to: a new one, or the caller's `out` of an earlier call, checked"""
-        if out is None:
-            import torch
-            return torch.empty(shape, dtype=dtype, device=torch.device("cuda", self.device))
-        return self._device_tensor(out, what, dtype, shape)
+        return self._new(shape, dtype) if out is None else self._device_tensor(out, what, dtype, shape)
+
+    def _outputs(self, out, want: dict, fill=None) -> dict:
+        """a call's dict of outputs, `want` = {name: (shape, dtype)}: each the tensor under that name in the caller's `out`, checked,
+        or a new one (set to `fill` where that is given)"""
+        res = {}
+        for name, (shape, dtype) in want.items():
+            given = None if out is None else out.get(name)
+            res[name] = self._out_tensor(given, shape, dtype, f"out[{name!r}]")
+            if given is None and fill is not None:
+                res[name].fill_(fill)
+        return res
+
+    def _observation(self, codes=None, planes=None, per_agent=None, view_radius=None, viewer_attrs=None, agent_attrs=None,
+                     env_attrs=None, *, raw: bool = False, dtype=None, out=None):
+        """The rules of an observation request (pom_api_observe.h's observe_args and view_args), stated once for observe(),
+        step_device_observe(), step_device_range() and expand().  The layout is given as `codes` or `planes` (the element type is the
+        tensor's, read by name), or as observe()'s `dtype` name with an optional `out`; with `raw` anything that is no tensor is a
+        device address the caller vouches for (planes then are uint8).  Contradictions and wrong tensors are refused with a ValueError;
+        no torch, no runtime call.  Returns a plain tuple, what every caller needs first (this is on the closed loop's host path, where
+        a named tuple costs half a microsecond a call): (the tensor or address the planes go to — None: to be allocated, or no
+        observation —, the library's dtype code, per_agent, view: these are the fogged views, the width of agent_attrs (8) or
+        viewer_attrs (12) — int32 [n, 4, width], env_attrs int32 [n, 4] —, the planes' shape, their element type by name)."""
+        view = view_radius is not None
+        if codes is not None and planes is not None:
+            raise ValueError("codes and planes are two forms of one observation: pass one")
+        if dtype is None:
+            out, name, is_codes = (codes, "codes", True) if codes is not None else (planes, "planes", False)
+            checked = hasattr(out, "data_ptr") or (out is not None and not raw)
+            dtype = "uint8" if is_codes or not checked else _dtype_name(getattr(out, "dtype", ""))
+            if dtype not in _PLANE_CODES:
+                raise ValueError(f"planes must be uint8, float16 or float32, got {getattr(out, 'dtype', None)}")
+        else:
+            name, is_codes, checked = "out", dtype == "codes", out is not None
+            if not is_codes and dtype not in _PLANE_CODES:
+                raise ValueError(f"dtype must be one of {sorted([*_PLANE_CODES, 'codes'])}")
+            dtype = "uint8" if is_codes else dtype
+        if per_agent and is_codes and not view:
+            raise ValueError("the codes layout has no per-agent view (but for the fogged ones: view_radius)")
+        if view and per_agent is not None and not per_agent:
+            raise ValueError("view_radius gives every agent its own view: per_agent=False contradicts it")
+        if view:
+            _bounded(view_radius, "view_radius", 0, 10)
+        if viewer_attrs is not None and not view:
+            raise ValueError("viewer_attrs are written with the fogged views only: pass view_radius")
+        if agent_attrs is not None and view:
+            raise ValueError("agent_attrs are written with the plain observation only: the fogged views have viewer_attrs")
+        per_agent, depth, width = bool(per_agent) or view, 5 if is_codes else 16, 12 if view else 8
+        shape = (self.n, 4, depth, 11, 11) if per_agent else (self.n, depth, 11, 11)
+        if checked:
+            self._device_tensor(out, name, dtype, shape)
+        if viewer_attrs is not None or agent_attrs is not None or env_attrs is not None:
+            for t, what, want in ((viewer_attrs, "viewer_attrs", (self.n, 4, width)), (agent_attrs, "agent_attrs", (self.n, 4, width)),
+                                  (env_attrs, "env_attrs", (self.n, 4))):
+                if hasattr(t, "data_ptr"):
+                    self._device_tensor(t, what, "int32", want)
+        return out, 3 if is_codes else _PLANE_CODES[dtype], per_agent, view, width, shape, dtype
 
     @contextlib.contextmanager
     def _ordered(self, back: bool = True, tensor=None):
@@ -375,8 +314,7 @@ class BatchEnvironment:
         if "torch" not in sys.modules or (tensor is not None and not hasattr(tensor, "is_cuda")):
             yield
             return
-        import torch
-        dev = torch.device("cuda", self.device)
+        torch, dev = self._torch_device()
         mine, theirs = torch.cuda.ExternalStream(self.stream_handle(), device=dev), torch.cuda.current_stream(dev)
         if mine.cuda_stream != theirs.cuda_stream:
             mine.wait_stream(theirs)
@@ -388,32 +326,32 @@ class BatchEnvironment:
     def make_game(self, states: np.ndarray, first: int = 0) -> None:
         """Upload start states; they also become the reset snapshot (MakeGame, environment.cpp:53-66)."""
         st = np.ascontiguousarray(states, dtype=STATE_DTYPE)
-        _check(self._lib, self._lib.pom_batch_upload(self._h, st.ctypes.data, first, st.size))
+        self._call("pom_batch_upload", st.ctypes.data, first, st.size)
 
     upload = make_game
 
     def generate(self, board_seed: int) -> None:
         """Start boards drawn on the device (pom_batch_generate, include/pom_boardgen.h): InitState's distribution, no host."""
-        _check(self._lib, self._lib.pom_batch_generate(self._h, board_seed))
+        self._call("pom_batch_generate", board_seed)
 
     def episodes(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
         """games started so far per env (0 = still the first)"""
-        count = self.n - first if count is None else count
+        first, count = self._span(first, count)
         out = np.zeros(count, dtype=np.uint32)
-        _check(self._lib, self._lib.pom_batch_episodes(self._h, first, count, out.ctypes.data))
+        self._call("pom_batch_episodes", first, count, out.ctypes.data)
         return out
 
     def get_state(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
-        count = self.n - first if count is None else count
+        first, count = self._span(first, count)
         out = np.zeros(count, dtype=STATE_DTYPE)
-        _check(self._lib, self._lib.pom_batch_download(self._h, out.ctypes.data, first, count))
+        self._call("pom_batch_download", out.ctypes.data, first, count)
         self._tapes.clear()  # the call has synchronised the handle: nothing reads a tape any more
         return out
 
     download = get_state
 
     def snapshot(self) -> None:
-        _check(self._lib, self._lib.pom_batch_snapshot(self._h))
+        self._call("pom_batch_snapshot")
 
     # ---- copy / restore games by index (tree search, rollouts, populations) ---------------------------
     def copy_envs(self, src, first: int = 0, *, from_snapshot: bool = False, set_snapshot: bool = False,
@@ -429,11 +367,11 @@ class BatchEnvironment:
         if hasattr(src, "data_ptr"):
             self._device_tensor(src, "src", "int64", (count,))
             with self._ordered(back=False, tensor=src):
-                _check(self._lib, self._lib.pom_batch_copy_envs_device(self._h, src.data_ptr(), int(first), src.shape[0], flags))
+                self._call("pom_batch_copy_envs_device", src.data_ptr(), int(first), src.shape[0], flags)
         elif isinstance(src, (int, np.integer)) and not isinstance(src, bool):
             if count is None:
                 raise ValueError("a raw device address needs `count`")
-            _check(self._lib, self._lib.pom_batch_copy_envs_device(self._h, int(src), int(first), int(count), flags))
+            self._call("pom_batch_copy_envs_device", int(src), int(first), int(count), flags)
         else:
             idx = np.asarray(src)
             if idx.ndim != 1 or not np.issubdtype(idx.dtype, np.integer):
@@ -441,7 +379,7 @@ class BatchEnvironment:
             idx = np.ascontiguousarray(idx, dtype=np.int64)
             if count is not None and count != idx.size:
                 raise ValueError(f"count {count} does not match src of {idx.size} entries")
-            _check(self._lib, self._lib.pom_batch_copy_envs(self._h, idx.ctypes.data, int(first), idx.size, flags))
+            self._call("pom_batch_copy_envs", idx.ctypes.data, int(first), idx.size, flags)
 
     def restore(self, envs) -> None:
         """Put the given envs back on their restart snapshot with fresh agents: a boolean mask of n, or a list of env indices.
@@ -468,21 +406,20 @@ class BatchEnvironment:
         mv = np.ascontiguousarray(moves, dtype=np.int32)
         if mv.shape != (self.n, 4):
             raise ValueError(f"moves must be int32[{self.n}, 4] (dead agents included), got {mv.shape}")
-        _check(self._lib, self._lib.pom_batch_step(self._h, mv.ctypes.data))
+        self._call("pom_batch_step", mv.ctypes.data)
 
     def step_device(self, moves) -> None:
         """moves: a device tensor int32[n,4] on this handle's device (anything with data_ptr / shape / dtype, e.g. a torch
         tensor: shape, element type, contiguity and device are checked), or the raw device address of such an array."""
-        if hasattr(moves, "data_ptr"):
-            self._device_tensor(moves, "moves", "int32", (self.n, 4))
+        ptr = self._moves(moves, raw=True)
         with self._ordered(back=False, tensor=moves):
-            _check(self._lib, self._lib.pom_batch_step_device(self._h, _ptr(moves)))
+            self._call("pom_batch_step_device", ptr)
 
     def step_device_many(self, moves, ticks: Optional[int] = None) -> None:
         """K ticks with explicit moves from a tape in device memory: a tensor int32[K, n, 4] on this handle's device (or the raw
         device address of one, with `ticks` = K).  Chained launches where the handle chains (pom_batch_step_device_many)."""
+        ptr = self._moves(moves, raw=True, shape=(ticks, self.n, 4))
         if hasattr(moves, "data_ptr"):
-            self._device_tensor(moves, "moves", "int32", (ticks, self.n, 4))
             ticks = moves.shape[0]
             # the tape is read asynchronously and must stay unchanged until the handle has been synchronised: keep the tensor (and
             # with it its memory) alive until then, whatever the caller does with its own reference
@@ -492,7 +429,7 @@ class BatchEnvironment:
         if ticks is None:
             raise ValueError("a raw device address needs `ticks`")
         with self._ordered(back=False, tensor=moves):
-            _check(self._lib, self._lib.pom_batch_step_device_many(self._h, _ptr(moves), int(ticks)))
+            self._call("pom_batch_step_device_many", ptr, int(ticks))
 
     def step_device_range(self, first: int, count: int, moves, stream=None, codes=None, planes=None, view_radius: Optional[int] = None,
                           viewer_attrs=None, env_attrs=None, *, per_agent: Optional[bool] = None, agent_attrs=None) -> None:
@@ -509,102 +446,73 @@ class BatchEnvironment:
         the batch, `codes` together with `planes`, `per_agent` with `codes` and attribute arrays that nothing would write are refused,
         all with a ValueError before anything is launched; a raw device address passes unchecked (planes then are uint8).  The checks
         make no runtime call."""
-        first, count, view = int(first), int(count), view_radius is not None
-        if first < 0 or count < 0 or first + count > self.n:
-            raise ValueError(f"the range [{first}, {first + count}) lies outside the batch of {self.n} envs")
-        if codes is not None and planes is not None:
-            raise ValueError("codes and planes are two forms of one observation: pass one")
-        if per_agent and codes is not None and not view:
-            raise ValueError("the codes layout has no per-agent view (but for the fogged ones: view_radius)")
-        if view and per_agent is not None and not per_agent:
-            raise ValueError("view_radius gives every agent its own view: per_agent=False contradicts it")
-        if view and not 0 <= int(view_radius) <= 10:
-            raise ValueError("view_radius must be 0..10")
-        if viewer_attrs is not None and not view:
-            raise ValueError("viewer_attrs are written with the fogged views only: pass view_radius")
-        if agent_attrs is not None and view:
-            raise ValueError("agent_attrs are written with the plain observation only: the fogged views have viewer_attrs")
-        out, name, code = (codes, "codes", 3) if codes is not None else (planes, "planes", 0)
-        if out is None and (view or per_agent or agent_attrs is not None or env_attrs is not None):
+        first, count = self._in_batch(first, count)
+        out, code, per_agent, view, _width, _shape, _dtype = self._observation(codes, planes, per_agent, view_radius, viewer_attrs, agent_attrs,
+                                                                                env_attrs, raw=True)
+        if out is None and (per_agent or agent_attrs is not None or env_attrs is not None):
             raise ValueError("view_radius, per_agent, agent_attrs and env_attrs belong to an observation: pass `codes` or `planes`")
-        per_agent = bool(per_agent) or view
-        if hasattr(moves, "data_ptr"):
-            self._device_tensor(moves, "moves", "int32", (self.n, 4))
-        if hasattr(out, "data_ptr"):
-            dtype = "uint8"
-            if codes is None:
-                dtype = str(getattr(planes, "dtype", "")).rsplit(".", 1)[-1]
-                code = {"uint8": 0, "float16": 1, "float32": 2}.get(dtype)
-                if code is None:
-                    raise ValueError(f"planes must be uint8, float16 or float32, got {getattr(planes, 'dtype', None)}")
-            self._device_tensor(out, name, dtype, (self.n,) + ((4,) if per_agent else ()) + (5 if codes is not None else 16, 11, 11))
-        for t, what, width in ((viewer_attrs, "viewer_attrs", 12), (agent_attrs, "agent_attrs", 8), (env_attrs, "env_attrs", None)):
-            if hasattr(t, "data_ptr"):
-                self._device_tensor(t, what, "int32", (self.n, 4) + (() if width is None else (width,)))
-        st = getattr(stream, "cuda_stream", stream)
+        ptr, st = self._moves(moves, raw=True), getattr(stream, "cuda_stream", stream)
         if view:
             spec = _view_spec(code, view_radius, out, viewer_attrs, env_attrs)
-            _check(self._lib, self._lib.pom_batch_step_device_range_view(self._h, first, count, _ptr(moves), st, C.byref(spec)))
-            return
-        _check(self._lib, self._lib.pom_batch_step_device_range(self._h, first, count, _ptr(moves), st, _ptr(out), code, int(per_agent), _ptr(agent_attrs),
-                                                                _ptr(env_attrs)))
+            self._call("pom_batch_step_device_range_view", first, count, ptr, st, C.byref(spec))
+        else:
+            self._call("pom_batch_step_device_range", first, count, ptr, st, _ptr(out), code, int(per_agent), _ptr(agent_attrs), _ptr(env_attrs))
 
     def chain_stats(self) -> dict:
         """chained launches since creation: launches issued, checks run, tiles found left behind, ticks replayed for them"""
         out = np.zeros(4, dtype=np.int64)
-        _check(self._lib, self._lib.pom_batch_chain_stats(self._h, out.ctypes.data))
+        self._call("pom_batch_chain_stats", out.ctypes.data)
         return dict(zip(("launches", "settles", "tiles_recovered", "ticks_replayed"), (int(v) for v in out)))
 
     def step_random(self, seed: int, dist: int = DIST_RANDOM, ticks: int = 1, ticks_per_launch: int = 1) -> None:
-        _check(self._lib, self._lib.pom_batch_step_random(self._h, seed, dist, ticks, ticks_per_launch))
+        self._call("pom_batch_step_random", seed, dist, ticks, ticks_per_launch)
 
     # ---- SimpleAgent policy on the device (agents::SimpleAgent) -------------------------------------
     def policy_simple(self, seed: int, want_moves: bool = False):
         """act() of all four agents of every env into the internal move buffer; optionally returns int32[n,4]."""
         out = np.zeros((self.n, 4), dtype=np.int32) if want_moves else None
-        _check(self._lib, self._lib.pom_batch_policy_simple(self._h, seed, out.ctypes.data if want_moves else None))
+        self._call("pom_batch_policy_simple", seed, out.ctypes.data if want_moves else None)
         return out
 
     def step_policy(self) -> None:
-        _check(self._lib, self._lib.pom_batch_step_policy(self._h))
+        self._call("pom_batch_step_policy")
 
     def step_simple(self, seed: int, ticks: int = 1) -> None:
-        _check(self._lib, self._lib.pom_batch_step_simple(self._h, seed, ticks))
+        self._call("pom_batch_step_simple", seed, ticks)
 
     def policy_memory(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
-        count = self.n - first if count is None else count
+        first, count = self._span(first, count)
         out = np.zeros((count, 4, 16), dtype=np.int32)
-        _check(self._lib, self._lib.pom_batch_policy_memory(self._h, first, count, out.ctypes.data))
+        self._call("pom_batch_policy_memory", first, count, out.ctypes.data)
         return out
 
     def set_tick(self, tick: int) -> None:
-        _check(self._lib, self._lib.pom_batch_set_tick(self._h, tick))
+        self._call("pom_batch_set_tick", tick)
 
     # ---- IsDone / IsDraw / GetWinner ------------------------------------------------------------
-    def status(self, first: int = 0, count: Optional[int] = None) -> dict:
-        count = self.n - first if count is None else count
-        names = ["done", "winner", "draw", "alive", "time_step", "ubflags"]
+    def _int32_columns(self, name: str, names, first, count) -> dict:
+        """the library's `name` read into one int32[count] array per entry of `names`"""
+        first, count = self._span(first, count)
         arrs = [np.zeros(count, dtype=np.int32) for _ in names]
-        _check(self._lib, self._lib.pom_batch_status(self._h, first, count, *[a.ctypes.data for a in arrs]))
+        self._call(name, first, count, *[a.ctypes.data for a in arrs])
+        return dict(zip(names, arrs))
+
+    def status(self, first: int = 0, count: Optional[int] = None) -> dict:
+        out = self._int32_columns("pom_batch_status", ("done", "winner", "draw", "alive", "time_step", "ubflags"), first, count)
         self._tapes.clear()
-        out = dict(zip(names, arrs))
         out["ubflags"] = out["ubflags"].view(np.uint32)
         return out
 
     def last_results(self, first: int = 0, count: Optional[int] = None) -> dict:
         """auto_reset=RESET_AT_END: `finished` = the env's latest tick ended an episode (it now stands on its next start state);
         winner / draw / length / alive describe the env's most recently finished episode."""
-        count = self.n - first if count is None else count
-        names = ["finished", "winner", "draw", "length", "alive"]
-        arrs = [np.zeros(count, dtype=np.int32) for _ in names]
-        _check(self._lib, self._lib.pom_batch_last_results(self._h, first, count, *[a.ctypes.data for a in arrs]))
-        return dict(zip(names, arrs))
+        return self._int32_columns("pom_batch_last_results", ("finished", "winner", "draw", "length", "alive"), first, count)
 
     def get_terminal_state(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
         """auto_reset=RESET_AT_END: the final State of each env's most recently finished episode (zeros: none yet)"""
-        count = self.n - first if count is None else count
+        first, count = self._span(first, count)
         out = np.zeros(count, dtype=STATE_DTYPE)
-        _check(self._lib, self._lib.pom_batch_download_terminal(self._h, out.ctypes.data, first, count))
+        self._call("pom_batch_download_terminal", out.ctypes.data, first, count)
         return out
 
     def is_done(self) -> np.ndarray:
@@ -634,40 +542,17 @@ class BatchEnvironment:
         the window around itself, fog elsewhere.  Returns (planes, viewer_attrs, env_attrs): planes [n,4,16,11,11], all-zero cells
         outside the window, or for "codes" [n,4,5,11,11] with board code 5 (fog) outside it; viewer_attrs int32 [n,4,12] = the
         viewer's own agent_attrs row, the alive flags of the next three agents, the time step.  per_agent is implied."""
-        import torch
-        if view_radius is not None and per_agent is not None and not per_agent:
-            raise ValueError("view_radius gives every agent its own view: per_agent=False contradicts it")
-        per_agent = bool(per_agent)
-        kinds = {"uint8": (0, torch.uint8), "float16": (1, torch.float16), "float32": (2, torch.float32), "codes": (3, torch.uint8)}
-        if dtype not in kinds:
-            raise ValueError(f"dtype must be one of {sorted(kinds)}")
-        if dtype == "codes" and per_agent and view_radius is None:
-            raise ValueError("the codes layout has no per-agent view (but for the fogged ones: view_radius)")
-        view = view_radius is not None
-        if view and not 0 <= int(view_radius) <= 10:
-            raise ValueError("view_radius must be 0..10")
-        code, tdt = kinds[dtype]
-        dev = torch.device("cuda", self.device)
-        shape = (self.n, 5, 11, 11) if dtype == "codes" else (self.n, 4, 16, 11, 11) if per_agent or view else (self.n, 16, 11, 11)
-        if view:
-            shape = (self.n, 4) + shape[-3:]
-        out = self._out_tensor(out, shape, tdt)
-        a_attrs = torch.empty((self.n, 4, 12 if view else 8), dtype=torch.int32, device=dev) if attrs else None
-        e_attrs = torch.empty((self.n, 4), dtype=torch.int32, device=dev) if attrs else None
-        if _step_moves is not None:
-            self._device_tensor(_step_moves, "moves", "int32", (self.n, 4))
+        out, code, per_agent, view, width, shape, elem = self._observation(per_agent=per_agent, view_radius=view_radius, dtype=dtype, out=out)
+        if out is None:
+            out = self._new(shape, elem)
+        a_attrs, e_attrs = self._new_attrs(width) if attrs else (None, None)
+        step = () if _step_moves is None else (self._moves(_step_moves),)
+        name = "pom_batch_observe" if _step_moves is None else "pom_batch_step_device_observe"
         with self._ordered():
             if view:
-                spec = _view_spec(code, view_radius, out, a_attrs, e_attrs)
-                if _step_moves is not None:
-                    _check(self._lib, self._lib.pom_batch_step_device_observe_view(self._h, _step_moves.data_ptr(), C.byref(spec)))
-                else:
-                    _check(self._lib, self._lib.pom_batch_observe_view(self._h, C.byref(spec)))
-            elif _step_moves is not None:
-                _check(self._lib, self._lib.pom_batch_step_device_observe(self._h, _step_moves.data_ptr(), out.data_ptr(), code, int(per_agent),
-                                                                          _ptr(a_attrs), _ptr(e_attrs)))
+                self._call(name + "_view", *step, C.byref(_view_spec(code, view_radius, out, a_attrs, e_attrs)))
             else:
-                _check(self._lib, self._lib.pom_batch_observe(self._h, out.data_ptr(), code, int(per_agent), _ptr(a_attrs), _ptr(e_attrs)))
+                self._call(name, *step, out.data_ptr(), code, int(per_agent), _ptr(a_attrs), _ptr(e_attrs))
         return out, a_attrs, e_attrs
 
     # ---- forecast: flames and deaths K ticks ahead (pom_batch_forecast) ---------------------------------
@@ -680,20 +565,16 @@ class BatchEnvironment:
         in, 0 alive at the end); with ubflags `ubflags` (int32 [n] holding the header's uint32 bit mask of the POM_UB_* flags the
         forecast ticks raised: test bits, do not compare signed values).  `out`: a dict
         with tensors of an earlier call under the same names, written in place of new ones."""
-        import torch
-        if not 1 <= int(horizon) <= 32:
-            raise ValueError("horizon must be 1..32")
-        want = {"flame_tick": ((self.n, 11, 11), torch.uint8)}
+        horizon = _lookahead(horizon)
+        want = {"flame_tick": ((self.n, 11, 11), "uint8")}
         if agent_ticks:
-            want["agent_tick"] = ((self.n, 4), torch.int32)
+            want["agent_tick"] = ((self.n, 4), "int32")
         if ubflags:
-            want["ubflags"] = ((self.n,), torch.int32)
-        res = {name: self._out_tensor(None if out is None else out.get(name), shape, tdt, f"out[{name!r}]") for name, (shape, tdt) in want.items()}
-        if moves is not None:
-            self._device_tensor(moves, "moves", "int32", (self.n, 4))
+            want["ubflags"] = ((self.n,), "int32")
+        res = self._outputs(out, want)
+        self._moves(moves)
         with self._ordered():
-            spec = _forecast_spec(horizon, moves, res["flame_tick"], res.get("agent_tick"), res.get("ubflags"))
-            _check(self._lib, self._lib.pom_batch_forecast(self._h, C.byref(spec)))
+            self._call("pom_batch_forecast", C.byref(_forecast_spec(horizon, moves, res["flame_tick"], res.get("agent_tick"), res.get("ubflags"))))
         return res
 
     # ---- move safety: every agent's six moves judged in one launch (pom_batch_move_safety) ------------------
@@ -708,27 +589,18 @@ class BatchEnvironment:
         walker that started with the move has no free cell left to stand on, 0 there still is one when the horizon ends: the header
         defines it exactly).  `out`: a dict with tensors of an earlier call under the same names, written in place of new ones.  The
         rows of agents not asked for are -1 in a tensor this call allocates and left as they were in a caller's."""
-        import torch
-        if not 1 <= int(horizon) <= 32:
-            raise ValueError("horizon must be 1..32")
+        horizon = _lookahead(horizon)
         mask = 0xF if agents is None else _agent_mask(agents, "agents")
         if mask == 0:
             raise ValueError("agents names nobody")
-        names = [name for name, wanted in (("death_tick", death), ("escape_tick", escape)) if wanted]
-        if not names:
+        want = {name: ((self.n, 4, 6), "int8") for name, wanted in (("death_tick", death), ("escape_tick", escape)) if wanted}
+        if not want:
             raise ValueError("death and escape are both False: nothing to compute")
-        res = {}
-        for name in names:
-            given = None if out is None else out.get(name)
-            res[name] = self._out_tensor(given, (self.n, 4, 6), torch.int8, f"out[{name!r}]")
-            if given is None and mask != 0xF:
-                res[name].fill_(-1)
-        if moves is not None:
-            self._device_tensor(moves, "moves", "int32", (self.n, 4))
+        res = self._outputs(out, want, fill=None if mask == 0xF else -1)
+        self._moves(moves)
         with self._ordered():
-            spec = _MoveSafetySpec(C.sizeof(_MoveSafetySpec), int(horizon), mask, 0, _ptr(moves), _ptr(res.get("death_tick")),
-                                   _ptr(res.get("escape_tick")), 0)
-            _check(self._lib, self._lib.pom_batch_move_safety(self._h, C.byref(spec)))
+            spec = _spec(_MoveSafetySpec, horizon, mask, 0, _ptr(moves), _ptr(res.get("death_tick")), _ptr(res.get("escape_tick")), 0)
+            self._call("pom_batch_move_safety", C.byref(spec))
         return res
 
     def safe_moves(self, horizon: int, agents=None, moves=None):
@@ -750,20 +622,15 @@ class BatchEnvironment:
         iterable of agent ids) names the agents that play SimpleAgent, starting from a copy per sample of the memory policy_memory()
         reports (`fresh_agents`: from new agents); the others draw from `dist`.  `first` (likewise) names the agents whose move of
         tick 1 is `moves[e][a]`; with `moves` given and `first` not, all four are."""
-        import torch
         with_policy = simple is not None or first is not None or bool(fresh_agents)
         horizon, samples, dist, simple_mask, first_mask, flags = _rollout_args(horizon, samples, dist, moves, simple, first, fresh_agents, with_policy)
-        out = self._out_tensor(out, (samples, self.n), torch.int32)
-        if moves is not None:
-            self._device_tensor(moves, "moves", "int32", (self.n, 4))
+        out = self._out_tensor(out, (samples, self.n), "int32")
+        common = horizon, samples, dist, _u64(seed), self._moves(moves), out.data_ptr()
         with self._ordered():
             if with_policy:
-                spec = _RolloutPolicySpec(C.sizeof(_RolloutPolicySpec), horizon, samples, dist, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(moves),
-                                          out.data_ptr(), simple_mask, first_mask, flags, 0)
-                _check(self._lib, self._lib.pom_batch_rollout_policy(self._h, C.byref(spec)))
+                self._call("pom_batch_rollout_policy", C.byref(_spec(_RolloutPolicySpec, *common, simple_mask, first_mask, flags, 0)))
             else:
-                spec = _RolloutSpec(C.sizeof(_RolloutSpec), horizon, samples, dist, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(moves), out.data_ptr(), 0)
-                _check(self._lib, self._lib.pom_batch_rollout(self._h, C.byref(spec)))
+                self._call("pom_batch_rollout", C.byref(_spec(_RolloutSpec, *common, 0)))
         return out
 
     # ---- rollout of a list of jobs (pom_batch_rollout_jobs) ----------------------------------------------
@@ -777,17 +644,14 @@ class BatchEnvironment:
         source env, so jobs of one source play under common random numbers and differ only through their first moves.
         `simple`, `first`, `fresh_agents`, `out`: as rollout() (the playouts are always pom_batch_rollout_policy's; with none of
         the three given: random playouts, all four tick-1 moves from `moves` if it is given)."""
-        import torch
         horizon, samples, dist, simple_mask, first_mask, flags = _rollout_args(horizon, samples, dist, moves, simple, first, fresh_agents)
         m = int(self._device_tensor(src, "src", "int64", (None,)).shape[0])
-        out = self._out_tensor(out, (samples, m), torch.int32)
-        if moves is not None:
-            self._device_tensor(moves, "moves", "int32", (m, 4))
+        out = self._out_tensor(out, (samples, m), "int32")
+        self._moves(moves, shape=(m, 4))
         with self._ordered():
-            spec = _RolloutJobsSpec(C.sizeof(_RolloutJobsSpec), horizon, samples, dist, int(seed) & 0xFFFFFFFFFFFFFFFF, m,
-                                    src.data_ptr() if m else None, _ptr(moves) if m else None, out.data_ptr() if m else None, simple_mask,
-                                    first_mask if m else 0, flags, 0)
-            _check(self._lib, self._lib.pom_batch_rollout_jobs(self._h, C.byref(spec)))
+            spec = _spec(_RolloutJobsSpec, horizon, samples, dist, _u64(seed), m, *_job_ptrs(m, src, moves, out), simple_mask,
+                         first_mask if m else 0, flags, 0)
+            self._call("pom_batch_rollout_jobs", C.byref(spec))
         return out
 
     # ---- expand: listed games copied into slots and ticked once (pom_batch_expand) ------------------------
@@ -804,45 +668,25 @@ class BatchEnvironment:
         float16 / float32): tensors sized for the WHOLE batch into which the same launch writes the observation of the tiles of 16 envs
         the range touches; the call then returns (words, agent_attrs, env_attrs), the latter two int32 [n, 4, 8] and [n, 4] written
         for the same envs (None, None with attrs=False)."""
-        import torch
-        dev = torch.device("cuda", self.device)
-
         def device_tensor(a, what, dtype, shape):  # numpy arrays are copied to the device, anything else is _device_tensor's
             if isinstance(a, np.ndarray):
                 if not np.issubdtype(a.dtype, np.integer):
                     raise ValueError(f"{what} must be an integer array")
+                torch, dev = self._torch_device()
                 a = torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
             return self._device_tensor(a, what, dtype, shape)
 
         src = device_tensor(src, "src", "int64", (None,))
         m = int(src.shape[0])
         moves = device_tensor(moves, "moves", "int32", (m, 4))
-        first = int(first)
-        if first < 0 or first + m > self.n:
-            raise ValueError(f"the range [{first}, {first + m}) lies outside the batch of {self.n} envs")
-        out = self._out_tensor(out, (m,), torch.int32)
-        obs, code, per_agent = None, 0, bool(per_agent)
-        if codes is not None and planes is not None:
-            raise ValueError("codes and planes are two forms of one observation: pass one")
-        if codes is not None:
-            if per_agent:
-                raise ValueError("the codes layout has no per-agent view")
-            obs, code, shape, name = codes, 3, (self.n, 5, 11, 11), "codes"
-        elif planes is not None:
-            code = {torch.uint8: 0, torch.float16: 1, torch.float32: 2}.get(getattr(planes, "dtype", None))
-            if code is None:
-                raise ValueError("planes must be uint8, float16 or float32")
-            obs, shape, name = planes, (self.n, 4, 16, 11, 11) if per_agent else (self.n, 16, 11, 11), "planes"
-        a_attrs = e_attrs = None
-        if obs is not None:
-            self._device_tensor(obs, name, torch.uint8 if codes is not None else obs.dtype, shape)
-            if attrs:
-                a_attrs = torch.empty((self.n, 4, 8), dtype=torch.int32, device=dev)
-                e_attrs = torch.empty((self.n, 4), dtype=torch.int32, device=dev)
+        first, _ = self._in_batch(first, m)
+        out = self._out_tensor(out, (m,), "int32")
+        obs, code, per_agent, _view, width, _shape, _dtype = self._observation(codes, planes, per_agent)
+        a_attrs, e_attrs = self._new_attrs(width) if obs is not None and attrs else (None, None)
         with self._ordered():
-            spec = _ExpandSpec(C.sizeof(_ExpandSpec), 0, first, m, src.data_ptr() if m else None, moves.data_ptr() if m else None,
-                               out.data_ptr() if m else None, _ptr(obs), code, int(per_agent), _ptr(a_attrs), _ptr(e_attrs), 0)
-            _check(self._lib, self._lib.pom_batch_expand(self._h, C.byref(spec)))
+            spec = _spec(_ExpandSpec, 0, first, m, *_job_ptrs(m, src, moves, out), _ptr(obs), code, int(per_agent), _ptr(a_attrs),
+                         _ptr(e_attrs), 0)
+            self._call("pom_batch_expand", C.byref(spec))
         return out if obs is None else (out, a_attrs, e_attrs)
 
     def move_table(self, agent: int, horizon: int, samples: int, seed: int, dist: int = DIST_RANDOM, others=None, *, simple=None,
@@ -852,33 +696,29 @@ class BatchEnvironment:
         The six playouts of an env and a sample share every draw (common random numbers): they differ through the move alone.
         `others`: a device int32 tensor [n, 4] — the other three agents' tick-1 moves are fixed to its entries too (`agent`'s own
         column is ignored); None: only `agent`'s move is fixed.  `simple`, `fresh_agents`, `dist`: as rollout()."""
-        import torch
-        if not 0 <= int(agent) <= 3:
-            raise ValueError("agent must be 0..3")
-        dev = torch.device("cuda", self.device)
-        n = self.n
+        agent, n = _bounded(agent, "agent", 0, 3), self.n
         if others is not None:
-            moves = self._device_tensor(others, "others", "int32", (n, 4)).unsqueeze(0).repeat(6, 1, 1)
-        else:
-            moves = torch.zeros((6, n, 4), dtype=torch.int32, device=dev)
-        moves[:, :, int(agent)] = torch.arange(6, dtype=torch.int32, device=dev).unsqueeze(1)
+            self._device_tensor(others, "others", "int32", (n, 4))
+        torch, dev = self._torch_device()
+        moves = torch.zeros((6, n, 4), dtype=torch.int32, device=dev) if others is None else others.unsqueeze(0).repeat(6, 1, 1)
+        moves[:, :, agent] = torch.arange(6, dtype=torch.int32, device=dev).unsqueeze(1)
         src = torch.arange(n, dtype=torch.int64, device=dev).repeat(6)  # job c * n + e plays env e
         res = self.rollout_jobs(src, horizon, samples, seed, dist, moves.view(6 * n, 4), simple=0 if simple is None else simple,
-                                first=0xF if others is not None else [int(agent)], fresh_agents=fresh_agents)
+                                first=0xF if others is not None else [agent], fresh_agents=fresh_agents)
         return res.view(int(samples), 6, n).permute(1, 0, 2).contiguous()
 
     def moves_tensor(self):
         """The handle's device move buffer as a torch int32 tensor [n, 4] (zero-copy): what policy_simple() fills and
         step_policy() consumes; overwrite entries on the handle's stream to mix in another policy."""
-        import torch
+        torch, dev = self._torch_device()
         ptr = C.POINTER(C.c_int32)()
-        _check(self._lib, self._lib.pom_batch_moves_device(self._h, C.byref(ptr)))
+        self._call("pom_batch_moves_device", C.byref(ptr))
         addr = C.cast(ptr, C.c_void_p).value
 
         class _Raw:  # the CUDA array interface is how torch adopts foreign device memory
             __cuda_array_interface__ = {"shape": (self.n, 4), "typestr": "<i4", "data": (addr, False), "version": 2}
 
-        t = torch.as_tensor(_Raw(), device=torch.device("cuda", self.device))
+        t = torch.as_tensor(_Raw(), device=dev)
         # the memory belongs to the handle: the view keeps its BatchEnvironment alive (no __del__ while a view exists), and an
         # explicit close() with views outstanding is refused
         t._pom_owner = self
@@ -888,62 +728,61 @@ class BatchEnvironment:
     def stream_handle(self) -> int:
         """the hipStream_t (as an integer) this handle's work is ordered on"""
         s = C.c_void_p()
-        _check(self._lib, self._lib.pom_batch_stream(self._h, C.byref(s)))
+        self._call("pom_batch_stream", C.byref(s))
         return s.value or 0
 
     # ---- counters / plumbing ------------------------------------------------------------------------
     def counters(self) -> np.ndarray:
         out = np.zeros(4, dtype=np.int64)
-        _check(self._lib, self._lib.pom_batch_counters(self._h, out.ctypes.data))
+        self._call("pom_batch_counters", out.ctypes.data)
         self._tapes.clear()
         return out
 
     def counters_into(self, dev_ptr: int) -> None:
-        _check(self._lib, self._lib.pom_batch_counters_device(self._h, dev_ptr))
+        self._call("pom_batch_counters_device", dev_ptr)
 
     def reset_counters(self) -> None:
-        _check(self._lib, self._lib.pom_batch_reset_counters(self._h))
+        self._call("pom_batch_reset_counters")
 
     def sync(self) -> None:
-        _check(self._lib, self._lib.pom_batch_sync(self._h))
+        self._call("pom_batch_sync")
         self._tapes.clear()
 
     def flush(self) -> None:
         """Make the handle's stream wait for all steps issued so far (host does not block)."""
-        _check(self._lib, self._lib.pom_batch_flush(self._h))
+        self._call("pom_batch_flush")
 
     def fork(self) -> None:
         """Order the internal sub-streams behind the handle's stream now (the next step then needs no cross-stream event first)."""
         if hasattr(self._lib, "pom_batch_fork"):  # (older experimental builds loaded through POM_LIB lack it)
-            _check(self._lib, self._lib.pom_batch_fork(self._h))
+            self._call("pom_batch_fork")
 
     def set_streams(self, streams: int) -> None:
-        _check(self._lib, self._lib.pom_batch_set_streams(self._h, streams))
+        self._call("pom_batch_set_streams", streams)
 
     def profile(self, enable: bool) -> None:
-        _check(self._lib, self._lib.pom_batch_profile(self._h, int(enable)))
+        self._call("pom_batch_profile", int(enable))
+
+    def _read(self, name: str, *types):
+        """the values the library's `name` writes through one pointer per ctypes type of `types`"""
+        outs = [t() for t in types]
+        self._call(name, *map(C.byref, outs))
+        return tuple(o.value for o in outs)
 
     def profile_read(self):
-        ms, n = C.c_double(), C.c_int64()
-        _check(self._lib, self._lib.pom_batch_profile_read(self._h, C.byref(ms), C.byref(n)))
-        return ms.value, n.value
+        return self._read("pom_batch_profile_read", C.c_double, C.c_int64)
 
     def launch_shape(self):
         """(envs per wavefront, lanes per env, launches per step)"""
-        epw, lpe, parts = C.c_int32(), C.c_int32(), C.c_int32()
-        _check(self._lib, self._lib.pom_batch_launch_shape(self._h, C.byref(epw), C.byref(lpe), C.byref(parts)))
-        return epw.value, lpe.value, parts.value
+        return self._read("pom_batch_launch_shape", C.c_int32, C.c_int32, C.c_int32)
 
     def issue_info(self):
         """(name of the issue mode in force for several-tick calls, streams their launches go to)"""
-        mode, streams = C.c_int32(), C.c_int32()
-        _check(self._lib, self._lib.pom_batch_issue_info(self._h, C.byref(mode), C.byref(streams)))
-        return {ISSUE_DIRECT: "direct", ISSUE_THREADS: "threads", ISSUE_GRAPH: "graph", ISSUE_CHAIN: "chain"}.get(mode.value, "?"), streams.value
+        mode, streams = self._read("pom_batch_issue_info", C.c_int32, C.c_int32)
+        return {ISSUE_DIRECT: "direct", ISSUE_THREADS: "threads", ISSUE_GRAPH: "graph", ISSUE_CHAIN: "chain"}.get(mode, "?"), streams
 
     def device_view(self):
-        base, n_pad, rec = C.c_void_p(), C.c_int64(), C.c_int32()
-        _check(self._lib, self._lib.pom_batch_device_view(self._h, C.byref(base), C.byref(n_pad), C.byref(rec)))
-        return base.value, n_pad.value, rec.value
+        return self._read("pom_batch_device_view", C.c_void_p, C.c_int64, C.c_int32)
 
 
 def bench_policy(codes, moves, first: int, count: int, tick: int, stream=None) -> None:
@@ -953,4 +792,3 @@ def bench_policy(codes, moves, first: int, count: int, tick: int, stream=None) -
     lib = load_library()
     st = getattr(stream, "cuda_stream", stream)
     _check(lib, lib.pom_bench_policy(codes.data_ptr() if codes is not None else None, moves.data_ptr(), int(first), int(count), int(tick) & 0xFFFFFFFF, st))
-

@@ -1,6 +1,6 @@
 """What BatchEnvironment's calls ask of their device tensors (pomcpp_amd/batch.py _device_tensor, _out_tensor): every tensor argument of
 step_device, step_device_many, step_device_range (plain, per-agent and fogged-view forms), copy_envs (tensor form), observe(out=),
-forecast, rollout, rollout_jobs, expand and move_table(others=) is
+forecast, move_safety, rollout, rollout_jobs, expand and move_table(others=) is
 refused with a ValueError that names the argument when its element type or its shape is wrong, when it is a non-contiguous view of a
 larger tensor, and when it lives on the CPU — and a refused call has done nothing: state, counters and episode numbers are what they were.
 
@@ -41,13 +41,12 @@ def range_rows(env, i32, u8, good):
     ]
 
 
-def _table(env, torch):
-    """(call, argument, the text that names it, element type, shape, free: the first dimension is the caller's, the call given a tensor)"""
-    dev = torch.device("cuda", 0)
-    i32, i64, u8 = torch.int32, torch.int64, torch.uint8
-    src = torch.full((M,), -1, dtype=i64, device=dev)   # entries without a job: even a call that went through would change nothing
-    mv = torch.zeros((M, 4), dtype=i32, device=dev)
-    return range_rows(env, i32, u8, lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=dev)) + [
+def other_rows(env, i8, i32, i64, u8, good):
+    """_table's rows of every other call, with the same good(shape, dtype); tests/test_wrapper_args_host.py drives these too, torch and
+    the library stood in for"""
+    src = good((M,), i64).fill_(-1)   # entries without a job: even a call that went through would change nothing
+    mv = good((M, 4), i32)
+    return [
         ("step_device", "moves", "moves", i32, (N, 4), False, lambda t: env.step_device(t)),
         ("step_device_many", "moves", "moves", i32, (3, N, 4), True, lambda t: env.step_device_many(t)),
         ("copy_envs", "src", "src", i64, (N,), True, lambda t: env.copy_envs(t)),
@@ -56,6 +55,9 @@ def _table(env, torch):
         ("forecast", "out[flame_tick]", "flame_tick", u8, (N, 11, 11), False, lambda t: env.forecast(HORIZON, out={"flame_tick": t})),
         ("forecast", "out[agent_tick]", "agent_tick", i32, (N, 4), False, lambda t: env.forecast(HORIZON, out={"agent_tick": t})),
         ("forecast", "out[ubflags]", "ubflags", i32, (N,), False, lambda t: env.forecast(HORIZON, out={"ubflags": t}, ubflags=True)),
+        ("move_safety", "moves", "moves", i32, (N, 4), False, lambda t: env.move_safety(HORIZON, moves=t)),
+        ("move_safety", "out[death_tick]", "death_tick", i8, (N, 4, 6), False, lambda t: env.move_safety(HORIZON, out={"death_tick": t})),
+        ("move_safety", "out[escape_tick]", "escape_tick", i8, (N, 4, 6), False, lambda t: env.move_safety(HORIZON, out={"escape_tick": t})),
         ("rollout", "moves", "moves", i32, (N, 4), False, lambda t: env.rollout(HORIZON, SAMPLES, 1, moves=t)),
         ("rollout", "out", "out", i32, (SAMPLES, N), False, lambda t: env.rollout(HORIZON, SAMPLES, 1, out=t)),
         ("rollout(simple=)", "moves", "moves", i32, (N, 4), False, lambda t: env.rollout(HORIZON, SAMPLES, 1, moves=t, simple=[0])),
@@ -70,6 +72,13 @@ def _table(env, torch):
         ("expand(per_agent)", "planes", "planes", u8, (N, 4, 16, 11, 11), False, lambda t: env.expand(src, mv, planes=t, per_agent=True)),
         ("move_table", "others", "others", i32, (N, 4), False, lambda t: env.move_table(0, HORIZON, SAMPLES, 1, others=t)),
     ]
+
+
+def _table(env, torch):
+    """(call, argument, the text that names it, element type, shape, free: the first dimension is the caller's, the call given a tensor)"""
+    dev = torch.device("cuda", 0)
+    good = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=dev)  # noqa: E731
+    return range_rows(env, torch.int32, torch.uint8, good) + other_rows(env, torch.int8, torch.int32, torch.int64, torch.uint8, good)
 
 
 def _bad(torch, dtype, shape, free):
