@@ -364,6 +364,71 @@ int pom_batch_step_device_range_view(PomBatch* h, int64_t first, int64_t count, 
                                      const PomViewSpec* spec);
 
 /*
+ * MIXED STEP: the closed-loop range call with SimpleAgent opponents — "my network plays some of the agents, agents::SimpleAgent the
+ * rest, every agent sees its fogged view" as ONE launch per range and tick.  The three-call recipe (pom_batch_policy_simple, an
+ * overwrite of the move buffer, pom_batch_step_policy, then an observation) is three launches on the whole batch, two reads of every
+ * record and a Move[4] round trip through memory, and has no range form; this call is pom_batch_step_device_range(_view) with the
+ * policy of pom_batch_step_simple inside it for the agents of simple_mask.
+ * Semantics, per env e of [first, first + count) (whole tiles, as pom_batch_step_device_range), in this order:
+ *   1 Restart at the start.  POM_RESET_AT_START and e finished: the env restarts from its snapshot, or on the next generated board
+ *          (fresh_boards), and the SimpleAgent memory of ALL FOUR of its agents becomes zero — as pom_batch_step_simple does it.
+ *   2 Finished envs.  POM_MODE_ENV, e finished and not restarted: nothing happens — no act, memory untouched, no tick.
+ *   3 SimpleAgent moves.  Every LIVE agent a of simple_mask is asked exactly as pom_batch_policy_simple(seed) asks it at handle tick
+ *          `tick`: SimpleAgent::act on the current state, its one draw (agent a's 16 bits of the pom_rng.h draw keyed (seed,
+ *          env_offset + e, tick)) * 5 >> 16, its memory updated in place.  A dead agent of the mask gives IDLE.
+ *   4 Explicit moves.  Every agent NOT in the mask gets moves_dev[e][a], dead agents' entries included (step_utility.cpp:138-170).  It
+ *          is not asked, and its memory is not touched (pom_batch_rollout_policy's rule: an actor is in the mask and alive).
+ *   5 The tick, its bookkeeping, counters, ubflags, terminal record and `finished` mark: exactly as pom_batch_step_device_range,
+ *          POM_RESET_AT_END included — the finishing tick restarts the env, marks it restarted and wipes all four agents' memory.
+ *   6 Observation: exactly as pom_batch_step_device_range (planes_dev) / _range_view (view) writes it for the range; the arrays are
+ *          sized for the WHOLE batch and rows outside the range are not touched.
+ * Ranges advance on their own, so the handle's tick cannot key the draw: `tick` is an argument, and the handle's tick does not
+ * advance.  Nothing else changes either: the handle's move buffer (pom_batch_moves_device), envs outside the range, snapshots.
+ * Equivalences:
+ *   simple_mask == 0 is pom_batch_step_device_range(_view), bit for bit (which knows nothing of the agents' memory: nobody is asked
+ *          here either, but where the memory exists step 1 and step 5 wipe that of the envs they restart).
+ *   Any mask, first = 0, count = n equals, on a twin handle, pom_batch_set_tick(tick); pom_batch_policy_simple(seed); the entries of
+ *          the move buffer of agents outside the mask overwritten with moves_dev; pom_batch_step_policy; pom_batch_observe(_view) —
+ *          records, status, episodes, counters, terminal records and observation, and the memory of the mask's agents.  The memory
+ *          of the agents outside the mask is what it was before the call, or zero where the env restarted in this call.  (One
+ *          difference, with POM_RESET_AT_END: the sequence's tick has no policy in it and leaves the memory of an env that it
+ *          restarts as it was; this call wipes it — step 5, as pom_batch_step_simple does.)
+ *   simple_mask == 15, first = 0, count = n equals pom_batch_set_tick(tick); pom_batch_step_simple(seed, 1), bit for bit, memory included.
+ * Ordering, settling, memory: as pom_batch_step_device_range — the handle is settled, nothing is forked or joined, ONE launch on
+ *          `stream`, no synchronising runtime call once the handle is settled.  The one exception: the agents' memory is allocated
+ *          and cleared by the first call with simple_mask != 0 on a handle that has none yet (no policy call before it), and that
+ *          call synchronises the handle's stream once, so that the clear is ordered before any later launch on any stream.  A call
+ *          with count == 0 is defined to do only that: make it once before capturing mixed steps into a graph.
+ * POM_E_ARG (with a pom_last_error text naming pom_batch_step_mixed; nothing is launched): a null handle or spec, struct_size !=
+ *          sizeof(PomMixedStepSpec) (POM_MIXED_STEP_SPEC_SIZE), simple_mask outside 0..15, tick outside 0..2^32-1, nonzero flags or
+ *          reserved_, a null moves_dev with simple_mask != 15, moves_dev not 4-byte aligned, whatever pom_batch_step_device_range
+ *          refuses of a range, pom_batch_observe of a plain observation and PomViewSpec of a view, `view` together with planes_dev,
+ *          `view` together with a non-NULL env_attrs_dev, a launch shape other than the quad shape.
+ * Not here: a host-pointer variant, several ticks per launch, a chained form, policies other than SimpleAgent, a mask per env, the
+ *          one-lane-per-env shapes.
+ */
+enum { POM_MIXED_STEP_SPEC_SIZE = 104 }; /* 2 x int32, 2 x int64, pointer, uint64, int64, 3 pointers, 2 x int32, 2 pointers, 2 x int32: no implicit padding on an LP64 target */
+typedef struct PomMixedStepSpec {
+    int32_t struct_size;       /*   0  = sizeof(PomMixedStepSpec) */
+    int32_t simple_mask;       /*   4  bit a: agent a plays SimpleAgent; 0..15 */
+    int64_t first;             /*   8  whole tiles, as pom_batch_step_device_range */
+    int64_t count;             /*  16 */
+    const int32_t* moves_dev;  /*  24  int32 [n][4], indexed by the env's number in the batch; required unless simple_mask == 15 */
+    uint64_t seed;             /*  32  seed of the SimpleAgent draw */
+    int64_t tick;              /*  40  0 .. 2^32-1: keys this call's SimpleAgent draw */
+    void* stream;              /*  48  NULL: the handle's stream */
+    const PomViewSpec* view;   /*  56  nullable: the fogged views */
+    void* planes_dev;          /*  64  nullable: the plain observation, as pom_batch_step_device_range */
+    int32_t dtype;             /*  72  POM_OBS_* */
+    int32_t per_agent;         /*  76 */
+    int32_t* agent_attrs_dev;  /*  80  nullable */
+    int32_t* env_attrs_dev;    /*  88  nullable; NULL if view is given (view->env_attrs_dev is the one used) */
+    int32_t flags;             /*  96  must be 0 */
+    int32_t reserved_;         /* 100  must be 0 */
+} PomMixedStepSpec;
+int pom_batch_step_mixed(PomBatch* h, const PomMixedStepSpec* spec);
+
+/*
  * FORECAST: where will the fire be, and when — flames and deaths K ticks ahead, without touching the batch.  The reference's own
  * answer is strategy::IsInDanger (src/bboard/strategy.cpp:229-249), the smallest timer over the bombs whose cross covers a cell; its
  * comment says "TODO: add consideration for chained bomb explosions", and it knows nothing of walls, wood or moving bombs either.

@@ -1,4 +1,4 @@
-"""The ctypes mirror of include/pom_batch.h, and nothing else: its constants, its eight spec structures with their builders, the
+"""The ctypes mirror of include/pom_batch.h, and nothing else: its constants, its nine spec structures with their builders, the
 prototype of every function it declares (PROTOTYPES) and the loading of libpom_batch.so.  Whatever is written here is written a
 second time in the header; tests/test_abi_mirror.py compares the two, field by field and argument by argument, without the library.
 """
@@ -97,9 +97,20 @@ class _ExpandSpec(C.Structure):
     ]
 
 
+class _MixedStepSpec(C.Structure):
+    """PomMixedStepSpec (include/pom_batch.h): one tick of a range, SimpleAgent for the agents of simple_mask, the others' moves, the
+    stream, and the observation as a PomViewSpec or as the range call's plain outputs"""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("simple_mask", C.c_int32), ("first", C.c_int64), ("count", C.c_int64), ("moves_dev", C.c_void_p),
+        ("seed", C.c_uint64), ("tick", C.c_int64), ("stream", C.c_void_p), ("view", C.POINTER(_ViewSpec)), ("planes_dev", C.c_void_p),
+        ("dtype", C.c_int32), ("per_agent", C.c_int32), ("agent_attrs_dev", C.c_void_p), ("env_attrs_dev", C.c_void_p),
+        ("flags", C.c_int32), ("reserved_", C.c_int32),
+    ]
+
+
 STRUCTURES = {"PomBatchOptions": _Options, "PomViewSpec": _ViewSpec, "PomForecastSpec": _ForecastSpec,
               "PomMoveSafetySpec": _MoveSafetySpec, "PomRolloutSpec": _RolloutSpec, "PomRolloutPolicySpec": _RolloutPolicySpec,
-              "PomRolloutJobsSpec": _RolloutJobsSpec, "PomExpandSpec": _ExpandSpec}  # the header's name of each
+              "PomRolloutJobsSpec": _RolloutJobsSpec, "PomExpandSpec": _ExpandSpec, "PomMixedStepSpec": _MixedStepSpec}  # the header's name of each
 
 
 def _ptr(t):
@@ -130,6 +141,7 @@ PROTOTYPES = (  # (name, argtypes or None: no parameters, restype or None: int)
     ("pom_batch_observe_view", [_P, C.POINTER(_ViewSpec)], None),
     ("pom_batch_step_device_observe_view", [_P, _VP, C.POINTER(_ViewSpec)], None),
     ("pom_batch_step_device_range_view", [_P, _I64, _I64, _VP, _VP, C.POINTER(_ViewSpec)], None),
+    ("pom_batch_step_mixed", [_P, C.POINTER(_MixedStepSpec)], None),
     ("pom_batch_forecast", [_P, C.POINTER(_ForecastSpec)], None),
     ("pom_batch_rollout", [_P, C.POINTER(_RolloutSpec)], None),
     ("pom_batch_rollout_policy", [_P, C.POINTER(_RolloutPolicySpec)], None),

@@ -28,7 +28,7 @@ from ._abi import (  # noqa: F401 (the binding's names are this module's too: ca
     COPY_FROM_SNAPSHOT, COPY_SET_SNAPSHOT, UB_LOST_AGENT, UB_NULL_BOMB, UB_QUEUE_OVERFLOW, UB_REVERT_LOOP, UB_BAD_INDEX,
     UB_FLAME_QUEUE_RANGE, ROLLOUT_FRESH_AGENTS, RO_NONE, RO_ALIVE, RO_DONE, RO_DRAW, RO_TIMEOUT, RO_UB, RO_WINNER_SHIFT,
     RO_WINNER_MASK, RO_LENGTH_SHIFT, PomError, _Options, _ViewSpec, _ForecastSpec, _MoveSafetySpec, _RolloutSpec,
-    _RolloutPolicySpec, _RolloutJobsSpec, _ExpandSpec, _ptr, _spec, _view_spec, _forecast_spec, library_path, load_library, _check)
+    _RolloutPolicySpec, _RolloutJobsSpec, _ExpandSpec, _MixedStepSpec, _ptr, _spec, _view_spec, _forecast_spec, library_path, load_library, _check)
 from .state import STATE_DTYPE
 
 
@@ -457,6 +457,35 @@ class BatchEnvironment:
             self._call("pom_batch_step_device_range_view", first, count, ptr, st, C.byref(spec))
         else:
             self._call("pom_batch_step_device_range", first, count, ptr, st, _ptr(out), code, int(per_agent), _ptr(agent_attrs), _ptr(env_attrs))
+
+    def step_mixed(self, first: int, count: int, moves, simple, seed: int, tick: int, stream=None, codes=None, planes=None,
+                   view_radius: Optional[int] = None, viewer_attrs=None, env_attrs=None, *, per_agent: Optional[bool] = None,
+                   agent_attrs=None) -> None:
+        """step_device_range() with SimpleAgent opponents (pom_batch_step_mixed): one tick for the envs [first, first + count) — whole
+        tiles of 16 — as ONE launch on `stream`, in which the agents of `simple` (a mask int 0..15 or an iterable of agent ids) are
+        played by SimpleAgent inside the launch — asked as policy_simple(seed) asks them at handle tick `tick` (0..2^32-1), their memory
+        (policy_memory()) moved on — and the others take `moves[e][a]` (int32[n, 4] device tensor or address, indexed by env; None only
+        if all four agents are SimpleAgents).  The ranges of a closed loop advance on their own, so the caller counts each range's
+        `tick`; the handle's tick, its move buffer and the envs outside the range are left alone.  The observation arguments, the
+        checks (a ValueError before anything is launched, no runtime call) and the ordering are step_device_range()'s.  The first call
+        with a non-empty `simple` on a handle that has run no policy yet allocates the agents' memory and synchronises the handle's
+        stream once: make it — count 0 does only that — before capturing mixed steps into a graph."""
+        first, count = self._in_batch(first, count)
+        mask, tick = _agent_mask(simple, "simple"), _bounded(tick, "tick", 0, 0xFFFFFFFF)
+        out, code, per_agent, view, _width, _shape, _dtype = self._observation(codes, planes, per_agent, view_radius, viewer_attrs, agent_attrs,
+                                                                                env_attrs, raw=True)
+        if out is None and (per_agent or agent_attrs is not None or env_attrs is not None):
+            raise ValueError("view_radius, per_agent, agent_attrs and env_attrs belong to an observation: pass `codes` or `planes`")
+        if moves is None and mask != 15:
+            raise ValueError("moves is None, but simple leaves agents to it")
+        ptr, st = self._moves(moves, raw=True), getattr(stream, "cuda_stream", stream)
+        if view:
+            vs = _view_spec(code, view_radius, out, viewer_attrs, env_attrs)
+            spec = _spec(_MixedStepSpec, mask, first, count, ptr, _u64(seed), tick, st, C.pointer(vs), None, 0, 0, None, None, 0, 0)
+        else:
+            spec = _spec(_MixedStepSpec, mask, first, count, ptr, _u64(seed), tick, st, None, _ptr(out), code if out is not None else 0,
+                         int(per_agent), _ptr(agent_attrs), _ptr(env_attrs), 0, 0)
+        self._call("pom_batch_step_mixed", C.byref(spec))
 
     def chain_stats(self) -> dict:
         """chained launches since creation: launches issued, checks run, tiles found left behind, ticks replayed for them"""
