@@ -8,7 +8,7 @@
  *   HBM (packed records in 16-env tiles, pom_packed.h) -> LDS tile + VGPRs -> tick(s) -> HBM,
  * the SimpleAgent policy kernel, the observation export, the board generator and counters.  This file holds the __global__
  * kernels and their parameter structs, and is the one to include for "the kernels"; what they are made of lies in parts:
- *   pom_tile.h         the LDS tile: its rows, LdsEnv, the record's loads and stores, restart_column / column_to_record,
+ *   pom_tile.h         the LDS tile: its rows, LdsEnv, the record's loads and stores, restart_column(s) / column_to_record,
  *                      lane_from_tile, pom_boardgen_wave, pom_xcd_tile_order
  *   pom_policy_wave.h  SimpleAgent for a wavefront: PolicyStore, the cooperative searches, pom_policy_wave
  *   pom_observe.h      the observation export of a tile in LDS: ObserveParams .. pom_observe_tile
@@ -257,6 +257,7 @@ __global__ __launch_bounds__(64 * POM_WPB, (POLICY ? 4 : G == 4 ? POM_QUAD_WAVES
     L.trunc = p.trunc;
 #endif
 #if defined(POM_DIAG)
+#pragma unroll /* (every loop over the phase clocks: an index the compiler does not resolve puts them into scratch) */
     for (int k = 0; k < POM_PH_N; k++) L.t_acc[k] = 0;
     L.t_last = t_begin;
     POM_STAMP(L, POM_PH_LOAD);
@@ -291,20 +292,16 @@ __global__ __launch_bounds__(64 * POM_WPB, (POLICY ? 4 : G == 4 ? POM_QUAD_WAVES
             c_resets += __popcll(__ballot(reload && owner));
         } else {
             /* a finished env restarts from its snapshot (tick 0: as the record says; later ticks of a launch: as the epilogue
-             * found), one restarting env after the other, by the whole wavefront */
+             * found), by the whole wavefront: one env's record, or those of up to four envs with their loads in flight together
+             * (restart_columns) */
             const bool reload = valid && env_mode && p.auto_reset == POM_RESET_AT_START && (status & POM_ST_DONE);
-            uint64_t todo = __ballot(reload && owner);
+            const uint64_t todo = __ballot(reload && owner);
             if (todo) {
                 c_resets += __popcll(todo);
                 int lane_now = lane; /* (as at the end of the tick: addresses worked out where they are used — a launch of several ticks
                                         would carry them from tick to tick) */
                 if (!SINGLE) asm volatile("" : "+v"(lane_now));
-                do {
-                    const int src = __builtin_amdgcn_readfirstlane(__ffsll((unsigned long long)todo) - 1); /* an owner lane */
-                    todo &= todo - 1;
-                    const int ec_u = G == 1 ? src : src >> 2;
-                    restart_column<EPW>(tile, ec_u, p.snap + (tile_id * EPW + ec_u) * POM_REC_DWORDS, lane_now);
-                } while (todo);
+                restart_columns<EPW, POM_REC_DWORDS, G == 1 ? 1 : 4>(tile, todo, p.snap + tile_id * EPW * POM_REC_DWORDS, lane_now);
                 asm volatile("" ::: "memory"); /* other lanes wrote this lane's column: no read of it may be scheduled earlier */
                 if (!UNPACK_LATE && reload) lane_from_tile(L, time_step, status, t, EPW); /* the register-resident rows, from the new record */
             }
@@ -423,6 +420,7 @@ __global__ __launch_bounds__(64 * POM_WPB, (POLICY ? 4 : G == 4 ? POM_QUAD_WAVES
                 int lane_end = lane; /* (a lane id the compiler cannot see through: the global addresses below are worked out here, not at
                                         the top of the kernel and carried through the tick) */
                 asm volatile("" : "+v"(lane_end));
+                const uint64_t finished = todo;
                 do {
                     const int src = __builtin_amdgcn_readfirstlane(__ffsll((unsigned long long)todo) - 1); /* an owner lane */
                     todo &= todo - 1;
@@ -439,10 +437,10 @@ __global__ __launch_bounds__(64 * POM_WPB, (POLICY ? 4 : G == 4 ? POM_QUAD_WAVES
                         ep = (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)ep, src));
                         const uint32_t key = pom_board_key(p.board_seed, (uint32_t)(p.env_offset + e_u), ep);
                         pom_boardgen_wave<EPW, POM_REC_DWORDS>(tile, ec_u, (uint32_t)__builtin_amdgcn_readfirstlane((int)key), lane_end);
-                    } else {
-                        restart_column<EPW>(tile, ec_u, p.snap + e_u * POM_REC_DWORDS, lane_end);
                     }
                 } while (todo);
+                /* the final records have been read out of the tile: the start states of all of them, their loads in flight together */
+                if (!FRESH) restart_columns<EPW, POM_REC_DWORDS, G == 1 ? 1 : 4>(tile, finished, p.snap + tile_id * EPW * POM_REC_DWORDS, lane_end);
                 asm volatile("" ::: "memory");
                 if (newly_done && runs) {
                     lane_from_tile(L, time_step, status, t, EPW);
@@ -506,6 +504,7 @@ __global__ __launch_bounds__(64 * POM_WPB, (POLICY ? 4 : G == 4 ? POM_QUAD_WAVES
                      only (the blast engines) are booked by the lanes inside; everybody else books the same time on the phase
                      around them — so the wavefront reports the lane that spent the most time inside */
         long long inside = 0;
+#pragma unroll
         for (int k = POM_PH_X_SCAN; k <= POM_PH_X_SHORT; k++) inside += L.t_acc[k];
         long long best = inside;
         for (int o = 32; o > 0; o >>= 1) {
@@ -514,6 +513,7 @@ __global__ __launch_bounds__(64 * POM_WPB, (POLICY ? 4 : G == 4 ? POM_QUAD_WAVES
         }
         const uint64_t who = __ballot(inside == best);
         if (lane == __ffsll((unsigned long long)who) - 1)
+#pragma unroll
             for (int k = 0; k < POM_PH_N; k++) p.diag[tile_id * POM_PH_N + k] += L.t_acc[k];
     }
 #endif
@@ -661,18 +661,18 @@ __global__ __launch_bounds__(64) void pom_policy_kernel(PolicyParams p)
     if (restart) m0 = m1 = 0; /* a new game gets fresh agents */
     {
         uint64_t todo = __ballot(restart && id == 0);
-        while (todo) {
-            const int src = __builtin_amdgcn_readfirstlane(__ffsll((unsigned long long)todo) - 1);
-            todo &= todo - 1;
-            const int ec_u = src >> 2;
-            if (p.fresh) {
+        if (p.fresh) {
+            while (todo) {
+                const int src = __builtin_amdgcn_readfirstlane(__ffsll((unsigned long long)todo) - 1);
+                todo &= todo - 1;
+                const int ec_u = src >> 2;
                 const uint32_t ep = p.episode[tile_id * 16 + ec_u] + 1u;
                 const uint32_t key = pom_board_key(p.board_seed, (uint32_t)(p.env_offset + tile_id * 16 + ec_u),
                                                    (uint32_t)__builtin_amdgcn_readfirstlane((int)ep));
                 pom_boardgen_wave<16, POL_ROWS>(tile, ec_u, (uint32_t)__builtin_amdgcn_readfirstlane((int)key), lane);
-            } else {
-                restart_column<16, POL_ROWS>(tile, ec_u, p.snap + (tile_id * 16 + ec_u) * POM_REC_DWORDS, lane);
             }
+        } else if (todo) { /* the records of up to four envs with their loads in flight together */
+            restart_columns<16, POL_ROWS, 4>(tile, todo, p.snap + tile_id * 16 * POM_REC_DWORDS, lane);
         }
         asm volatile("" ::: "memory");
     }

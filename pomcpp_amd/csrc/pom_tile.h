@@ -288,6 +288,18 @@ __device__ __forceinline__ void store_tile16_x4(uint32_t* base, const uint32_t* 
     for (int r0 = 0; r0 + 16 <= ROWS; r0 += 16) put(r0);
     if (ROWS % 16 != 0 && (lane >> 2) < ROWS % 16) put(ROWS / 16 * 16); /* the last rows, as in load_tile16_x4 */
 }
+/* lane l's two dwords of a dense record (v0 = dword l, v1 = dword l + 64) into column el of the tile: the write half of
+ * restart_column and restart_columns */
+template <int EPW, int ROWS = POM_REC_DWORDS>
+__device__ __forceinline__ void record_to_column(uint32_t* tile, int el, uint32_t v0, uint32_t v1, int lane)
+{
+    if (lane < POM_REC_BOARD_DWORDS) { /* a dense record holds four cells per dword, the tile lays the board out by cell */
+        uint8_t* cells = reinterpret_cast<uint8_t*>(tile);
+#pragma unroll
+        for (int j = 0; j < 4; j++) cells[tile_cell_byte<EPW>(el, 4 * lane + j)] = (uint8_t)(v0 >> (8 * j));
+    } else tile[lane * EPW + el] = v0;
+    if (lane + 64 < ROWS) tile[(lane + 64) * EPW + el] = v1;
+}
 /*
  * The restart snapshot is kept array-of-structs: env e's record is the 320 contiguous bytes snap[e * 80 .. e * 80 + 79].
  * A restart needs ONE env's whole record, and in the column layout of the state buffer that is 80 dwords in 80
@@ -301,12 +313,42 @@ __device__ __forceinline__ void restart_column(uint32_t* tile, int el, const uin
 {
     const uint32_t v0 = src[lane];
     const uint32_t v1 = lane + 64 < ROWS ? src[lane + 64] : 0u;
-    if (lane < POM_REC_BOARD_DWORDS) { /* a dense record holds four cells per dword, the tile lays the board out by cell */
-        uint8_t* cells = reinterpret_cast<uint8_t*>(tile);
+    record_to_column<EPW, ROWS>(tile, el, v0, v1, lane);
+}
+/*
+ * Every restarting env of a tile: `todo` (wave-uniform, not 0) holds one lane per restarting env — lane LPE * el, LPE = the lanes
+ * an env has in the ballot it comes from —, `snap_tile` = the snapshot record of the tile's env 0.  A wavefront that restarts ONE
+ * env (most of those that restart any) goes through restart_column as it always did.  With several, their records are fetched
+ * up to four per round, all of a round's loads asked for before the first is waited for: a wavefront that restarts two to five
+ * envs in one visit pays one or two trips to memory instead of one per env.
+ */
+template <int EPW, int ROWS, int LPE>
+__device__ __forceinline__ void restart_columns(uint32_t* tile, uint64_t todo, const uint32_t* snap_tile, int lane)
+{
+    if ((todo & (todo - 1)) == 0) { /* one env */
+        const int el = (int)((unsigned)__builtin_amdgcn_readfirstlane(__ffsll((unsigned long long)todo) - 1) / LPE);
+        restart_column<EPW, ROWS>(tile, el, snap_tile + el * POM_REC_DWORDS, lane);
+        return;
+    }
+    POM_NOUNROLL
+    do {
+        int el[4] = {0, 0, 0, 0}, n = 0;
+        uint32_t v0[4] = {0u, 0u, 0u, 0u}, v1[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
-        for (int j = 0; j < 4; j++) cells[tile_cell_byte<EPW>(el, 4 * lane + j)] = (uint8_t)(v0 >> (8 * j));
-    } else tile[lane * EPW + el] = v0;
-    if (lane + 64 < ROWS) tile[(lane + 64) * EPW + el] = v1;
+        for (int k = 0; k < 4; k++) {
+            if (todo) { /* wave-uniform */
+                el[k] = (int)((unsigned)__builtin_amdgcn_readfirstlane(__ffsll((unsigned long long)todo) - 1) / LPE);
+                todo &= todo - 1;
+                const uint32_t* src = snap_tile + el[k] * POM_REC_DWORDS;
+                v0[k] = src[lane];
+                if (lane + 64 < ROWS) v1[k] = src[lane + 64];
+                n = k + 1;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if (k < n) record_to_column<EPW, ROWS>(tile, el[k], v0[k], v1[k], lane);
+    } while (todo);
 }
 /* the other way: env number el's column of the tile as a dense record (terminal buffer, snapshot) */
 template <int EPW>
@@ -337,6 +379,7 @@ __device__ __forceinline__ void lane_from_tile(PomLane& L, int& time_step, uint3
 __device__ __forceinline__ void pom_lane_diag_off(PomLane& L)
 {
 #if defined(POM_DIAG)
+#pragma unroll
     for (int k = 0; k < POM_PH_N; k++) L.t_acc[k] = 0;
     L.t_last = 0;
 #endif

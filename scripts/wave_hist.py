@@ -15,8 +15,8 @@ lib = a.lib or os.path.join(ROOT, "build", "libpom_batch_diag.so")
 if not a.lib:
     subprocess.run(["hipcc", "-Os", "--offload-arch=gfx950", "-std=c++17", "-shared", "-fPIC", "-DPOM_DIAG", "-I" + ROOT + "/include",
                     "-I" + ROOT + "/pomcpp_amd/csrc", "-o", lib, ROOT + "/pomcpp_amd/csrc/pom_batch.hip"], check=True)
+os.environ["POM_LIB"] = lib  # what pomcpp_amd loads (pomcpp_amd/_abi.py)
 import pomcpp_amd.batch as B
-B.library_path = lambda: lib
 import pomcpp_amd as pa
 env = B.BatchEnvironment(a.envs, mode=B.MODE_ENV, auto_reset=True, max_steps=800, streams=1)
 env.make_game(pa.make_boards(a.envs, seed=1, kind=a.kind))
