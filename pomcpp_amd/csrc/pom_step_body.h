@@ -30,6 +30,8 @@
  * sub, sub+G, ... and writes with put_* — and the partial results are combined with the group reductions
  * gor / gmin / gadd (DPP quad permutes on the device, identities for G = 1).  Every split section is
  * read-only until a group vote has excluded the order-dependent cases, which then run replicated.
+ * One thing is NOT replicated during a quad's tick: the four agent words.  Lane m keeps agent m's alone (PomStepper::mine_, below),
+ * and PomLane::a0 is identical in the four lanes again when step_packed returns.
  *
  * Store interface A (all indices per lane):
  *   static constexpr int G;  int sub();  int gor(int) / gmin(int) / gadd(int) / gbcast<J>(int)
@@ -285,9 +287,54 @@ struct PomStepper {
         return -1;
     }
 
+    /* ---- the agent words during the tick.
+     * One lane per env (G = 1): L.a0[0..3], read with sel4 and written with put4.
+     * A quad per env (G = 4): lane m carries agent m's word alone — `mine_`, taken from L.a0 at the top of step_packed and handed
+     * back to all four lanes at its end (owner_lanes_begin / owner_lanes_end).  In between L.a0 is STALE; "agent id" is a predicate
+     * on the lane number, a look at somebody else's word is one quad reduction, and the deaths are counted per lane (`died_`) and
+     * taken off L.alive once.  Only the literal agent loop (step_middle's fall-back) works on the replicated words: it has them
+     * handed back on entry and takes `mine_` again on exit. */
+    int mine_ = 0, died_ = 0;
+    POM_HD void owner_lanes_begin()
+    {
+        if (A::G == 4) {
+            mine_ = sel4(a.sub(), L.a0);
+            died_ = 0;
+        }
+    }
+    POM_HD void owner_lanes_replicate() /* identical L.a0 in all four lanes again */
+    {
+        if (A::G == 4) {
+            L.a0[0] = a.template gbcast<0>(mine_); L.a0[1] = a.template gbcast<1>(mine_);
+            L.a0[2] = a.template gbcast<2>(mine_); L.a0[3] = a.template gbcast<3>(mine_);
+        }
+    }
+    POM_HD void owner_lanes_end()
+    {
+        if (A::G == 4) {
+            owner_lanes_replicate();
+            L.alive -= a.gadd(died_);
+        }
+    }
+    POM_HD int agent_word(int id) const /* id 0..3, the same in all lanes of the group */
+    {
+        if (A::G == 4) return a.gor(a.sub() == id ? mine_ : 0);
+        return sel4(id, L.a0);
+    }
+    POM_HD void set_agent_word(int id, int v)
+    {
+        if (A::G == 4) mine_ = a.sub() == id ? v : mine_;
+        else put4(id, L.a0, v);
+    }
+
     POM_HD int get_agent(int x, int y) const /* bboard.cpp:289-299 */
     {
         const int want = x | (y << 4);
+        if (A::G == 4) { /* each lane compares its own agent; the lowest hit of the quad wins */
+            const int hit = (!ag_dead(mine_)) & (int)(ag_pos(mine_) == want);
+            const int r = a.gmin(hit ? a.sub() : 4);
+            return r == 4 ? -1 : r;
+        }
         int r = -1;
 #pragma unroll
         for (int i = 3; i >= 0; i--)
@@ -295,7 +342,7 @@ struct PomStepper {
         return r;
     }
 
-    POM_HD void kill(int id) /* State::Kill, bboard.hpp:474-481 */
+    POM_HD void kill_replicated(int id) /* State::Kill, bboard.hpp:474-481, on L.a0 */
     {
         if (id >= POM_AGENT_COUNT) {
             L.ub |= POM_UB_BAD_INDEX;
@@ -307,6 +354,20 @@ struct PomStepper {
             L.alive--;
         }
     }
+    POM_HD void kill(int id) /* State::Kill, bboard.hpp:474-481 */
+    {
+        if (A::G != 4) {
+            kill_replicated(id);
+            return;
+        }
+        if (id >= POM_AGENT_COUNT) {
+            L.ub |= POM_UB_BAD_INDEX;
+            return;
+        }
+        const int hit = (int)(a.sub() == id) & !ag_dead(mine_);
+        mine_ |= hit << 17;
+        died_ += hit;
+    }
 
     POM_HD void owner_bombcount_dec(int b)
     {
@@ -315,7 +376,8 @@ struct PomStepper {
             L.ub |= POM_UB_BAD_INDEX;
             return;
         }
-        put4(id, L.a0, ag_bombcount_add(sel4(id, L.a0), -1));
+        if (A::G == 4) mine_ = a.sub() == id ? ag_bombcount_add(mine_, -1) : mine_;
+        else put4(id, L.a0, ag_bombcount_add(sel4(id, L.a0), -1));
     }
 
     POM_HD void remove_at(int at) /* FixedQueue::RemoveAt, bboard.hpp:151-160 */
@@ -416,6 +478,12 @@ struct PomStepper {
     /* Kill (bboard.hpp:474-481) for every agent in the bit set `victims`; all lanes of the group hold the same set */
     POM_HD void kill_set(int victims)
     {
+        if (A::G == 4) { /* each lane looks at its own agent's bit */
+            const int hit = (victims >> a.sub()) & 1 & !ag_dead(mine_);
+            mine_ |= hit << 17;
+            died_ += hit;
+            return;
+        }
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const int hit = (victims >> j) & 1 & !ag_dead(L.a0[j]);
@@ -884,7 +952,7 @@ struct PomStepper {
                 L.ub |= POM_UB_REVERT_LOOP;
                 return;
             }
-            const int av = sel4(id, L.a0);
+            const int av = agent_word(id);
             const int m = (mvp >> (4 * id)) & 0xF;
             /* OriginPosition, step_utility.cpp:33-55: one step against the move */
             const int ox = ag_x(av) - mv_dx(m), oy = ag_y(av) - mv_dy(m);
@@ -904,7 +972,7 @@ struct PomStepper {
                 bd = a.gmin(bd);
                 if (bd == 99) bd = -1;
             }
-            put4(id, L.a0, ag_setpos(av, ox, oy));
+            set_agent_word(id, ag_setpos(av, ox, oy));
             irregular_ |= (ox | (oy << 4)) != (int)((oldp_ >> (8 * id)) & 0xFF);
             a.set_cell(oy * POM_N + ox, POM_C_AGENT + id);
             if (origin_agent != -1) {
@@ -992,7 +1060,7 @@ struct PomStepper {
             const int ag = get_agent(bx, by);
             if (ag > -1) {
                 const int m = (mvp >> (4 * ag)) & 0xF;
-                const int av = sel4(ag, L.a0);
+                const int av = agent_word(ag);
                 const int was = (oldp >> (8 * ag)) & 0xFF;
                 if ((int)(m != POM_MOVE_IDLE) & (int)(m != POM_MOVE_BOMB) & (int)((ag_x(av) | (ag_y(av) << 4)) != was)) {
                     chain_reversion(mvp, ag, bombs_move);
@@ -1024,6 +1092,7 @@ struct PomStepper {
     POM_HD void step_packed(uint32_t mvp)
     {
         int ftop, fn, btop, bn;
+        owner_lanes_begin();
         flames_dec(ftop, fn); /* step.cpp:15 */
         POM_STAMP(L, POM_PH_FLAMES_DEC);
         POM_CUT(L, 10);
@@ -1032,6 +1101,7 @@ struct PomStepper {
         POM_CUT(L, 20);
         step_middle(mvp, btop, bn);
         top_explosions(btop, bn);
+        owner_lanes_end();
         POM_STAMP(L, POM_PH_TICK_BOMBS);
     }
     /* TickBombs' second half, step_utility.cpp:233-244: explode the head of the queue while its timer has run out; `n` = 0
@@ -1058,13 +1128,17 @@ struct PomStepper {
     {
         oldp = dstp = 0;
         deadmask = 0;
+        if (A::G == 4) {
+            deadmask = a.gor(ag_dead(mine_) << a.sub()); /* one shifted bit per lane */
+        } else {
 #pragma unroll
-        for (int i = 0; i < 4; i++) deadmask |= ag_dead(L.a0[i]) << i;
+            for (int i = 0; i < 4; i++) deadmask |= ag_dead(L.a0[i]) << i;
+        }
         contact = 0;
         clash = 0; /* two live agents on one cell */
         if (A::G == 4) {
             const int m = a.sub();
-            const int av = sel4(m, L.a0);
+            const int av = mine_;
             const int mvm = (int)((mvp >> (4 * m)) & 0xF);
             const int pxm = ag_x(av), pym = ag_y(av);
             const int dxm = pxm + mv_dx(mvm), dym = pym + mv_dy(mvm);
@@ -1313,7 +1387,7 @@ struct PomStepper {
             if (par) {
                 agents_done = 1;
                 const int m = a.sub();
-                int av = sel4(m, L.a0), a1v = a.ag1(m);
+                int av = mine_, a1v = a.ag1(m);
                 const int a1_before = a1v;
                 const int mvm = (mvp >> (4 * m)) & 0xF;
                 const int live = !ag_dead(av);
@@ -1415,16 +1489,15 @@ struct PomStepper {
                      * collision is looked at.  (Only with chains: most wavefronts skip it.) */
                     if (r + 1 < rounds) dead80 |= (uint32_t)a.gor(died << (8 * m + 7));
                 }
-                /* back to identical registers in all four lanes */
-                L.a0[0] = a.template gbcast<0>(av); L.a0[1] = a.template gbcast<1>(av);
-                L.a0[2] = a.template gbcast<2>(av); L.a0[3] = a.template gbcast<3>(av);
+                mine_ = av; /* (stays with its lane; the four lanes get identical words again at the end of the tick: owner_lanes_end) */
+                died_ += died_sum;
                 if (a1v != a1_before) a.put_ag1(m, a1v); /* (a power-up picked up: rare) */
-                L.alive -= a.gadd(died_sum);
                 L.bCnt += a.gadd(fits);
                 L.ub |= (uint32_t)a.gor(ubm);
             }
         }
         if (!agents_done) {
+            owner_lanes_replicate(); /* the literal loop works on L.a0 */
             int root_idx = 0;
             int i = ouroboros ? 0 : (int)(roots & 0xF);
             POM_NOUNROLL
@@ -1480,7 +1553,7 @@ struct PomStepper {
                 if (ouroboros && bomb_index(ddx | (ddy << 4)) >= 0) item = POM_C_BOMB; /* step.cpp:71-82 */
 
                 if (pc_is_flame(item)) { /* step.cpp:84-99 */
-                    kill(i);
+                    kill_replicated(i);
                     deadmask |= 1 << i;
                     const int oc = y * POM_N + x;
                     if (a.cell(oc) == POM_C_AGENT + i)
@@ -1527,6 +1600,7 @@ struct PomStepper {
                 }
                 i = next;
             }
+            if (A::G == 4) mine_ = sel4(a.sub(), L.a0);
         }
 
         POM_STAMP(L, POM_PH_AGENT_LOOP);
@@ -1550,9 +1624,17 @@ struct PomStepper {
             uint32_t movers = 0; /* queue offsets of the bombs with a direction */
             /* where the agents stand NOW (after the agent loop), a byte each, and 0x80 in the bytes of the dead (the dead bit is bit 1 of
              * an agent word's third byte) */
-            const uint32_t nowp = pom_gather_bytes<0>((uint32_t)L.a0[0], (uint32_t)L.a0[1], (uint32_t)L.a0[2], (uint32_t)L.a0[3]);
-            const uint32_t nowflags = pom_gather_bytes<2>((uint32_t)L.a0[0], (uint32_t)L.a0[1], (uint32_t)L.a0[2], (uint32_t)L.a0[3]);
-            const uint32_t nowdead80 = (nowflags << 6) & 0x80808080u;
+            uint32_t nowp, nowdead80;
+            if (A::G == 4) {
+                /* each lane puts its agent's byte into its place of one word.  A dead agent's byte reads 0xFF, which is no cell (x = y = 15:
+                 * the test below is only made for a bomb on the board), so the dead need no mask of their own */
+                nowp = (uint32_t)a.gor((int)((uint32_t)((mine_ | -ag_dead(mine_)) & 0xFF) << (8 * a.sub())));
+                nowdead80 = 0u;
+            } else {
+                nowp = pom_gather_bytes<0>((uint32_t)L.a0[0], (uint32_t)L.a0[1], (uint32_t)L.a0[2], (uint32_t)L.a0[3]);
+                const uint32_t nowflags = pom_gather_bytes<2>((uint32_t)L.a0[0], (uint32_t)L.a0[1], (uint32_t)L.a0[2], (uint32_t)L.a0[3]);
+                nowdead80 = (nowflags << 6) & 0x80808080u;
+            }
             POM_NOUNROLL
             for (int k = a.sub(); k < L.bCnt; k += A::G) { /* split: each lane its own slots, combined below */
                 int b = pb_set(bomb_at(k), 0xF000000u, 0);

@@ -19,15 +19,15 @@ ap.add_argument("--burn", type=int, default=300)
 ap.add_argument("--build-only", action="store_true")
 ap.add_argument("--policy", action="store_true", help="4x SimpleAgent fused with the tick (fresh boards)")
 a = ap.parse_args()
-lib = os.path.join(ROOT, "build", "libpom_batch_trunc.so")
-if a.build_only or not os.path.exists(lib):
+lib = os.environ.get("POM_TRUNC_LIB") or os.path.join(ROOT, "build", "libpom_batch_trunc.so")  # POM_TRUNC_LIB: a POM_TRUNC build made elsewhere (another commit's)
+if (a.build_only and "POM_TRUNC_LIB" not in os.environ) or not os.path.exists(lib):
     os.makedirs(os.path.dirname(lib), exist_ok=True)
     subprocess.run(["hipcc", "-Os", "--offload-arch=gfx950", "-std=c++17", "-shared", "-fPIC", "-DPOM_TRUNC", "-I" + ROOT + "/include",
                     "-I" + ROOT + "/pomcpp_amd/csrc", "-o", lib, ROOT + "/pomcpp_amd/csrc/pom_batch.hip"], check=True)
-    if a.build_only:
-        sys.exit(0)
+if a.build_only:
+    sys.exit(0)
+os.environ["POM_LIB"] = lib  # what pomcpp_amd loads (pomcpp_amd/_abi.py; assigning batch.library_path no longer reaches the loader)
 import pomcpp_amd.batch as B
-B.library_path = lambda: lib
 import pomcpp_amd as pa
 if a.policy:
     env = B.BatchEnvironment(a.envs, mode=B.MODE_ENV, auto_reset=True, max_steps=800, streams=1, fresh_boards=True, board_seed=1)

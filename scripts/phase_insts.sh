@@ -1,5 +1,6 @@
 #!/bin/bash
 # scripts/phase_insts.sh <out dir> [phase_insts.py args] — one rocprofv3 --pmc run per cut; prints the per-phase differences
+# (POM_TRUNC_LIB=<library>: count that POM_TRUNC build instead of building this tree's)
 REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$1; shift
 case $OUT in /*) ;; *) OUT=$REPO/$OUT ;; esac
