@@ -748,6 +748,50 @@ typedef struct PomMoveSafetySpec {
 } PomMoveSafetySpec;
 int pom_batch_move_safety(PomBatch* h, const PomMoveSafetySpec* spec);
 
+/*
+ * REACH: where can an agent walk, how far is it, and which way does it start?  The reference's reachability map — strategy::FillRMap
+ * and, for every reached cell, MoveTowardsPosition (src/bboard/strategy.cpp:58-120, include/strategy.hpp:29-63) — of every asked agent
+ * of every env in ONE launch, without touching the batch.  SimpleAgent runs the same search on the device for the one target its
+ * decision is about (pom_batch_policy_simple); this call hands out the whole map: a distance plane for a network, "walk to the nearest
+ * power-up" composed on top of pom_batch_forecast and pom_batch_move_safety, reward shaping.
+ * Semantics: for every env e < n and agent a of agent_mask:
+ *          agent a dead in the env's current State (AgentInfo::dead, bboard.hpp:239): both rows [e][a] are all zero.
+ *          Otherwise let r be what FillRMap(state, r, a) leaves.
+ *          dist[e][a][y][x] (nullable; uint8 [n][4][11][11]) = r.GetDistance(x, y) if that is <= max_dist, else 0.  0 is the source
+ *          itself or a cell not reached.  All of the reference's rules hold: the search is breadth-first from the agent's cell, passage
+ *          and power-ups are walked through (IS_WALKABLE, bboard.hpp:77-84), a cell showing any agent is reached but not walked
+ *          through (strategy.cpp:49-52), bomb, flame, wood and rigid cells block, and the source is never re-entered and keeps 0
+ *          (:82-89) — an agent standing on its own bomb starts like any other.
+ *          move[e][a][y][x] (nullable; uint8 [n][4][11][11]) = the Move that MoveTowardsPosition(r, {x, y}) returns, for every cell
+ *          with dist != 0: 1 UP, 2 DOWN, 3 LEFT, 4 RIGHT — the first step of the path the map's predecessors describe, which is the
+ *          lexicographically smallest of the cell's shortest paths under FillRMap's neighbour order DOWN, UP, RIGHT, LEFT.  0 (IDLE)
+ *          elsewhere: the reference spins forever when asked for the source or for a cell not reached, so 0 is unambiguous.
+ *          With move_dev alone the rule is the same: cells farther than max_dist are 0.
+ * Rows:    the rows [e][a] of agents outside agent_mask are not written.  At least one of the two outputs is given.
+ * Nothing else changes: after the call nothing this API can read differs from before — records, snapshots and terminal records,
+ *          status and the envs' ubflags, POM_CNT_*, episode counters, the handle's tick, agent memory, chain statistics.
+ * Ordering: exactly as pom_batch_forecast — chained launches are settled and the sub-streams joined first, then ONE launch on the
+ *          handle's stream; the outputs are written in stream order.  Every launch shape of the handle gives the same bytes (the
+ *          device buffers are 16-env tiles whatever the shape).
+ * POM_E_ARG (with a pom_last_error text naming pom_batch_reach; nothing is written): a null handle or spec, struct_size !=
+ *          sizeof(PomReachSpec) (POM_REACH_SPEC_SIZE), agent_mask outside 1 .. 15, max_dist outside 1 .. POM_REACH_MAX_DIST, nonzero
+ *          reserved_ or reserved2_, both outputs null, an output not 8-byte aligned.
+ * Not here: a range or stream form, fogged reach (a viewer's window), a job list, IsInDanger / SafeDirections planes
+ *          (pom_batch_forecast answers the danger question better), the raw predecessor index, a fused step + reach.
+ */
+enum { POM_REACH_MAX_DIST = 120 }; /* no cell of an 11 x 11 board is farther than 120 steps */
+enum { POM_REACH_SPEC_SIZE = 40 }; /* 4 x int32, 2 pointers, int64: no implicit padding on an LP64 target */
+typedef struct PomReachSpec {
+    int32_t struct_size; /*  0  = sizeof(PomReachSpec) */
+    int32_t agent_mask;  /*  4  bit a: agent a's map is computed; 1..15 */
+    int32_t max_dist;    /*  8  1..POM_REACH_MAX_DIST: cells farther away are reported as not reached */
+    int32_t reserved_;   /* 12  must be 0 */
+    uint8_t* dist_dev;   /* 16  nullable: uint8 [n][4][11][11], 8-byte aligned */
+    uint8_t* move_dev;   /* 24  nullable: uint8 [n][4][11][11], 8-byte aligned; at least one of the two outputs is given */
+    int64_t reserved2_;  /* 32  must be 0 */
+} PomReachSpec;
+int pom_batch_reach(PomBatch* h, const PomReachSpec* spec);
+
 /* A stand-in for a learned policy in measurements and tests of the closed loop (NOT part of the stepper): one launch on `stream`
  * that writes Move[4] of the envs [first, first + count) into moves_dev (int32 [n][4]).  codes_dev != NULL: the POM_OBS_CODES
  * observation of the batch (uint8 [n][5][11][11]) — every byte of the range's observations is read and the moves depend on them;

@@ -27,7 +27,7 @@ from ._abi import (  # noqa: F401 (the binding's names are this module's too: ca
     CNT_STEPS, CNT_EPISODES, CNT_RESETS, CNT_UB_TICKS, ISSUE_AUTO, ISSUE_DIRECT, ISSUE_THREADS, ISSUE_GRAPH, ISSUE_CHAIN,
     COPY_FROM_SNAPSHOT, COPY_SET_SNAPSHOT, UB_LOST_AGENT, UB_NULL_BOMB, UB_QUEUE_OVERFLOW, UB_REVERT_LOOP, UB_BAD_INDEX,
     UB_FLAME_QUEUE_RANGE, ROLLOUT_FRESH_AGENTS, RO_NONE, RO_ALIVE, RO_DONE, RO_DRAW, RO_TIMEOUT, RO_UB, RO_WINNER_SHIFT,
-    RO_WINNER_MASK, RO_LENGTH_SHIFT, PomError, _Options, _ViewSpec, _ForecastSpec, _MoveSafetySpec, _RolloutSpec,
+    RO_WINNER_MASK, RO_LENGTH_SHIFT, REACH_MAX_DIST, PomError, _Options, _ViewSpec, _ForecastSpec, _MoveSafetySpec, _ReachSpec, _RolloutSpec,
     _RolloutPolicySpec, _RolloutJobsSpec, _ExpandSpec, _MixedStepSpec, _ptr, _spec, _view_spec, _forecast_spec, library_path, load_library, _check)
 from .state import STATE_DTYPE
 
@@ -107,6 +107,22 @@ def decode_rollout(result) -> dict:
         bits, i32 = w[..., None] >> torch.arange(4, device=w.device) & 1, lambda a: a.to(torch.int32)  # noqa: E731
     return {"alive": bits != 0, "done": (w & RO_DONE) != 0, "draw": (w & RO_DRAW) != 0, "timeout": (w & RO_TIMEOUT) != 0,
             "ub": (w & RO_UB) != 0, "winner": i32(((w & RO_WINNER_MASK) >> RO_WINNER_SHIFT) - 1), "length": i32(w >> RO_LENGTH_SHIFT)}
+
+
+def move_towards(reach: dict, targets):
+    """Walk to the nearest target: int32 [n, 4], per env and agent the `move` entry of the target cell with the smallest nonzero
+    `dist` — ties go to the lowest cell index y * 11 + x — and 0 (IDLE) where no target is reached (a dead agent's rows reach
+    nothing).  `reach`: what BatchEnvironment.reach() returns, both tensors; `targets`: bool [n, 4, 11, 11] on their device, e.g.
+    the power-up cells of an observation, the same for all four agents.  Pure torch: no library call, no copy to the host."""
+    import torch
+    dist, move = reach["dist"], reach["move"]
+    if targets.dtype != torch.bool or tuple(targets.shape) != tuple(dist.shape) or tuple(move.shape) != tuple(dist.shape):
+        raise ValueError(f"targets must be bool {list(dist.shape)}, as reach's tensors are, got {targets.dtype} {list(targets.shape)}")
+    d = dist.flatten(2).to(torch.int32)
+    # a key per cell that orders by distance, then by cell index: no target or not reached sorts behind every real key
+    key = torch.where(targets.flatten(2) & (d != 0), d * 128 + torch.arange(121, device=d.device, dtype=torch.int32), 1 << 20)
+    best, cell = key.min(dim=2)
+    return torch.where(best < (1 << 20), move.flatten(2).gather(2, cell.unsqueeze(2)).squeeze(2).to(torch.int32), 0)
 
 
 def chain_litmus(tiles: int, launches: int, streams: int, device: int = 0) -> dict:
@@ -636,6 +652,29 @@ class BatchEnvironment:
         """The action mask: bool [n, 4, 6], True where move_safety()'s escape_tick is 0 — the agent is alive and, having made the
         move, still has somewhere to be when the horizon ends.  Rows of dead agents and of agents not asked for are all False."""
         return self.move_safety(horizon, agents, moves, death=False)["escape_tick"] == 0
+
+    # ---- reach: every agent's FillRMap distances and first moves in one launch (pom_batch_reach) --------------
+    def reach(self, agents=None, max_dist: int = REACH_MAX_DIST, out=None, dist: bool = True, move: bool = True) -> dict:
+        """Where can an agent walk, how far is it, and which way does it start: the reference's reachability map (strategy::FillRMap
+        and MoveTowardsPosition) of every agent of `agents` (a mask int 1..15 or an iterable of agent ids; None: all four) in every
+        env by one kernel on the handle's stream; the batch itself is left exactly as it is (pom_batch_reach, include/pom_batch.h).
+        Returns a dict of uint8 [n, 4, 11, 11] tensors on the handle's device, indexed [env, agent, y, x]: with `dist` `dist`, the
+        walking distance from the agent's cell (0: the agent's own cell, a cell it cannot reach, or one farther than `max_dist`,
+        1..120), with `move` `move`, the first step of the reference's path to the cell (1 UP, 2 DOWN, 3 LEFT, 4 RIGHT; 0 where
+        dist is 0).  A dead agent's rows are 0.  `out`: a dict with tensors of an earlier call under the same names, written in
+        place of new ones.  The rows of agents not asked for are 0 in a tensor this call allocates and left as they were in a
+        caller's.  move_towards(reach, targets) picks the step to the nearest of a set of cells."""
+        max_dist = _bounded(max_dist, "max_dist", 1, REACH_MAX_DIST)
+        mask = 0xF if agents is None else _agent_mask(agents, "agents")
+        if mask == 0:
+            raise ValueError("agents names nobody")
+        want = {name: ((self.n, 4, 11, 11), "uint8") for name, wanted in (("dist", dist), ("move", move)) if wanted}
+        if not want:
+            raise ValueError("dist and move are both False: nothing to compute")
+        res = self._outputs(out, want, fill=None if mask == 0xF else 0)
+        with self._ordered():
+            self._call("pom_batch_reach", C.byref(_spec(_ReachSpec, mask, max_dist, 0, _ptr(res.get("dist")), _ptr(res.get("move")), 0)))
+        return res
 
     # ---- rollout: R random playouts of every env (pom_batch_rollout) ---------------------------------------
     def rollout(self, horizon: int, samples: int, seed: int, dist: int = DIST_RANDOM, moves=None, out=None, *, simple=None, first=None,

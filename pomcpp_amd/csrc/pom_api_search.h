@@ -2,6 +2,8 @@
  * pom_api_search.h — the search entry points: calls that play ahead on scratch copies and leave the batch as it is (forecast, the
  * three rollouts, move safety), and the expansion that copies listed games into slots and plays them one tick.  Each kernel header
  * is included right in front of its entry point, after every other kernel of the library: the order kernels are emitted in stays.
+ * (pom_batch_reach's kernel came after pom_api_mixed.h's: pom_batch.hip includes pom_reach.h behind that, and the entry point here
+ * reaches it through a launch function.)
  */
 #ifndef POM_API_SEARCH_H_
 #define POM_API_SEARCH_H_
@@ -262,6 +264,35 @@ extern "C" int pom_batch_move_safety(PomBatch* h, const PomMoveSafetySpec* s)
     p.tiles = (uint32_t)tiles;
     p.tiles8 = (uint32_t)tiles8;
     pom_move_safety_kernel<<<dim3((unsigned)(tiles8 * variants)), dim3(64), 0, h->stream>>>(p);
+    HIPCHK(hipGetLastError());
+    return POM_OK;
+}
+
+/* ---- the reach (pom_batch.h PomReachSpec): every asked agent's FillRMap distances and first moves, one launch.  Its kernel header,
+ * pom_reach.h, is the last thing pom_batch.hip includes — behind pom_step_mixed.h, so that every kernel before it is emitted as it
+ * was —: here the kernel is known by its launch function only ---- */
+static void pom_reach_launch(const uint32_t* state, int64_t n, int32_t agent_mask, int32_t max_dist, uint8_t* dist, uint8_t* move,
+                             uint32_t tiles, uint32_t tiles8, hipStream_t stream);
+
+static_assert(sizeof(PomReachSpec) == POM_REACH_SPEC_SIZE, "pom_batch.h states the size");
+
+extern "C" int pom_batch_reach(PomBatch* h, const PomReachSpec* s)
+{
+    static const char who[] = "pom_batch_reach";
+    const char* what = !h ? "the handle is NULL" : SPEC_HEAD(PomReachSpec, s);
+    /* tiles of 16 envs, rounded up to a multiple of 8 as the rollouts' grid (rollout_begin); a variant per agent of the mask */
+    const int64_t tiles = h ? (h->n + 15) / 16 : 0, tiles8 = (tiles + 7) / 8 * 8;
+    if (what) {}
+    else if (s->reserved2_ != 0) what = "reserved2_ must be 0";
+    else if (s->agent_mask < 1 || s->agent_mask > 15) what = "agent_mask must be 1..15";
+    else if (s->max_dist < 1 || s->max_dist > POM_REACH_MAX_DIST) what = "max_dist must be 1..120";
+    else if (!s->dist_dev && !s->move_dev) what = "dist_dev and move_dev are both NULL";
+    else if (((uintptr_t)s->dist_dev & 7) || ((uintptr_t)s->move_dev & 7)) what = "dist_dev and move_dev must be 8-byte aligned";
+    static_assert((((int64_t)1 << 30) / 16 + 8) * 4 < (int64_t)INT_MAX, "four variants of the largest batch (create_plan) fit one grid");
+    /* settled, not only joined (as pom_batch_forecast): after chained launches a tile left behind is caught up first — the maps are
+     * those of the state a download returns */
+    if (int rc = begin_call(h, who, POM_SETTLED, what)) return rc;
+    pom_reach_launch(h->state, h->n, s->agent_mask, s->max_dist, s->dist_dev, s->move_dev, (uint32_t)tiles, (uint32_t)tiles8, h->stream);
     HIPCHK(hipGetLastError());
     return POM_OK;
 }
