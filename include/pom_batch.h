@@ -792,6 +792,63 @@ typedef struct PomReachSpec {
 } PomReachSpec;
 int pom_batch_reach(PomBatch* h, const PomReachSpec* spec);
 
+/*
+ * VIEW MEMORY: what each agent saw last, and how long ago.  The fogged views (PomViewSpec) are what an agent sees at one tick; every
+ * agent, scripted or learned, merges them into a memory in its next line: keep what was seen, count remembered bombs and flames down,
+ * stop believing in an enemy at a cell once it is visibly elsewhere or dead.  This call does that merge for the envs
+ * [first, first + count) and the agents of agent_mask in ONE launch on `stream` (NULL: the handle's stream), in place of the view
+ * export of a closed loop, not behind it: pom_batch_step_device_range / pom_batch_step_mixed without an observation, then this call on
+ * the same stream.  A stated heuristic, as escape_tick is: the reference has no fog and no memory.
+ * memory:  uint8 [n][4][6][11][11], caller-owned, sized for the WHOLE batch, 4-byte aligned (an env's four views are 2,904 bytes).  View v
+ *          of env e belongs to agent v, alive or dead.  Planes 0..4 hold POM_OBS_CODES bytes (board code, bomb strength, bomb life, bomb
+ *          direction, flame life), plane 5 is the AGE: 0 seen this tick, 1..254 ticks since the cell was last seen (saturating), 255 never
+ *          seen in this game.  A WIPED view has board 5 (Item::FOG) in every cell, planes 1..4 = 0 and age 255.
+ * stamp:   int32 [n][4][2], caller-owned, 8-byte aligned: (episode, timeStep) of the view's last update; episode -1 = no memory yet.
+ * THE RULE, per env e of the range and agent v of the mask (other views and their stamp rows are not touched).  ep: the env's episode
+ *          counter (pom_batch_episodes), t: its timeStep (env_attrs), (ep0, t0): the stamp.
+ *          1 Wipe or age.  If ep0 != ep or t < t0 (a new game; a batch put back to an earlier state) the view is wiped.  Otherwise
+ *            dt = min(t - t0, 255), and every cell OUTSIDE the viewer's window — PomViewSpec's: the agent's position as agent_attrs gives
+ *            it, a dead agent looks out from where it died — goes through, in this order:
+ *            1.1 a cell with age 255 stays as it is;
+ *            1.2 a remembered bomb (life byte > 0): life = max(life - dt, 0); at 0 it is forgotten — planes 1..3 become 0, a board byte 3
+ *                becomes 0, an agent code standing on it stays.  Remembered bombs do not move;
+ *            1.3 a remembered flame (board 4): flame life = max(life - dt, 0); at 0 the board becomes 0;
+ *            1.4 a stale agent (board 10 + a): cleared if agent a is dead by the public alive flags or a's present position lies inside
+ *                v's window (v sees it elsewhere; the viewer itself is always such an agent) — to board 3 if the cell's bomb life after
+ *                1.2 is above 0, else to 0;
+ *            1.5 age = min(age + dt, 254).
+ *            With dt = 0 none of 1.1 - 1.5 is applied.  Wood, power-ups and walls are kept as remembered.
+ *          2 Copy the window.  Every cell INSIDE the window gets the five bytes pom_batch_observe(POM_OBS_CODES) writes for it now,
+ *            verbatim, and age 0.
+ *          3 Stamp := (ep, t).
+ *          So: two calls at one tick equal one; a call every k-th tick ages by k; view_radius 10 gives the unfogged code planes, age 0.
+ * What stamps do not catch: pom_batch_copy_envs / pom_batch_expand into a slot, or pom_batch_upload over it, at an equal or later
+ *          timeStep of the same episode number — the caller sets those stamp rows to -1.  An env's four views are one call's business:
+ *          two calls on the same env at the same time are not supported, whatever their masks.
+ * viewer_attrs, env_attrs (nullable): exactly PomViewSpec's, written for the range.
+ * Nothing else changes: records, snapshots and terminal records, status and ubflags, POM_CNT_*, episode counters, the handle's tick,
+ *          agent memory, chain statistics.
+ * Ordering: as pom_batch_step_device_range — whole tiles, quad shape, the handle is settled, nothing is forked or joined, ONE launch
+ *          ordered by `stream` alone, no synchronising runtime call once the handle is settled (capturable behind a range step).
+ * POM_E_ARG (with a pom_last_error text naming pom_batch_remember_view; nothing is written): a null spec, struct_size !=
+ *          sizeof(PomMemorySpec) (POM_MEMORY_SPEC_SIZE), view_radius outside 0..10, agent_mask outside 1..15, nonzero reserved_, a null
+ *          memory_dev or stamp_dev, memory_dev not 4-byte or stamp_dev not 8-byte aligned, attribute pointers not 16-byte aligned,
+ *          whatever pom_batch_step_device_range refuses of a range or a handle.
+ * Not here: the merge fused into the step kernels, other element types than the code bytes, remembered bombs that move.
+ */
+enum { POM_MEMORY_PLANES = 6, POM_MEMORY_AGE_NEVER = 255, POM_MEMORY_AGE_MAX = 254, POM_MEMORY_SPEC_SIZE = 48 };
+typedef struct PomMemorySpec {
+    int32_t struct_size;       /*  0  = sizeof(PomMemorySpec) */
+    int32_t view_radius;       /*  4  0..POM_VIEW_RADIUS_MAX, Chebyshev */
+    int32_t agent_mask;        /*  8  bit v: agent v's memory is updated; 1..15 */
+    int32_t reserved_;         /* 12  must be 0 */
+    uint8_t* memory_dev;       /* 16  uint8 [n][4][POM_MEMORY_PLANES][11][11] */
+    int32_t* stamp_dev;        /* 24  int32 [n][4][2] */
+    int32_t* viewer_attrs_dev; /* 32  nullable: int32 [n][4][POM_OBS_VIEWER_ATTRS] */
+    int32_t* env_attrs_dev;    /* 40  nullable: as pom_batch_observe */
+} PomMemorySpec;
+int pom_batch_remember_view(PomBatch* h, int64_t first, int64_t count, const PomMemorySpec* spec, void* stream);
+
 /* A stand-in for a learned policy in measurements and tests of the closed loop (NOT part of the stepper): one launch on `stream`
  * that writes Move[4] of the envs [first, first + count) into moves_dev (int32 [n][4]).  codes_dev != NULL: the POM_OBS_CODES
  * observation of the batch (uint8 [n][5][11][11]) — every byte of the range's observations is read and the moves depend on them;

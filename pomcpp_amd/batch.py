@@ -27,7 +27,8 @@ from ._abi import (  # noqa: F401 (the binding's names are this module's too: ca
     CNT_STEPS, CNT_EPISODES, CNT_RESETS, CNT_UB_TICKS, ISSUE_AUTO, ISSUE_DIRECT, ISSUE_THREADS, ISSUE_GRAPH, ISSUE_CHAIN,
     COPY_FROM_SNAPSHOT, COPY_SET_SNAPSHOT, UB_LOST_AGENT, UB_NULL_BOMB, UB_QUEUE_OVERFLOW, UB_REVERT_LOOP, UB_BAD_INDEX,
     UB_FLAME_QUEUE_RANGE, ROLLOUT_FRESH_AGENTS, RO_NONE, RO_ALIVE, RO_DONE, RO_DRAW, RO_TIMEOUT, RO_UB, RO_WINNER_SHIFT,
-    RO_WINNER_MASK, RO_LENGTH_SHIFT, REACH_MAX_DIST, PomError, _Options, _ViewSpec, _ForecastSpec, _MoveSafetySpec, _ReachSpec, _RolloutSpec,
+    RO_WINNER_MASK, RO_LENGTH_SHIFT, REACH_MAX_DIST, MEMORY_PLANES, MEMORY_AGE_NEVER, MEMORY_AGE_MAX, PomError, _Options, _ViewSpec, _ForecastSpec,
+    _MoveSafetySpec, _ReachSpec, _MemorySpec, _RolloutSpec,
     _RolloutPolicySpec, _RolloutJobsSpec, _ExpandSpec, _MixedStepSpec, _ptr, _spec, _view_spec, _forecast_spec, library_path, load_library, _check)
 from .state import STATE_DTYPE
 
@@ -123,6 +124,18 @@ def move_towards(reach: dict, targets):
     key = torch.where(targets.flatten(2) & (d != 0), d * 128 + torch.arange(121, device=d.device, dtype=torch.int32), 1 << 20)
     best, cell = key.min(dim=2)
     return torch.where(best < (1 << 20), move.flatten(2).gather(2, cell.unsqueeze(2)).squeeze(2).to(torch.int32), 0)
+
+
+def new_view_memory(n: int, device=None):
+    """A wiped (memory, stamp) pair for BatchEnvironment.remember(): `memory` uint8 [n, 4, 6, 11, 11] with board 5 (fog), planes 1..4
+    = 0 and age 255 in every cell, `stamp` int32 [n, 4, 2] of -1 ("no memory yet"); torch tensors on `device` (a torch device, a GPU's
+    index, or None: cuda:0)."""
+    import torch
+    dev = torch.device("cuda", 0 if device is None else device) if device is None or isinstance(device, int) else torch.device(device)
+    memory = torch.zeros((int(n), 4, MEMORY_PLANES, 11, 11), dtype=torch.uint8, device=dev)
+    memory[:, :, 0] = 5
+    memory[:, :, MEMORY_PLANES - 1] = MEMORY_AGE_NEVER
+    return memory, torch.full((int(n), 4, 2), -1, dtype=torch.int32, device=dev)
 
 
 def chain_litmus(tiles: int, launches: int, streams: int, device: int = 0) -> dict:
@@ -675,6 +688,36 @@ class BatchEnvironment:
         with self._ordered():
             self._call("pom_batch_reach", C.byref(_spec(_ReachSpec, mask, max_dist, 0, _ptr(res.get("dist")), _ptr(res.get("move")), 0)))
         return res
+
+    # ---- view memory: the fogged views merged into what each agent remembers (pom_batch_remember_view) ------------
+    def remember(self, memory, stamp, view_radius: int = 4, agents=None, first: int = 0, count: Optional[int] = None, stream=None,
+                 viewer_attrs=None, env_attrs=None) -> None:
+        """What each agent saw last and how long ago (pom_batch_remember_view; include/pom_batch.h states THE RULE): the fogged views of
+        the agents of `agents` (a mask int 1..15 or an iterable of agent ids; None: all four) of the envs [first, first + count) —
+        whole tiles of 16; no count: all from `first` on — merged into `memory`, uint8 [n, 4, 6, 11, 11] (planes 0..4 the code bytes of
+        observe(dtype="codes"), plane 5 the age: 0 seen now, 1..254 ticks ago, 255 never), as ONE launch on `stream` (a raw
+        hipStream_t / torch stream; None: the handle's stream), in place of the view export of a closed loop: step_device_range() or
+        step_mixed() without an observation, then this on the same stream.  Cells inside a viewer's window (`view_radius` 0..10) are
+        copied with age 0; outside it remembered bombs and flames count down, agents seen elsewhere or dead are cleared and the age
+        grows.  `stamp`, int32 [n, 4, 2], holds each view's (episode, timeStep) of its last update: a new game, a restore() or a
+        stamp of -1 wipes the view first.  new_view_memory(n) makes a wiped pair; after copy_envs() / expand() / make_game() onto an
+        env set its stamp rows to -1.  Optionally `viewer_attrs` int32 [n, 4, 12] and `env_attrs` int32 [n, 4], as observe(view_radius=)
+        returns them.  Every array is sized for the WHOLE batch; only the range's rows of the mask's views are written.  The batch is
+        left exactly as it is.  The tensors are checked as step_device_range() checks its own — a ValueError before anything is
+        launched, no runtime call; a raw device address passes unchecked — and nothing is forked or joined: the stream orders the call."""
+        first, count = self._in_batch(*self._span(int(first), count))
+        view_radius = _bounded(view_radius, "view_radius", 0, 10)
+        mask = 0xF if agents is None else _agent_mask(agents, "agents")
+        if mask == 0:
+            raise ValueError("agents names nobody")
+        for t, what, dtype, shape in ((memory, "memory", "uint8", (self.n, 4, MEMORY_PLANES, 11, 11)), (stamp, "stamp", "int32", (self.n, 4, 2)),
+                                      (viewer_attrs, "viewer_attrs", "int32", (self.n, 4, 12)), (env_attrs, "env_attrs", "int32", (self.n, 4))):
+            if hasattr(t, "data_ptr"):
+                self._device_tensor(t, what, dtype, shape)
+            elif t is None and what in ("memory", "stamp"):
+                raise ValueError(f"{what} must be a device tensor {self._want(dtype, shape)} or a device address, got None")
+        spec = _spec(_MemorySpec, view_radius, mask, 0, _ptr(memory), _ptr(stamp), _ptr(viewer_attrs), _ptr(env_attrs))
+        self._call("pom_batch_remember_view", first, count, C.byref(spec), getattr(stream, "cuda_stream", stream))
 
     # ---- rollout: R random playouts of every env (pom_batch_rollout) ---------------------------------------
     def rollout(self, horizon: int, samples: int, seed: int, dist: int = DIST_RANDOM, moves=None, out=None, *, simple=None, first=None,
