@@ -503,6 +503,10 @@ public:
     // in one launch, no restart played; a result word (POM_RO_*) per child, optionally the observation of the new nodes; src_dev[j] =
     // first + j is a masked step; all pointers of the spec are DEVICE memory (pom_batch_expand)
     void Expand(const PomExpandSpec& spec) { pom_check(pom_batch_expand(h_, &spec)); }
+    // search under fog without peeking: game spec.first + j is built from row spec.view_dev[j] of an agent's view memory, what that agent
+    // never saw drawn by (spec.seed, view, sample); a result word (POM_IMAGINE_*) per job; the built games are for the calls that never
+    // restart a game; all pointers of the spec are DEVICE memory (pom_batch_imagine)
+    void Imagine(const PomImagineSpec& spec) { pom_check(pom_batch_imagine(h_, &spec)); }
     bool IsDone(int64_t e) { return Query(e, 0) != 0; }
     bool IsDraw(int64_t e) { return Query(e, 2) != 0; }
     int GetWinner(int64_t e) { return Query(e, 1); }

@@ -16,5 +16,5 @@ from .state import (  # noqa: F401
     is_flame, is_wood, is_powerup, is_agent, queue_get,
 )
 from .boards import make_boards  # noqa: F401
-from .batch import (BatchEnvironment, PomError, library_path, load_library, decode_rollout, move_towards, new_view_memory,  # noqa: F401
+from .batch import (BatchEnvironment, PomError, library_path, load_library, decode_rollout, move_towards, new_view_memory, decode_imagine,  # noqa: F401
                     RESET_OFF, RESET_AT_START, RESET_AT_END)

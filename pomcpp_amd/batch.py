@@ -28,7 +28,8 @@ from ._abi import (  # noqa: F401 (the binding's names are this module's too: ca
     COPY_FROM_SNAPSHOT, COPY_SET_SNAPSHOT, UB_LOST_AGENT, UB_NULL_BOMB, UB_QUEUE_OVERFLOW, UB_REVERT_LOOP, UB_BAD_INDEX,
     UB_FLAME_QUEUE_RANGE, ROLLOUT_FRESH_AGENTS, RO_NONE, RO_ALIVE, RO_DONE, RO_DRAW, RO_TIMEOUT, RO_UB, RO_WINNER_SHIFT,
     RO_WINNER_MASK, RO_LENGTH_SHIFT, REACH_MAX_DIST, MEMORY_PLANES, MEMORY_AGE_NEVER, MEMORY_AGE_MAX, PomError, _Options, _ViewSpec, _ForecastSpec,
-    _MoveSafetySpec, _ReachSpec, _MemorySpec, _RolloutSpec,
+    _MoveSafetySpec, _ReachSpec, _MemorySpec, _ImagineSpec, _RolloutSpec, IMAGINE_SAMPLE, IMAGINE_PASSAGE, IMAGINE_BUILT, IMAGINE_DROPPED_BOMBS,
+    IMAGINE_DROPPED_FLAMES, IMAGINE_NO_ROOM, IMAGINE_UNKNOWN_SHIFT, IMAGINE_DRAWN_SHIFT,
     _RolloutPolicySpec, _RolloutJobsSpec, _ExpandSpec, _MixedStepSpec, _ptr, _spec, _view_spec, _forecast_spec, library_path, load_library, _check)
 from .state import STATE_DTYPE
 
@@ -108,6 +109,22 @@ def decode_rollout(result) -> dict:
         bits, i32 = w[..., None] >> torch.arange(4, device=w.device) & 1, lambda a: a.to(torch.int32)  # noqa: E731
     return {"alive": bits != 0, "done": (w & RO_DONE) != 0, "draw": (w & RO_DRAW) != 0, "timeout": (w & RO_TIMEOUT) != 0,
             "ub": (w & RO_UB) != 0, "winner": i32(((w & RO_WINNER_MASK) >> RO_WINNER_SHIFT) - 1), "length": i32(w >> RO_LENGTH_SHIFT)}
+
+
+def decode_imagine(word) -> dict:
+    """The fields of imagine()'s result words (torch tensor or numpy array of any shape [...], int32 or uint32): `built`,
+    `dropped_bombs`, `dropped_flames`, `no_room` bool [...], `unknown` (the never-seen cells of the view) int32 [...], `drawn` bool
+    [..., 4] (agent a was placed by a draw); the same kind of array as the input, on its device.  A word of 0 is "no job"."""
+    w = word
+    if isinstance(w, np.ndarray):
+        w = w.astype(np.int64) & 0xFFFFFFFF
+        bits, i32 = (w >> IMAGINE_DRAWN_SHIFT)[..., None] >> np.arange(4) & 1, lambda a: a.astype(np.int32)  # noqa: E731
+    else:
+        import torch
+        w = w.to(torch.int64) & 0xFFFFFFFF
+        bits, i32 = (w >> IMAGINE_DRAWN_SHIFT)[..., None] >> torch.arange(4, device=w.device) & 1, lambda a: a.to(torch.int32)  # noqa: E731
+    return {"built": (w & IMAGINE_BUILT) != 0, "dropped_bombs": (w & IMAGINE_DROPPED_BOMBS) != 0, "dropped_flames": (w & IMAGINE_DROPPED_FLAMES) != 0,
+            "no_room": (w & IMAGINE_NO_ROOM) != 0, "unknown": i32((w >> IMAGINE_UNKNOWN_SHIFT) & 0xFF), "drawn": bits != 0}
 
 
 def move_towards(reach: dict, targets):
@@ -718,6 +735,54 @@ class BatchEnvironment:
                 raise ValueError(f"{what} must be a device tensor {self._want(dtype, shape)} or a device address, got None")
         spec = _spec(_MemorySpec, view_radius, mask, 0, _ptr(memory), _ptr(stamp), _ptr(viewer_attrs), _ptr(env_attrs))
         self._call("pom_batch_remember_view", first, count, C.byref(spec), getattr(stream, "cuda_stream", stream))
+
+    # ---- imagine: playable games from an agent's view memory (pom_batch_imagine) ----------------------------
+    def imagine(self, memory, viewer_attrs, view, first: int = 0, sample=None, seed: int = 0, unknown: str = "sample", belief=None,
+                out=None, stream=None):
+        """Determinization, for search under fog without peeking (pom_batch_imagine; include/pom_batch.h states THE RULE): env
+        `first + j` becomes a playable game built from row `view[j]` = e * 4 + v of `memory` (uint8 [m, 4, 6, 11, 11], what remember()
+        maintains — of this batch or any other) and `viewer_attrs` (int32 [m, 4, 12], as remember() or observe(view_radius=) write them),
+        with sample number `sample[j]` (None: j) and `seed` keying every draw for what the viewer never saw: the same (view, sample)
+        builds the same game in any slot.  `view`, `sample`: int32 [count] device tensors (or numpy arrays, which are copied there);
+        a view < 0 or >= 4 m is "no job".  `unknown`: "sample" draws a never-seen cell from the start board's distribution, "passage"
+        makes it passage.  `belief`: None, or int32 [m, 4, 4, 3], (maxBombCount, bombStrength, canKick) of agent a as viewer v believes
+        them.  Returns the result words, int32 [count] on the handle's device holding the header's uint32 words (decode_imagine names
+        the fields); `out`: such a tensor of an earlier call.  A built env is left as make_game() leaves one — status clear, the record
+        also its restart snapshot, fresh SimpleAgent memory; episode counters, counters and the handle's tick are untouched — and is
+        meant for the calls that never restart a game: forecast(), the rollouts, expand(), move_safety(), reach().  ONE launch on
+        `stream` (a raw hipStream_t / torch stream; None: the handle's stream, ordered with torch's current one)."""
+        def device_tensor(a, what, shape):  # numpy arrays are copied to the device, anything else is _device_tensor's
+            if isinstance(a, np.ndarray):
+                if not np.issubdtype(a.dtype, np.integer):
+                    raise ValueError(f"{what} must be an integer array")
+                torch, dev = self._torch_device()
+                a = torch.from_numpy(np.ascontiguousarray(a, dtype="int32")).to(dev)
+            return self._device_tensor(a, what, "int32", shape)
+
+        if unknown not in ("sample", "passage"):
+            raise ValueError('unknown must be "sample" or "passage"')
+        view = device_tensor(view, "view", (None,))
+        count = int(view.shape[0])
+        first, _ = self._in_batch(first, count)
+        if sample is not None:
+            sample = device_tensor(sample, "sample", (count,))
+        memory = self._device_tensor(memory, "memory", "uint8", (None, 4, MEMORY_PLANES, 11, 11))
+        m = int(memory.shape[0])
+        self._device_tensor(viewer_attrs, "viewer_attrs", "int32", (m, 4, 12))
+        if belief is not None:
+            self._device_tensor(belief, "belief", "int32", (m, 4, 4, 3))
+        if m == 0 and count:
+            raise ValueError("memory holds no view")
+        out = self._out_tensor(out, (count,), "int32")
+        raw = getattr(stream, "cuda_stream", stream)
+        spec = _spec(_ImagineSpec, IMAGINE_SAMPLE if unknown == "sample" else IMAGINE_PASSAGE, first, count, 4 * max(m, 1), 0, _u64(seed),
+                     *_job_ptrs(count, view, sample, memory, viewer_attrs, belief, out), raw)
+        if raw is None:
+            with self._ordered():
+                self._call("pom_batch_imagine", C.byref(spec))
+        else:
+            self._call("pom_batch_imagine", C.byref(spec))
+        return out
 
     # ---- rollout: R random playouts of every env (pom_batch_rollout) ---------------------------------------
     def rollout(self, horizon: int, samples: int, seed: int, dist: int = DIST_RANDOM, moves=None, out=None, *, simple=None, first=None,
