@@ -930,6 +930,102 @@ typedef struct PomImagineSpec {
 } PomImagineSpec;
 int pom_batch_imagine(PomBatch* h, const PomImagineSpec* spec);
 
+/*
+ * DEAL: Pommerman's standard start board, drawn on the device.  pom_batch_generate and fresh_boards draw the REFERENCE's board
+ * (pom_boardgen.h: every cell on its own, about 17 rigid and 17 wood, agents in the corners, nothing cleared around them).  The game
+ * the 9x9 views, the view memory, pom_batch_imagine and the search calls aim at starts on another board: mirror-symmetric, exact counts
+ * of walls, woods and hidden items, every agent one cell in from its corner with free cells beside it, wooden lanes between neighbours,
+ * and rejected if too many of its passages are walled off.  This call deals that board for any range of envs, as a pure function of
+ * (seed, env, game number), into the env's record and restart snapshot (POM_DEAL_START) or into the restart snapshot alone
+ * (POM_DEAL_NEXT: the board the env's NEXT restart lands on — how a closed loop gets a new board for every game without any change to a
+ * step kernel).  The reference has no such generator: THE RULE below is the specification, modelled on the Pommerman playground's
+ * make_board / make_items but written from memory, not from its source — where the two differ, this header holds.
+ * tests/deal_oracle.py is its slow, literal checker.
+ *
+ * Coordinates: cell c = y * 11 + x; agents numbered as PutAgentsInCorners numbers them (0 top left, 1 top right, 2 bottom right, 3
+ * bottom left).
+ * Layout.     PomBoardLayout {num_rigid, num_wood, num_items, max_inaccessible, flags}; the standard one is {36, 36, 20, 4, 0}.  flags
+ *             bit 0, POM_LAYOUT_NO_LANES: clause 2's cells are passage instead.  L = 12 lane woods (0 with POM_LAYOUT_NO_LANES).  Refused
+ *             unless num_rigid and num_wood are even and >= 0, num_wood >= L, num_rigid / 2 + (num_wood - L) / 2 <= 40, 0 <= num_items
+ *             <= num_wood, 0 <= max_inaccessible <= 121, and no other flag bit is set.
+ * THE RULE.
+ *          1 Fixed cells.  Agents: 0 at (1,1), 1 at (9,1), 2 at (9,9), 3 at (1,9).  On each of the four lines y = 1, y = 9, x = 1, x = 9
+ *            positions 2, 3, 7, 8 along the line are always passage.  Every diagonal cell x = y that is not an agent's is always passage.
+ *          2 Lanes.  Positions 4, 5, 6 along each of those four lines are wood: 12 cells, which count towards num_wood.
+ *          3 Pairs.  The remaining 80 cells form 40 mirror pairs {(x,y), (y,x)}, x > y, numbered k = 0..39 by ascending c of the member
+ *            with x > y.
+ *          4 Draws.  key = pom_board_key(seed, env_offset + e, g) (pom_boardgen.h; g = the game number as uint32), draw(i) =
+ *            pom_board_draw(key, i), below(d, n) = pom_mulhi32(d, n).
+ *          5 Attempt a = 0..15.  needR = num_rigid / 2, needW = (num_wood - L) / 2.  For k ascending, t = below(draw(64 a + k), 40 - k):
+ *            t < needR: both cells of the pair are rigid, needR goes down by one; else t < needR + needW: both are wood, needW goes down
+ *            by one; else both are passage.  (Sequential sampling: every assignment with those counts is equally likely.)
+ *          6 Acceptance.  R = the cells reachable from (1,1) by 4-neighbour steps over cells that are not rigid (wood and agents' cells
+ *            are stepped over).  bad = the number of passage cells — agents' cells and woods are none — not in R.  The attempt is
+ *            accepted iff bad <= max_inaccessible; the first accepted attempt is the board.  If all 16 are rejected, attempt 15 is the
+ *            board and the result word carries POM_DEAL_FALLBACK.  (The standard layout accepts an attempt with probability about 0.8.)
+ *          7 Items.  Over the wood cells of that board in ascending c, lanes included: `left` counts the woods not yet visited, this
+ *            one included, `need` counts down from num_items: the wood is chosen iff below(draw(1024 + c), left) < need; a chosen wood
+ *            gets flag 1 + below(draw(1280 + c), 3) (1 extra-bomb, 2 incr-range, 3 kick), every other wood flag 0.
+ *          8 The rest is a fresh State as pom_batch_generate makes one, with the agents' positions from clause 1: aliveAgents 4,
+ *            bombCount 0, maxBombCount 1, bombStrength 1, empty queues (every flame slot timeLeft 4), timeStep 0.
+ * The call:   envs [first, first + count), any range (it need not be whole tiles), ONE launch on `stream` (NULL: the handle's).
+ * games_dev:  required, int32 [n], caller-owned, indexed by the env's number in the batch, 4-byte aligned.  For a dealt env e the kernel
+ *             reads g = games[e], deals board (seed, env_offset + e, g) and writes games[e] = g + 1 (2^31 - 1 wraps to -2^31): env e plays
+ *             boards 0, 1, 2, ... of its key, whenever the calls happen.  An env that is not dealt keeps its entry.
+ * which:      the envs of the range that are dealt.  POM_DEAL_ALL: every one.  POM_DEAL_MASK: those with which_dev[e] != 0 (int32 [n]
+ *             by env, required then).  POM_DEAL_RESTARTED: those whose status carries the "restarted" bit (POM_E_ARG unless the handle
+ *             is POM_RESET_AT_END).  POM_DEAL_DONE: those whose status is done.
+ * mode:       POM_DEAL_START: the board becomes the env's record AND its restart snapshot; the env is left as pom_batch_imagine leaves a
+ *             built one — status and ubflags clear, SimpleAgent memory fresh; episode counter and terminal record untouched.
+ *             POM_DEAL_NEXT: the board becomes the restart snapshot ONLY; record, status and memory are as they were.
+ * result_dev: nullable uint32 [n] by env, 4-byte aligned.  A dealt env: POM_DEAL_DEALT | POM_DEAL_FALLBACK | (attempts used - 1) << 8 |
+ *             bad << 16; every other env of the range: 0; outside the range nothing is written.
+ * The closed loop: a POM_RESET_AT_END handle with fresh_boards = 0; deal(START, ALL), deal(NEXT, ALL); after every
+ *             tick deal(NEXT, RESTARTED) on the tick's stream.  The tick restarts a finished env from its snapshot exactly as before, the
+ *             call behind it replaces the snapshot that was used up.  POM_RESET_AT_START: deal(NEXT, DONE) between the ticks.  An env
+ *             that finishes twice between two deals replays a board.
+ * Nothing else changes: POM_CNT_*, episode counters, terminal records, the handle's tick, envs that are not dealt.
+ * Ordering:   the handle is settled (as pom_batch_imagine), then ONE launch and no runtime call beside it: capturable once the handle is
+ *             settled.  Quad shape only.  A POM_DEAL_START call loads and stores whole 16-env tiles (the columns it does not deal leave as they
+ *             came): two START calls in flight on different streams — or a START call beside anything else that writes the batch —
+ *             must not touch the same tile; cut ranges that run on different streams at multiples of 16.  POM_DEAL_NEXT writes its own
+ *             envs' snapshot records and game counters only and has no such limit.
+ * POM_E_ARG (with a pom_last_error text naming pom_batch_deal; nothing is written): a null handle or spec, struct_size !=
+ *             sizeof(PomDealSpec) (POM_DEAL_SPEC_SIZE), nonzero reserved_ or reserved2_, an unknown mode or which, a layout as above, a
+ *             range outside the batch, (count > 0:) a null games_dev, a null which_dev with POM_DEAL_MASK, games_dev, which_dev or
+ *             result_dev not 4-byte aligned, POM_DEAL_RESTARTED on a handle that is not POM_RESET_AT_END, a handle without the quad
+ *             shape.  count == 0 is POM_OK.
+ * Not here:   a layout inside the tick's own fresh_boards path, start abilities other than the reference's, the 2-agent board, a
+ *             host-side numpy twin in the product, the C++ BatchEnvironment, teams.
+ */
+enum { POM_DEAL_START = 0, POM_DEAL_NEXT = 1 };                                          /* mode  */
+enum { POM_DEAL_ALL = 0, POM_DEAL_MASK = 1, POM_DEAL_RESTARTED = 2, POM_DEAL_DONE = 3 }; /* which */
+enum { POM_LAYOUT_NO_LANES = 1 };
+enum { POM_DEAL_DEALT = 1, POM_DEAL_FALLBACK = 2, POM_DEAL_ATTEMPTS_SHIFT = 8, POM_DEAL_BAD_SHIFT = 16, POM_DEAL_SPEC_SIZE = 96 };
+typedef struct PomBoardLayout {
+    int32_t num_rigid;        /* rigid walls, even */
+    int32_t num_wood;         /* woods, lanes included, even */
+    int32_t num_items;        /* woods that hide a power-up */
+    int32_t max_inaccessible; /* clause 6 */
+    int32_t flags;            /* POM_LAYOUT_* */
+} PomBoardLayout;
+typedef struct PomDealSpec {   /* 4 x int32, 2 x int64, uint64, 5 x int32 (layout), int32, 4 pointers: no implicit padding on an LP64 target */
+    int32_t struct_size;       /*  0  = sizeof(PomDealSpec) */
+    int32_t mode;              /*  4  POM_DEAL_START / POM_DEAL_NEXT */
+    int32_t which;             /*  8  POM_DEAL_ALL / _MASK / _RESTARTED / _DONE */
+    int32_t reserved_;         /* 12  must be 0 */
+    int64_t first;             /* 16 */
+    int64_t count;             /* 24 */
+    uint64_t seed;             /* 32 */
+    PomBoardLayout layout;     /* 40 */
+    int32_t reserved2_;        /* 60  must be 0 */
+    int32_t* games_dev;        /* 64  int32 [n] by env: read and counted up */
+    const int32_t* which_dev;  /* 72  POM_DEAL_MASK: int32 [n] by env; else ignored */
+    uint32_t* result_dev;      /* 80  nullable: uint32 [n] by env */
+    void* stream;              /* 88  NULL: the handle's stream */
+} PomDealSpec;
+int pom_batch_deal(PomBatch* h, const PomDealSpec* spec);
+
 /* A stand-in for a learned policy in measurements and tests of the closed loop (NOT part of the stepper): one launch on `stream`
  * that writes Move[4] of the envs [first, first + count) into moves_dev (int32 [n][4]).  codes_dev != NULL: the POM_OBS_CODES
  * observation of the batch (uint8 [n][5][11][11]) — every byte of the range's observations is read and the moves depend on them;

@@ -17,4 +17,5 @@ from .state import (  # noqa: F401
 )
 from .boards import make_boards  # noqa: F401
 from .batch import (BatchEnvironment, PomError, library_path, load_library, decode_rollout, move_towards, new_view_memory, decode_imagine,  # noqa: F401
+                    BoardLayout, new_games, decode_deal,
                     RESET_OFF, RESET_AT_START, RESET_AT_END)

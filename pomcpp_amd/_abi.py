@@ -1,4 +1,4 @@
-"""The ctypes mirror of include/pom_batch.h, and nothing else: its constants, its twelve spec structures with their builders, the
+"""The ctypes mirror of include/pom_batch.h, and nothing else: its constants, its thirteen spec structures with their builders, the
 prototype of every function it declares (PROTOTYPES) and the loading of libpom_batch.so.  Whatever is written here is written a
 second time in the header; tests/test_abi_mirror.py compares the two, field by field and argument by argument, without the library.
 """
@@ -22,6 +22,10 @@ MEMORY_PLANES, MEMORY_AGE_NEVER, MEMORY_AGE_MAX = 6, 255, 254  # POM_MEMORY_*: a
 IMAGINE_SAMPLE, IMAGINE_PASSAGE = 0, 1  # POM_IMAGINE_*: how pom_batch_imagine fills a never-seen cell
 # its result word: POM_IMAGINE_BUILT, _DROPPED_BOMBS, _DROPPED_FLAMES, _NO_ROOM, _UNKNOWN_SHIFT, _DRAWN_SHIFT
 IMAGINE_BUILT, IMAGINE_DROPPED_BOMBS, IMAGINE_DROPPED_FLAMES, IMAGINE_NO_ROOM, IMAGINE_UNKNOWN_SHIFT, IMAGINE_DRAWN_SHIFT = 1, 2, 4, 8, 8, 16
+DEAL_START, DEAL_NEXT = 0, 1  # POM_DEAL_*: what a dealt env receives (PomDealSpec.mode)
+DEAL_ALL, DEAL_MASK, DEAL_RESTARTED, DEAL_DONE = 0, 1, 2, 3  # which envs of the range are dealt (PomDealSpec.which)
+LAYOUT_NO_LANES = 1  # POM_LAYOUT_NO_LANES
+DEAL_DEALT, DEAL_FALLBACK, DEAL_ATTEMPTS_SHIFT, DEAL_BAD_SHIFT = 1, 2, 8, 16  # pom_batch_deal's result word
 RO_NONE = 0  # POM_RO_NONE: rollout_jobs' word of an entry without a job
 # the result word of a rollout (the header's POM_RO_*)
 RO_ALIVE, RO_DONE, RO_DRAW, RO_TIMEOUT, RO_UB, RO_WINNER_SHIFT, RO_WINNER_MASK, RO_LENGTH_SHIFT = 0xF, 0x10, 0x20, 0x40, 0x80, 8, 0x700, 16
@@ -92,6 +96,21 @@ class _ImagineSpec(C.Structure):
     ]
 
 
+class _BoardLayout(C.Structure):
+    """PomBoardLayout (include/pom_batch.h): the counts of a dealt board; no spec of its own, a member of PomDealSpec"""
+    _fields_ = [("num_rigid", C.c_int32), ("num_wood", C.c_int32), ("num_items", C.c_int32), ("max_inaccessible", C.c_int32), ("flags", C.c_int32)]
+
+
+class _DealSpec(C.Structure):
+    """PomDealSpec (include/pom_batch.h): what a dealt env receives, which envs of the range are dealt, the draws' seed, the layout, the
+    game counters, the mask, the result words, the stream"""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("mode", C.c_int32), ("which", C.c_int32), ("reserved_", C.c_int32), ("first", C.c_int64),
+        ("count", C.c_int64), ("seed", C.c_uint64), ("layout", _BoardLayout), ("reserved2_", C.c_int32), ("games_dev", C.c_void_p),
+        ("which_dev", C.c_void_p), ("result_dev", C.c_void_p), ("stream", C.c_void_p),
+    ]
+
+
 class _RolloutSpec(C.Structure):
     """PomRolloutSpec (include/pom_batch.h): the rollout's horizon, samples, move stream, first-tick moves and result"""
     _fields_ = [
@@ -139,7 +158,7 @@ class _MixedStepSpec(C.Structure):
 
 
 STRUCTURES = {"PomBatchOptions": _Options, "PomViewSpec": _ViewSpec, "PomForecastSpec": _ForecastSpec,
-              "PomMoveSafetySpec": _MoveSafetySpec, "PomReachSpec": _ReachSpec, "PomMemorySpec": _MemorySpec, "PomImagineSpec": _ImagineSpec, "PomRolloutSpec": _RolloutSpec,
+              "PomMoveSafetySpec": _MoveSafetySpec, "PomReachSpec": _ReachSpec, "PomMemorySpec": _MemorySpec, "PomImagineSpec": _ImagineSpec, "PomDealSpec": _DealSpec, "PomRolloutSpec": _RolloutSpec,
               "PomRolloutPolicySpec": _RolloutPolicySpec, "PomRolloutJobsSpec": _RolloutJobsSpec, "PomExpandSpec": _ExpandSpec, "PomMixedStepSpec": _MixedStepSpec}  # the header's name of each
 
 
@@ -181,6 +200,7 @@ PROTOTYPES = (  # (name, argtypes or None: no parameters, restype or None: int)
     ("pom_batch_reach", [_P, C.POINTER(_ReachSpec)], None),
     ("pom_batch_remember_view", [_P, _I64, _I64, C.POINTER(_MemorySpec), _VP], None),
     ("pom_batch_imagine", [_P, C.POINTER(_ImagineSpec)], None),
+    ("pom_batch_deal", [_P, C.POINTER(_DealSpec)], None),
     ("pom_batch_step_device_range", [_P, _I64, _I64, _VP, _VP, _VP, _I32, _I32, _VP, _VP], None),
     ("pom_bench_policy", [_VP, _VP, _I64, _I64, C.c_uint32, _VP], None),
     ("pom_batch_stream", [_P, C.POINTER(C.c_void_p)], None),

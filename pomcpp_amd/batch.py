@@ -29,7 +29,8 @@ from ._abi import (  # noqa: F401 (the binding's names are this module's too: ca
     UB_FLAME_QUEUE_RANGE, ROLLOUT_FRESH_AGENTS, RO_NONE, RO_ALIVE, RO_DONE, RO_DRAW, RO_TIMEOUT, RO_UB, RO_WINNER_SHIFT,
     RO_WINNER_MASK, RO_LENGTH_SHIFT, REACH_MAX_DIST, MEMORY_PLANES, MEMORY_AGE_NEVER, MEMORY_AGE_MAX, PomError, _Options, _ViewSpec, _ForecastSpec,
     _MoveSafetySpec, _ReachSpec, _MemorySpec, _ImagineSpec, _RolloutSpec, IMAGINE_SAMPLE, IMAGINE_PASSAGE, IMAGINE_BUILT, IMAGINE_DROPPED_BOMBS,
-    IMAGINE_DROPPED_FLAMES, IMAGINE_NO_ROOM, IMAGINE_UNKNOWN_SHIFT, IMAGINE_DRAWN_SHIFT,
+    IMAGINE_DROPPED_FLAMES, IMAGINE_NO_ROOM, IMAGINE_UNKNOWN_SHIFT, IMAGINE_DRAWN_SHIFT, _BoardLayout, _DealSpec, DEAL_START, DEAL_NEXT, DEAL_ALL,
+    DEAL_MASK, DEAL_RESTARTED, DEAL_DONE, LAYOUT_NO_LANES, DEAL_DEALT, DEAL_FALLBACK, DEAL_ATTEMPTS_SHIFT, DEAL_BAD_SHIFT,
     _RolloutPolicySpec, _RolloutJobsSpec, _ExpandSpec, _MixedStepSpec, _ptr, _spec, _view_spec, _forecast_spec, library_path, load_library, _check)
 from .state import STATE_DTYPE
 
@@ -125,6 +126,63 @@ def decode_imagine(word) -> dict:
         bits, i32 = (w >> IMAGINE_DRAWN_SHIFT)[..., None] >> torch.arange(4, device=w.device) & 1, lambda a: a.to(torch.int32)  # noqa: E731
     return {"built": (w & IMAGINE_BUILT) != 0, "dropped_bombs": (w & IMAGINE_DROPPED_BOMBS) != 0, "dropped_flames": (w & IMAGINE_DROPPED_FLAMES) != 0,
             "no_room": (w & IMAGINE_NO_ROOM) != 0, "unknown": i32((w >> IMAGINE_UNKNOWN_SHIFT) & 0xFF), "drawn": bits != 0}
+
+
+def decode_deal(word) -> dict:
+    """The fields of deal()'s result words (torch tensor or numpy array of any shape [...], int32 or uint32): `dealt`, `fallback` bool
+    [...] (all 16 attempts were rejected: the board is the last one), `attempts` (used, 1..16) and `bad` (passages walled off from
+    agent 0's cell) int32 [...]; the same kind of array as the input, on its device.  A word of 0: the env was not dealt."""
+    w = word
+    if isinstance(w, np.ndarray):
+        w, i32 = w.astype(np.int64) & 0xFFFFFFFF, lambda a: a.astype(np.int32)  # noqa: E731
+    else:
+        import torch
+        w, i32 = w.to(torch.int64) & 0xFFFFFFFF, lambda a: a.to(torch.int32)  # noqa: E731
+    dealt = (w & DEAL_DEALT) != 0
+    return {"dealt": dealt, "fallback": (w & DEAL_FALLBACK) != 0, "attempts": i32(((w >> DEAL_ATTEMPTS_SHIFT) & 0xFF) + dealt),
+            "bad": i32((w >> DEAL_BAD_SHIFT) & 0xFF)}
+
+
+class BoardLayout:
+    """The counts of a dealt start board (PomBoardLayout, include/pom_batch.h): `num_rigid` rigid walls and `num_wood` woods (both even;
+    the woods include the 12 of the lanes between neighbouring agents unless `no_lanes`), `num_items` woods that hide a power-up,
+    `max_inaccessible` passages that may be walled off from agent 0's cell before an attempt is rejected.  The default is Pommerman's
+    standard board: 36, 36, 20, 4.  A layout the library would refuse raises ValueError here."""
+    __slots__ = ("num_rigid", "num_wood", "num_items", "max_inaccessible", "flags")
+
+    def __init__(self, num_rigid: int = 36, num_wood: int = 36, num_items: int = 20, max_inaccessible: int = 4, no_lanes: bool = False):
+        self.num_rigid, self.num_wood, self.num_items = int(num_rigid), int(num_wood), int(num_items)
+        self.max_inaccessible, self.flags = int(max_inaccessible), LAYOUT_NO_LANES if no_lanes else 0
+        lanes = 0 if no_lanes else 12
+        for name in ("num_rigid", "num_wood"):
+            if getattr(self, name) < 0 or getattr(self, name) % 2:
+                raise ValueError(f"{name} must be even and >= 0")
+        if self.num_wood < lanes:
+            raise ValueError("num_wood must hold the 12 lane woods (or no_lanes=True)")
+        if self.num_rigid // 2 + (self.num_wood - lanes) // 2 > 40:
+            raise ValueError("num_rigid / 2 + (num_wood - lane woods) / 2 must be <= 40: the board has 40 free mirror pairs")
+        if not 0 <= self.num_items <= self.num_wood:
+            raise ValueError("num_items must be 0..num_wood")
+        if not 0 <= self.max_inaccessible <= 121:
+            raise ValueError("max_inaccessible must be 0..121")
+
+    def as_tuple(self):
+        return self.num_rigid, self.num_wood, self.num_items, self.max_inaccessible, self.flags
+
+    def __repr__(self):
+        return f"BoardLayout({self.num_rigid}, {self.num_wood}, {self.num_items}, {self.max_inaccessible}, no_lanes={bool(self.flags)})"
+
+
+def new_games(n: int, device=None):
+    """The game counters deal() reads and counts up: int32 [n] of zeros, a torch tensor on `device` (a torch device, a GPU's index, or
+    None: cuda:0).  Entry e is the number of the next board env e is dealt."""
+    import torch
+    dev = torch.device("cuda", 0 if device is None else device) if device is None or isinstance(device, int) else torch.device(device)
+    return torch.zeros((int(n),), dtype=torch.int32, device=dev)
+
+
+_DEAL_MODES = {"start": DEAL_START, "next": DEAL_NEXT}
+_DEAL_WHICH = {"all": DEAL_ALL, "restarted": DEAL_RESTARTED, "done": DEAL_DONE}
 
 
 def move_towards(reach: dict, targets):
@@ -782,6 +840,49 @@ class BatchEnvironment:
                 self._call("pom_batch_imagine", C.byref(spec))
         else:
             self._call("pom_batch_imagine", C.byref(spec))
+        return out
+
+    # ---- deal: Pommerman's standard start boards drawn on the device (pom_batch_deal) ------------------------
+    def deal(self, games, seed: int = 0, mode: str = "start", which="all", first: int = 0, count: Optional[int] = None, layout=None,
+             out=None, stream=None):
+        """Pommerman's standard start board — mirror-symmetric, 36 rigid walls, 36 woods, 20 hidden items, every agent one cell in from
+        its corner, lanes of wood between neighbours, rejected if too many passages are walled off — for the envs [first, first + count)
+        (any range; no count: all from `first` on), drawn on the device as ONE launch (pom_batch_deal; include/pom_batch.h states THE
+        RULE).  generate() and fresh_boards give the reference's board instead.  `games`: int32 [n] device tensor (new_games(n)), by
+        env: a dealt env e gets board (seed, env_offset + e, games[e]) and games[e] goes up by one.  `which`: "all", "restarted" (the
+        envs the last tick restarted; RESET_AT_END handles), "done" (the finished ones), or an int32 [n] device tensor: the envs with a
+        nonzero entry.  `mode`: "start" — the board is the env's state and its restart snapshot, status clear, fresh SimpleAgent memory
+        — or "next" — it is the restart snapshot only: the board the env's next restart lands on; deal(games, seed, "next",
+        "restarted") after every tick of a closed loop gives every game a new board.  `layout`: a BoardLayout (None: the standard one).
+        `out`: None, or an int32 [n] device tensor for the result words, by env (decode_deal names the fields; envs of the range that
+        are not dealt get 0, envs outside it are not written); returned.  `stream`: a raw hipStream_t / torch stream; None: the
+        handle's stream, ordered with torch's current one.  The tensors are checked as step_device_range() checks its own — a
+        ValueError before anything is launched, no runtime call."""
+        if mode not in _DEAL_MODES:
+            raise ValueError('mode must be "start" or "next"')
+        mask = None
+        if isinstance(which, str):
+            if which not in _DEAL_WHICH:
+                raise ValueError('which must be "all", "restarted", "done" or a mask tensor')
+            which_code = _DEAL_WHICH[which]
+        else:
+            mask, which_code = self._device_tensor(which, "which", "int32", (self.n,)), DEAL_MASK
+        first, count = self._in_batch(*self._span(int(first), count))
+        self._device_tensor(games, "games", "int32", (self.n,))
+        if layout is None:
+            layout = BoardLayout()
+        elif not isinstance(layout, BoardLayout):
+            raise ValueError(f"layout must be a BoardLayout, got {type(layout).__name__}")
+        if out is not None:
+            self._device_tensor(out, "out", "int32", (self.n,))
+        raw = getattr(stream, "cuda_stream", stream)
+        spec = _spec(_DealSpec, _DEAL_MODES[mode], which_code, 0, first, count, _u64(seed), _BoardLayout(*layout.as_tuple()), 0,
+                     *_job_ptrs(count, games, mask, out), raw)
+        if raw is None:
+            with self._ordered():
+                self._call("pom_batch_deal", C.byref(spec))
+        else:
+            self._call("pom_batch_deal", C.byref(spec))
         return out
 
     # ---- rollout: R random playouts of every env (pom_batch_rollout) ---------------------------------------
