@@ -156,6 +156,54 @@ def cases():
         assert w == BUILT | (3 << 8) and s["board"][0, :5].tolist() == [1, 0, 0, 0, 1]
     out.append(_case("garbage_byte_on_a_known_cell", 0, m, attrs_of(0, 5, 5, others=(0, 0, 0)), garbage))
 
+    # bytes beyond what a record holds (clauses 1, 4, 5).  Four bombs on row 0: (8, 0) is an ordinary one and leads the queue by its life 9;
+    # the others have life 40, 16, 255 -> time 15, strength 200, 16 -> 15 (3 stays), direction 7, 5 -> 0 (4 stays), in cell order.  The viewer's
+    # bombCount 300 is more than there are bombs: all four are its own, and it is stored as 107.  Flame bytes 200, 127, 128 are all life 127:
+    # (1, 3) and (2, 3) are one flame of strength 1, (4, 3) behind the gap another.  A life byte on wood, passage, a power-up and a burnt-out
+    # flame (fl 0) makes no bomb: the cells are what their board byte says
+    m = seen(wiped(), 1)
+    put(m, 1, 2, 0, 3, strength=200, life=40, direction=7)
+    put(m, 1, 4, 0, 3, strength=16, life=16, direction=4)
+    put(m, 1, 6, 0, 3, strength=3, life=255, direction=5)
+    put(m, 1, 8, 0, 3, strength=2, life=9, direction=2)
+    put(m, 1, 1, 3, 4, flame=200)
+    put(m, 1, 2, 3, 4, flame=127)
+    put(m, 1, 4, 3, 4, flame=128)
+    put(m, 1, 3, 6, 2, strength=5, life=9)
+    put(m, 1, 5, 6, 0, life=7)
+    put(m, 1, 7, 6, 6, life=3)
+    put(m, 1, 9, 6, 4, life=5)
+    put(m, 1, 9, 9, 13)
+
+    def clamped_bombs(s, w):
+        assert w == BUILT and s["bombs_count"] == 4 and s["bombs_index"] == 0
+        assert s["bombs_queue"][:5].tolist() == [bomb(8, 0, 1, 2, 9, 2), bomb(2, 0, 1, 15, 15), bomb(4, 0, 1, 15, 15, 4), bomb(6, 0, 1, 3, 15), 0]
+        assert s["board"][0].tolist() == [0, 0, Item.BOMB, 0, Item.BOMB, 0, Item.BOMB, 0, Item.BOMB, 0, 0]
+        assert s["flames_count"] == 2 and s["flames_index"] == 0
+        assert [tuple(int(k) for k in f) for f in s["flames_queue"][:3]] == [(1, 3, 127, 1), (4, 3, 127, 0), (0, 0, 0, 0)]
+        assert s["board"][3].tolist() == [0, Item.FLAMES + (34 << 3), Item.FLAMES + (34 << 3), 0, Item.FLAMES + (37 << 3), 0, 0, 0, 0, 0, 0]
+        assert s["board"][6, 3] >> 8 == 2 and s["board"][6, 5] == 0 and s["board"][6, 7] == 6 and s["board"][6, 9] == 0
+        assert s["board"][5, 5] == A0 + 1 and s["board"][9, 9] == A0 + 3 and (s["board"] != 0).sum() == 4 + 3 + 2 + 2
+        assert tuple(s["agents"][1])[:6] == (5, 5, 107, 2, 1, 0) and tuple(s["agents"][3])[:6] == (9, 9, 0, 1, 1, 0) and s["aliveAgents"] == 2
+    out.append(_case("clamped_bombs_and_flames", 1, m, attrs_of(1, 5, 5, bombs=300, max_bombs=2, others=(0, 1, 0)), clamped_bombs))
+
+    # a viewer row beyond the board and the record (clauses 4, 6): (-3, 14) is (0, 10); bombCount -500 is stored as -108 and owns nothing — the
+    # one bomb goes to agent 0, the only other one alive —, maxBombCount 40000 is 32646, bombStrength 200 is 134, canKick 7 is 1.  (One row
+    # holds one bombCount: the count larger than the bombs is clamped_bombs_and_flames'.)  The viewer's own code where it no longer stands
+    # places nobody: passage
+    m = seen(wiped(), 3)
+    put(m, 3, 4, 4, 10, age=2)
+    put(m, 3, 7, 7, 3, strength=2, life=6)
+    put(m, 3, 2, 2, 13, age=5)
+
+    def clamped_viewer(s, w):
+        assert w == BUILT and s["board"][10, 0] == A0 + 3 and s["board"][4, 4] == A0 and s["board"][7, 7] == Item.BOMB and s["board"][2, 2] == 0
+        assert (s["board"] != 0).sum() == 3 and s["bombs_count"] == 1 and s["bombs_queue"][:2].tolist() == [bomb(7, 7, 0, 2, 6), 0]
+        assert tuple(s["agents"][3])[:6] == (0, 10, -108, 32646, 134, 1) and tuple(s["agents"][0])[:6] == (4, 4, 1, 1, 1, 0)
+        assert [int(d) for d in s["agents"]["dead"]] == [0, 1, 1, 0] and s["aliveAgents"] == 2 and s["timeStep"] == 799 and s["flames_count"] == 0
+    out.append(_case("clamped_viewer_attrs", 3, m, attrs_of(3, -3, 14, bombs=-500, max_bombs=40000, strength=200, kick=7, others=(1, 0, 0), t=799),
+                     clamped_viewer))
+
     # an unseen enemy goes to a cell the viewer does not see NOW: three stale passage cells among cells seen this tick — and to any
     # passage cell when every cell is seen now
     m = seen(wiped(), 0)

@@ -79,7 +79,9 @@ def _same(a, b):
 def test_the_cases_cover_every_clause():
     assert {c["name"] for c in CASES} >= {
         "wiped_viewer_alone", "bomb_under_an_agent", "21_bombs", "21_flame_pieces", "flames_L_and_cross", "dead_viewer", "dead_enemys_stale_code",
-        "no_room", "garbage_byte_on_a_known_cell", "unseen_enemy_where_the_viewer_does_not_look", "unseen_enemy_all_seen"}
+        "no_room", "garbage_byte_on_a_known_cell", "unseen_enemy_where_the_viewer_does_not_look", "unseen_enemy_all_seen",
+        "clamped_bombs_and_flames", "clamped_viewer_attrs"}
+    assert len(CASES) == 13
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: c["name"])
