@@ -34,6 +34,15 @@ FATAL = UB_NULL_BOMB | UB_QUEUE_OVERFLOW | UB_REVERT_LOOP | UB_BAD_INDEX
 BOMBCOUNT_MIN, BOMBCOUNT_MAX, MAXBOMBS_MAX, STRENGTH_MAX, ALIVE_MIN = -108, 107, 32646, 134, -124
 
 
+def uploadable(s):
+    """the agent fields and aliveAgents within upload's bounds (pom_packed.h POM_PACK_*)"""
+    a = s["agents"]
+    return bool((a["bombCount"] >= BOMBCOUNT_MIN).all() and (a["bombCount"] <= BOMBCOUNT_MAX).all()
+                and (a["maxBombCount"] >= -32768).all() and (a["maxBombCount"] <= MAXBOMBS_MAX).all()
+                and (a["bombStrength"] >= 0).all() and (a["bombStrength"] <= STRENGTH_MAX).all()
+                and ALIVE_MIN <= int(s["aliveAgents"]) <= 127)
+
+
 @dataclass
 class Entry:
     name: str

@@ -14,7 +14,8 @@ import numpy as np
 import pytest
 
 from pomcpp_amd.state import STATE_DTYPE
-from tests.edge_states import ALIVE_MIN, BOMBCOUNT_MAX, BOMBCOUNT_MIN, MAXBOMBS_MAX, STRENGTH_MAX
+from tests.edge_states import BOMBCOUNT_MAX, BOMBCOUNT_MIN, MAXBOMBS_MAX
+from tests.edge_states import uploadable as _uploadable
 from tests.policy_edge_states import check_memory
 from tests.test_policy_fixtures import _replay_on_gpu
 
@@ -88,15 +89,6 @@ def _origin_unreachable_chase(s, i, mem):
         return False
     target = next(j for j in range(4) if not a["dead"][j] and (int(a["x"][j]), int(a["y"][j])) != (0, 0) and dist(j) <= 7)
     return (int(a["x"][target]), int(a["y"][target])) not in _reach(s, 0, 0)
-
-
-def _uploadable(s):
-    """the agent fields and aliveAgents within upload's bounds (pom_packed.h POM_PACK_*)"""
-    a = s["agents"]
-    return bool((a["bombCount"] >= BOMBCOUNT_MIN).all() and (a["bombCount"] <= BOMBCOUNT_MAX).all()
-                and (a["maxBombCount"] >= -32768).all() and (a["maxBombCount"] <= MAXBOMBS_MAX).all()
-                and (a["bombStrength"] >= 0).all() and (a["bombStrength"] <= STRENGTH_MAX).all()
-                and ALIVE_MIN <= int(s["aliveAgents"]) <= 127)
 
 
 def test_fixture_reaches_what_it_claims(fx):
