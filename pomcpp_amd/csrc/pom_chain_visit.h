@@ -37,9 +37,27 @@ __device__ __forceinline__ uint32_t pom_chain_xcd()
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(x));
     return x & 0xFu;
 }
+/* The address of an atomic that ONE lane issues (its caller stands behind `if (lane == 0)`).  The compiler cannot see that: it wraps
+ * every atomic add on a wave-uniform address in its wave-reduction form — count the active lanes, a second exec bracket, a multiply; a
+ * scalar loop over the active lanes where the value is not uniform; a multiply-add to hand every lane its own old value.  An address
+ * that has been through a vector register counts as lane-varying and is left alone: the same vector atomic of the same order and scope,
+ * issued by the one lane, without the scaffolding (profiles/queue_first_trip_ab.txt). */
+template <bool ONE_LANE, class T>
+__device__ __forceinline__ auto pom_one_lane_address(T* p)
+{
+    if constexpr (ONE_LANE) {
+        /* (named a global address: behind the asm the compiler no longer sees where the pointer came from, and would issue a flat atomic) */
+        auto g = (__attribute__((address_space(1))) T*)p;
+        asm("" : "+v"(g));
+        return g;
+    } else {
+        return p;
+    }
+}
 /* Take a ticket for the tile's word and wait for the visit before it.  true: the tile is this wavefront's to play — its record, as
  * the previous visit stored it, may be loaded NOW (past the vector cache: sc1).  false: nothing may be touched (the tile is, or
  * has just been, poisoned; the flag word says why). */
+template <bool ONE_LANE = false> /* the step kernels: the ticket as a plain one-lane atomic (pom_one_lane_address) */
 __device__ __forceinline__ bool pom_chain_enter(unsigned long long* word, uint32_t chain_xcd, uint32_t chain_seq0, uint32_t tape_len, uint64_t wait_limit,
                                                 uint32_t* err, int lane, PomChainVisit& v)
 {
@@ -50,7 +68,7 @@ __device__ __forceinline__ bool pom_chain_enter(unsigned long long* word, uint32
 #endif
     /* take a ticket: the old value says which visit of the tile this is — and, mostly, that the visit before it is stored */
     unsigned long long w = 0;
-    if (lane == 0) w = __hip_atomic_fetch_add(word, 1ull << POM_CHAIN_TICKET_SHIFT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane == 0) w = __hip_atomic_fetch_add(pom_one_lane_address<ONE_LANE>(word), 1ull << POM_CHAIN_TICKET_SHIFT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     w = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(w >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)w);
     const uint32_t visit = (uint32_t)(w >> POM_CHAIN_TICKET_SHIFT);
     /* which tick: the call's first tick + how far this visit is from the call's first visit — a signed distance: launches of
@@ -105,10 +123,11 @@ __device__ __forceinline__ bool pom_chain_enter(unsigned long long* word, uint32
 }
 /* Hand the tile on: called after the record's stores have been ISSUED; waits until the L2 has acknowledged them, then counts the
  * visit as stored (which is what the next visitor polls for). */
+template <bool ONE_LANE = false>
 __device__ __forceinline__ void pom_chain_leave(unsigned long long* word, int lane, const PomChainVisit& v)
 {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0) __hip_atomic_fetch_add(word, v.done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane == 0) __hip_atomic_fetch_add(pom_one_lane_address<ONE_LANE>(word), v.done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 #endif /* POM_CHAIN_VISIT_H_ */

@@ -129,6 +129,8 @@ __global__ __launch_bounds__(64 * POM_WPB, (POLICY ? 4 : G == 4 ? POM_QUAD_WAVES
     static_assert(!CHAIN || SINGLE, "chained launches play one tick each");
     static_assert(!OBS || (SINGLE && !CHAIN && !POLICY && POM_WPB == 1), "the fused observation exists for the one-tick explicit-move shape");
     static_assert(!VIEW || OBS, "the fogged views are a kind of fused observation");
+    /* the one-tick kernels' ticket, hand-on and wave-counter adds are issued as plain one-lane atomics (pom_one_lane_address) */
+    constexpr bool ONE_LANE_ATOMICS = SINGLE && !(POM_TAKE_OUT & 8);
     static_assert(!SINGLE || G == 4, "the one-tick instantiation exists for the quad shape");
     static_assert(G == 1 || (G == 4 && EPW == 16), "a quad per env needs 16 envs per wavefront");
     static_assert(!POLICY || G == 4, "the policy runs one agent per lane of the quad");
@@ -206,7 +208,7 @@ __global__ __launch_bounds__(64 * POM_WPB, (POLICY ? 4 : G == 4 ? POM_QUAD_WAVES
     PomChainVisit cv; /* CHAIN: this wavefront's visit of its tile */
     if (CHAIN) {
         unsigned long long* const word = p.tile_seq + tile_id * POM_CHAIN_WORD_STRIDE;
-        if (!pom_chain_enter(word, chain_xcd, p.chain_seq0, p.tape_len, p.chain_wait_limit, p.chain_err, lane, cv)) return;
+        if (!pom_chain_enter<ONE_LANE_ATOMICS>(word, chain_xcd, p.chain_seq0, p.tape_len, p.chain_wait_limit, p.chain_err, lane, cv)) return;
         tick0 += (uint32_t)cv.dist;
         /* the loads below are issued after the word has been seen: the record they fetch is the stored one */
         load_tile16_x4<POM_REC_DWORDS, 16>(p.state + tile_id * POM_TILE_DWORDS, tile, lane);
@@ -483,7 +485,7 @@ __global__ __launch_bounds__(64 * POM_WPB, (POLICY ? 4 : G == 4 ? POM_QUAD_WAVES
         pom_observe_tile<OBS_PASS_ENVS_FUSED, VIEW>(op, tile, reinterpret_cast<uint4*>(tile + POM_REC_DWORDS * EPW), tile_id, lane);
     }
     if (CHAIN) { /* the record's stores have been acknowledged by the L2 before the word that hands the tile on is written */
-        pom_chain_leave(p.tile_seq + tile_id * POM_CHAIN_WORD_STRIDE, lane, cv);
+        pom_chain_leave<ONE_LANE_ATOMICS>(p.tile_seq + tile_id * POM_CHAIN_WORD_STRIDE, lane, cv);
 #if defined(POM_CHAIN_DIAG)
         if (lane == 0) { /* per tile, summed over launches: cycles to the ticket, cycles polling, cycles in all, polls */
             unsigned long long* d = p.tile_seq + (p.block_end - p.block0) * POM_CHAIN_WORD_STRIDE + 68 * tile_id;
@@ -520,7 +522,7 @@ __global__ __launch_bounds__(64 * POM_WPB, (POLICY ? 4 : G == 4 ? POM_QUAD_WAVES
     if (lane == 0) {
         /* each wavefront owns its slot, so nothing contends; the adds are returnless atomics only because those are
          * fire-and-forget — a load / add / store would keep the finished wavefront alive for a global round trip */
-        unsigned long long* wc = reinterpret_cast<unsigned long long*>(p.wave_counters + tile_id * POM_CNT_N);
+        auto* wc = pom_one_lane_address<ONE_LANE_ATOMICS>(reinterpret_cast<unsigned long long*>(p.wave_counters + tile_id * POM_CNT_N));
         __hip_atomic_fetch_add(&wc[POM_CNT_STEPS], (unsigned long long)c_steps, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (c_episodes) __hip_atomic_fetch_add(&wc[POM_CNT_EPISODES], (unsigned long long)c_episodes, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (c_resets) __hip_atomic_fetch_add(&wc[POM_CNT_RESETS], (unsigned long long)c_resets, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

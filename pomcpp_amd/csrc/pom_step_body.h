@@ -64,6 +64,13 @@
 #define POM_N 11
 #define POM_Q 20
 #define POM_STACK_DEPTH 21 /* one frame per queued bomb + the initiating flame */
+/* POM_TAKE_OUT (diagnostic builds, never shipped; same results): the quad path's straight-line first trips put back one by one, to count
+ * what each is worth (profiles/queue_first_trip_valu.txt).  Bit 0 flames_dec, 1 flame_pops, 2 the bomb scan and the bomb pass,
+ * 3 the single-lane atomics of the step kernels (pom_chain_visit.h, pom_kernels.h), 4 the shift-and-OR gathers */
+#ifndef POM_TAKE_OUT
+#define POM_TAKE_OUT 0
+#endif
+#define POM_QUAD_ITEM(A, bit) (A::G == 4 && !(POM_TAKE_OUT & (1 << (bit))))
 
 /* POM_DIAG builds (scripts/phase_stamps.py, never shipped) accumulate s_memtime deltas per phase */
 #if defined(POM_DIAG) && defined(__HIP_DEVICE_COMPILE__)
@@ -880,10 +887,41 @@ struct PomStepper {
      * i = 0, 20, 40, ..., so the head is what the LAST of those visits leaves.  A timeLeft of -128 (the record's 8 bits) is held
      * there and raises POM_UB_FLAME_QUEUE_RANGE: the reference's value only falls further, and a negative timeLeft never reaches 0
      * again, so no pop and no other part of the tick can tell the two apart (pom_state.h). */
+    POM_HD static int flame_dec_word(int f, int& held_any) /* one flame's timeLeft--, with the hold at -128 */
+    {
+        const int held = (f & 0xFF0000) == 0x800000;
+        held_any |= held;
+        return held ? f : (f & ~0xFF0000) | ((f - 0x10000) & 0xFF0000);
+    }
     POM_HD void flames_dec(int& top, int& n)
     {
         top = 0;
         n = L.fCnt;
+        if (POM_QUAD_ITEM(A, 0)) {
+            /* A quad per env: lane `sub` owns offset `sub`, and four offsets cover the queue in almost every wavefront-tick, so the
+             * first trip is played straight-line — no running slot, no loop-carried exit mask.  Offsets sub + 4, ... (and with them
+             * the head's later visits of a queue of more than 20: offsets 20, 40, ... fall to lane 0 again) take the loop, which
+             * most wavefronts skip.  The head is lane 0's word: an empty queue leaves its 0 there. */
+            int held_any = 0;
+            if (a.sub() < L.fCnt) {
+                const int p = wrap20(L.fIdx + a.sub());
+                top = flame_dec_word(a.flame(p), held_any);
+                a.put_flame(p, top);
+            }
+            if (L.fCnt > 4) {
+                int p = wrap20(wrap20(L.fIdx + a.sub()) + 4);
+                POM_NOUNROLL
+                for (int i = a.sub() + 4; i < L.fCnt; i += 4) {
+                    const int nf = flame_dec_word(a.flame(p), held_any);
+                    a.put_flame(p, nf);
+                    if (p == L.fIdx) top = nf;
+                    p = wrap20(p + 4);
+                }
+            }
+            top = a.template gbcast<0>(top);
+            if (a.gor(held_any)) L.ub |= POM_UB_FLAME_QUEUE_RANGE;
+            return;
+        }
         if (L.fCnt <= 0) return;
         /* split over the lanes (offsets i and i+20 fall to the same lane: the head's visits all to lane 0) */
         int p = L.fIdx + a.sub();
@@ -907,8 +945,38 @@ struct PomStepper {
     /* second half: PopFlame (bboard.cpp:148-180) while the head has run out, by the env's own lanes */
     POM_HD void flame_pops(int top, int n)
     {
+        int k = 0;
+        if (POM_QUAD_ITEM(A, 1)) {
+            /* A quad per env: the first pop straight-line, lane r takes arm r.  The head comes from `top`; the centre cell and the
+             * arm's first cell are read together (one round trip instead of two: with lim >= 1 the arm's cell is another cell than
+             * the centre, and no lane writes another lane's arm, so nothing orders that read behind the centre's write).  A second
+             * pop in the same tick — two flames that run out together — goes through the loop below from k = 1. */
+            if ((int)(n <= 0) | (int)(((top >> 16) & 0xFF) != 0)) return;
+            const int x = top & 0xFF, y = (top >> 8) & 0xFF;
+            int s = (top >> 24) & 0xFF;
+            s = s > POM_N ? POM_N : s;
+            if (!oob(x, y)) {
+                const int c0 = y * POM_N + x;
+                const int r = a.sub();
+                const int lim = ray_room(x, y, s, r);
+                const int c = ray_cell(c0, r, lim >= 1); /* (no cell: the centre again, ignored) */
+                const int e0 = a.cell(c0), e1 = a.cell(c);
+                const int to = pc_flame_pops_to(e1, c0, r, 1);
+                if (e0 == POM_C_FLAME + c0) a.set_cell(c0, POM_C_PASSAGE);
+                if ((int)(lim >= 1) & (int)(to >= 0)) a.put_cell(c, to);
+                POM_NOUNROLL
+                for (int i = 2; i <= lim; i++) {
+                    const int ci = ray_cell(c0, r, i);
+                    const int ti = pc_flame_pops_to(a.cell(ci), c0, r, i);
+                    if (ti >= 0) a.put_cell(ci, ti);
+                }
+            }
+            L.fIdx = wrap20(L.fIdx + 1);
+            L.fCnt--;
+            k = 1;
+        }
         POM_NOUNROLL
-        for (int k = 0; k < n; k++) {
+        for (; k < n; k++) {
             const int f = k == 0 ? top : a.flame(L.fIdx); /* the first look needs no trip to the queue */
             if (((f >> 16) & 0xFF) != 0) break; /* nothing pops, so flames[0] stays what it is for the remaining rounds */
             /* PopFlame: every flame cell on the +-strength cross that carries this origin's id gives way to the item
@@ -1086,6 +1154,7 @@ struct PomStepper {
     POM_HD uint32_t pack_moves_quad(int mine) const
     {
         const int c = clamp_move(mine);
+        if (POM_QUAD_ITEM(A, 4)) return (uint32_t)a.gor(c << (4 * a.sub())); /* each lane its nibble, one quad OR */
         return (uint32_t)a.template gbcast<0>(c) | ((uint32_t)a.template gbcast<1>(c) << 4) | ((uint32_t)a.template gbcast<2>(c) << 8) |
                ((uint32_t)a.template gbcast<3>(c) << 12);
     }
@@ -1143,19 +1212,25 @@ struct PomStepper {
             const int pxm = ag_x(av), pym = ag_y(av);
             const int dxm = pxm + mv_dx(mvm), dym = pym + mv_dy(mvm);
             const int pos8 = ag_pos(av);
-            oldp = (uint32_t)a.template gbcast<0>(pos8) | ((uint32_t)a.template gbcast<1>(pos8) << 8) |
-                   ((uint32_t)a.template gbcast<2>(pos8) << 16) | ((uint32_t)a.template gbcast<3>(pos8) << 24);
             const int d8 = ((dxm + 1) & 0xF) | (((dym + 1) & 0xF) << 4);
-            dstp = (uint32_t)a.template gbcast<0>(d8) | ((uint32_t)a.template gbcast<1>(d8) << 8) |
-                   ((uint32_t)a.template gbcast<2>(d8) << 16) | ((uint32_t)a.template gbcast<3>(d8) << 24);
+            constexpr bool by_shift = POM_QUAD_ITEM(A, 4);
+            if (by_shift) { /* each lane shifts its byte into its place, one quad OR each (the form of the bomb pass's nowp) */
+                oldp = (uint32_t)a.gor((int)((uint32_t)pos8 << (8 * m)));
+                dstp = (uint32_t)a.gor((int)((uint32_t)d8 << (8 * m)));
+            } else {
+                oldp = (uint32_t)a.template gbcast<0>(pos8) | ((uint32_t)a.template gbcast<1>(pos8) << 8) |
+                       ((uint32_t)a.template gbcast<2>(pos8) << 16) | ((uint32_t)a.template gbcast<3>(pos8) << 24);
+                dstp = (uint32_t)a.template gbcast<0>(d8) | ((uint32_t)a.template gbcast<1>(d8) << 8) |
+                       ((uint32_t)a.template gbcast<2>(d8) << 16) | ((uint32_t)a.template gbcast<3>(d8) << 24);
+            }
             /* my destination as a position byte: off the board it carries a nibble 15 or 11, which no position has.  Both
              * questions — is my destination somebody's cell; do I, alive, share my cell with a live agent — are asked of all
              * four position bytes at once: an exact zero-byte test of oldp ^ (byte in every byte), my own byte masked out. */
             const uint32_t want = (uint32_t)((dxm & 0xF) | ((dym & 0xF) << 4));
             const uint32_t others = ~(0x80u << (8 * m));
             const uint32_t dead80 = (((uint32_t)deadmask * 0x00204081u) & 0x01010101u) << 7; /* 0x80 in the bytes of dead agents */
-            const uint32_t hit_d = pom_zero_bytes(oldp ^ (want * 0x01010101u)) & others;
-            const uint32_t hit_p = pom_zero_bytes(oldp ^ ((uint32_t)pos8 * 0x01010101u)) & others & ~dead80;
+            const uint32_t hit_d = pom_zero_bytes(oldp ^ (by_shift ? pom_byte_x4(want) : want * 0x01010101u)) & others;
+            const uint32_t hit_p = pom_zero_bytes(oldp ^ (by_shift ? pom_byte_x4((uint32_t)pos8) : (uint32_t)pos8 * 0x01010101u)) & others & ~dead80;
             int mine = (int)(hit_d != 0u) | ((int)((hit_p != 0u) & !ag_dead(av)) << 1);
             mine = a.gor(mine);
             contact = mine & 1;
@@ -1306,6 +1381,53 @@ struct PomStepper {
         explode(pb_x(jb), pb_y(jb), owner_strength(jb), j);
     }
 
+    /* one queued bomb of step_middle's scan, ORed into on_bomb: bit j if it lies under agent j (position bytes posb), bit 4 if it
+     * has a direction */
+    POM_HD static void under_agents(int bw, const int posb[4], int& on_bomb)
+    {
+        const int bp = pb_pos(bw);
+#pragma unroll
+        for (int j = 0; j < 4; j++) on_bomb |= (bp == posb[j]) << j;
+        on_bomb |= (pb_dir(bw) != 0) << 4;
+    }
+    /* one queued bomb (offset k) of step_middle's bomb pass: flags reset, timer decrement folded in, destination noted, the pass's
+     * findings ORed into moving .. movers (step_middle says what they are).  `top` gets the word as written where it is the head of
+     * the queue: HEAD_ALWAYS (the caller knows: lane 0's first trip; the other lanes' words are not looked at), HEAD_NEVER (offsets 4
+     * and up), HEAD_IF_FIRST (k == 0) */
+    enum { HEAD_NEVER = 0, HEAD_ALWAYS = 1, HEAD_IF_FIRST = 2 };
+    POM_HD void bomb_pass_slot(int k, int head, int& top, uint32_t mvp, uint32_t oldp, uint32_t nowp, uint32_t nowdead80, int& moving, int& ripe, uint32_t& cand,
+                               int& late, uint32_t& movers)
+    {
+        int b = pb_set(bomb_at(k), 0xF000000u, 0);
+        const int key = bomb_target_key(b);
+        if (pb_time(b) == 0) {
+            late = 1;
+            b |= 1 << 24;
+        } else {
+            b = (int)((uint32_t)b - (1u << 16));
+        }
+        put_bomb_at(k, b);
+        if (head == HEAD_ALWAYS || (head == HEAD_IF_FIRST && k == 0)) top = b;
+        a.put_bdest(k, key);
+        moving |= pb_dir(b) != 0;
+        movers |= (uint32_t)(pb_dir(b) != 0) << k;
+        const int idx = pb_y(b) * POM_N + pb_x(b);
+        /* loop A, looked at in the same pass (only meaningful if nothing moves, see step_middle): a resting bomb under an
+         * agent that walked onto it this tick means a bounce-back */
+        if (idx < POM_CELLS) {
+            const int e = a.cell(idx);
+            ripe |= (e == POM_C_PASSAGE) | pc_is_flame(e);
+            /* GetAgent (bboard.cpp:289-299) of the bomb's cell: its position byte against the four agents' at once, the dead masked
+             * out, the lowest index wins (nobody: agent 3's fields are read and the answer masked) */
+            const uint32_t hit = pom_zero_bytes(nowp ^ pom_byte_x4((uint32_t)pb_pos(b))) & ~nowdead80;
+            const int sh = __builtin_ctz(hit | 0x80000000u) - 7; /* 8 * index */
+            const int m2 = (mvp >> (sh >> 1)) & 0xF;
+            const int was = (oldp >> sh) & 0xFF;
+            cand |= (uint32_t)(pc_blocks_bomb(e) & (int)(hit != 0u) & (int)(m2 != POM_MOVE_IDLE) & (int)(m2 != POM_MOVE_BOMB) &
+                                 (int)(pb_pos(b) != was)) << k;
+        }
+    }
+
     /* everything between the flame pops and the top-bomb explosions; returns the head of the bomb queue after the timer
      * decrement and the number of rounds the explosion loop may take */
     POM_HD void step_middle(const uint32_t mvp, int& top, int& n)
@@ -1332,13 +1454,18 @@ struct PomStepper {
         /* HasBomb(x, y) is only ever asked about the moving agent's own cell (step.cpp:89,127,152,172) and bombs
          * do not move during the agent loop: one pass over the queue answers it for all four agents */
         int on_bomb = 0; /* bit 4: some queued bomb has a direction (before this tick's kicks) */
-        POM_NOUNROLL
-        for (int k = a.sub(); k < L.bCnt; k += A::G) { /* split over the lanes, OR-combined */
-            const int bw = bomb_at(k);
-            const int bp = pb_pos(bw);
+        /* split over the lanes, OR-combined.  A quad per env: offset `sub` straight-line, the loop only for offsets 4 and up */
+        constexpr bool first_trip = POM_QUAD_ITEM(A, 2);
+        if (first_trip && a.sub() < L.bCnt) under_agents(bomb_at(a.sub()), posb, on_bomb);
+        if (!first_trip || L.bCnt > 4) {
+            POM_NOUNROLL
+            for (int k = a.sub() + (first_trip ? 4 : 0); k < L.bCnt; k += A::G) {
+                const int bw = bomb_at(k);
+                const int bp = pb_pos(bw);
 #pragma unroll
-            for (int j = 0; j < 4; j++) on_bomb |= (bp == posb[j]) << j;
-            on_bomb |= (pb_dir(bw) != 0) << 4;
+                for (int j = 0; j < 4; j++) on_bomb |= (bp == posb[j]) << j;
+                on_bomb |= (pb_dir(bw) != 0) << 4;
+            }
         }
         on_bomb = a.gor(on_bomb);
         POM_STAMP(L, POM_PH_AGENT_PREP);
@@ -1612,15 +1739,15 @@ struct PomStepper {
              * IDLE already to IDLE, and the bombs of such a group that skip their cell test share their cell with one that
              * makes it: without a moving bomb shared cells change nothing.  Rounds 1 - 3 tracked them in a 121-bit occupancy
              * set: ~50 VALU per wavefront-tick for a distinction without a difference.) */
-            int moving = 0;
-            int ripe = 0; /* some bomb's own cell shows PASSAGE or a flame: the only cells loop B's resting case acts on */
-            uint32_t cand = 0; /* queue offsets of the resting bombs under an agent that walked onto them this tick */
             /* TickBombs' timer decrement (step_utility.cpp:226-231) is folded into this pass: nothing between here and TickBombs
              * reads a timer, and loops A / B only replace the position and direction fields of a word, which commutes with
              * `- (1 << 16)` as long as that does not borrow.  A bomb whose timer is already 0 (out-of-order timers)
              * WOULD borrow into the fields above: it is left as it is, marked in the (just cleared, otherwise unused) moved
              * nibble, and decremented where the reference does it, after loop B (the cold pass below). */
-            int late = 0;
+            int moving = 0;
+            int ripe = 0; /* some bomb's own cell shows PASSAGE or a flame: the only cells loop B's resting case acts on */
+            uint32_t cand = 0; /* queue offsets of the resting bombs under an agent that walked onto them this tick */
+            int late = 0;  /* some bomb's timer was 0 already */
             uint32_t movers = 0; /* queue offsets of the bombs with a direction */
             /* where the agents stand NOW (after the agent loop), a byte each, and 0x80 in the bytes of the dead (the dead bit is bit 1 of
              * an agent word's third byte) */
@@ -1635,36 +1762,13 @@ struct PomStepper {
                 const uint32_t nowflags = pom_gather_bytes<2>((uint32_t)L.a0[0], (uint32_t)L.a0[1], (uint32_t)L.a0[2], (uint32_t)L.a0[3]);
                 nowdead80 = (nowflags << 6) & 0x80808080u;
             }
-            POM_NOUNROLL
-            for (int k = a.sub(); k < L.bCnt; k += A::G) { /* split: each lane its own slots, combined below */
-                int b = pb_set(bomb_at(k), 0xF000000u, 0);
-                const int key = bomb_target_key(b);
-                if (pb_time(b) == 0) {
-                    late = 1;
-                    b |= 1 << 24;
-                } else {
-                    b = (int)((uint32_t)b - (1u << 16));
-                }
-                put_bomb_at(k, b);
-                if (k == 0) top = b;
-                a.put_bdest(k, key);
-                moving |= pb_dir(b) != 0;
-                movers |= (uint32_t)(pb_dir(b) != 0) << k;
-                const int idx = pb_y(b) * POM_N + pb_x(b);
-                /* loop A, looked at in the same pass (only meaningful if nothing moves, see below): a resting bomb under an
-                 * agent that walked onto it this tick means a bounce-back */
-                if (idx < POM_CELLS) {
-                    const int e = a.cell(idx);
-                    ripe |= (e == POM_C_PASSAGE) | pc_is_flame(e);
-                    /* GetAgent (bboard.cpp:289-299) of the bomb's cell: its position byte against the four agents' at once, the dead masked
-                     * out, the lowest index wins (nobody: agent 3's fields are read and the answer masked) */
-                    const uint32_t hit = pom_zero_bytes(nowp ^ pom_byte_x4((uint32_t)pb_pos(b))) & ~nowdead80;
-                    const int sh = __builtin_ctz(hit | 0x80000000u) - 7; /* 8 * index */
-                    const int m2 = (mvp >> (sh >> 1)) & 0xF;
-                    const int was = (oldp >> sh) & 0xFF;
-                    cand |= (uint32_t)(pc_blocks_bomb(e) & (int)(hit != 0u) & (int)(m2 != POM_MOVE_IDLE) & (int)(m2 != POM_MOVE_BOMB) &
-                                       (int)(pb_pos(b) != was)) << k;
-                }
+            /* split: each lane its own slots, combined below.  A quad per env: offset `sub` straight-line (lane 0's word is the head of
+             * the queue: no per-trip select), the loop only for offsets 4 and up */
+            if (first_trip && a.sub() < L.bCnt) bomb_pass_slot(a.sub(), HEAD_ALWAYS, top, mvp, oldp, nowp, nowdead80, moving, ripe, cand, late, movers);
+            if (!first_trip || L.bCnt > 4) {
+                POM_NOUNROLL
+                for (int k = a.sub() + (first_trip ? 4 : 0); k < L.bCnt; k += A::G)
+                    bomb_pass_slot(k, first_trip ? HEAD_NEVER : HEAD_IF_FIRST, top, mvp, oldp, nowp, nowdead80, moving, ripe, cand, late, movers);
             }
             if (A::G > 1) {
                 /* one quad reduction for all the flags: cand (offsets 0..19) | ripe | late | moving */

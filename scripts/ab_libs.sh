@@ -1,7 +1,12 @@
 #!/bin/bash
 # A/B of library builds (POM_LIB): usage [REPS=3] [SHAPES="driver long ..."] ab_libs.sh lib1 lib2 ... ; the builds alternate within every
 # repetition.  Shapes: driver (20 steps), long (500 steps: the default `python bench.py`), plain launch, stress, simple, tape, 262144 envs
-run() { python3 bench.py --no-cpu-baseline --no-config3 "$@" 2>/dev/null | python3 -c "import sys,json; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%.2f us %.2f G' % (r['ms_per_step']*1e3, r['value']/1e9))"; }
+# Every bench run has its own time limit (STEP_LIMIT seconds, default 300); the first run that fails or is cut off ends the script.
+set -o pipefail
+run() {
+  timeout -k 10 ${STEP_LIMIT:-300} python3 bench.py --no-cpu-baseline --no-config3 "$@" 2>/dev/null | python3 -c "import sys,json; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%.2f us %.2f G' % (r['ms_per_step']*1e3, r['value']/1e9))" \
+    || { echo "bench.py $* failed (status ${PIPESTATUS[0]}): stopping"; exit 1; }
+}
 SHAPES=${SHAPES:-driver long plain stress simple tape big}
 for rep in $(seq 1 ${REPS:-3}); do for lib in "$@"; do
   export POM_LIB=$PWD/$lib
