@@ -16,8 +16,8 @@ static bool obs_misaligned(const void* planes_dev, int32_t dtype, const void* at
     return ((uintptr_t)planes_dev & (4 * esz - 1)) || ((uintptr_t)attrs_a & 15) || ((uintptr_t)attrs_b & 15);
 }
 
-/* what every call with a plain observation asks of its outputs: what is wrong, or nullptr */
-static const char* observe_args(const void* planes_dev, int32_t dtype, int32_t per_agent, const int32_t* agent_attrs_dev, const int32_t* env_attrs_dev)
+/* what every call with a plain observation asks of its outputs (pom_host.h) */
+const char* observe_args(const void* planes_dev, int32_t dtype, int32_t per_agent, const int32_t* agent_attrs_dev, const int32_t* env_attrs_dev)
 {
     if (!planes_dev) return "planes_dev is NULL";
     if (dtype < POM_OBS_U8 || dtype > POM_OBS_CODES) return "unknown dtype";
@@ -27,9 +27,9 @@ static const char* observe_args(const void* planes_dev, int32_t dtype, int32_t p
     return nullptr;
 }
 
-/* the export kernels' arguments for the whole batch (viewer_attrs / view_radius: the fogged views only) */
-static ObserveParams observe_params(const PomBatch* h, void* planes_dev, int32_t dtype, int32_t per_agent, int32_t* agent_attrs_dev,
-                                    int32_t* env_attrs_dev, int32_t* viewer_attrs_dev = nullptr, int32_t view_radius = 0)
+/* the export kernels' arguments for the whole batch (pom_host.h) */
+ObserveParams observe_params(const PomBatch* h, void* planes_dev, int32_t dtype, int32_t per_agent, int32_t* agent_attrs_dev,
+                             int32_t* env_attrs_dev, int32_t* viewer_attrs_dev, int32_t view_radius)
 {
     ObserveParams p;
     p.state = h->state;
@@ -48,7 +48,7 @@ static ObserveParams observe_params(const PomBatch* h, void* planes_dev, int32_t
 
 /* ---- the fogged views (pom_batch.h PomViewSpec): the observation calls with the four agents' windows ---- */
 static_assert(sizeof(PomViewSpec) == POM_VIEW_SPEC_SIZE, "pom_batch.h states the size");
-static const char* view_args(const PomViewSpec* s)
+const char* view_args(const PomViewSpec* s)
 {
     if (const char* head = SPEC_HEAD(PomViewSpec, s)) return head;
     if (s->dtype < POM_OBS_U8 || s->dtype > POM_OBS_CODES) return "unknown dtype";
@@ -58,7 +58,7 @@ static const char* view_args(const PomViewSpec* s)
         return "planes_dev must be aligned to 4 elements, the attribute pointers to 16 bytes";
     return nullptr;
 }
-static PomObserveOut view_out(const PomViewSpec* s)
+PomObserveOut view_out(const PomViewSpec* s)
 {
     return PomObserveOut{s->planes_dev, nullptr, s->env_attrs_dev, s->dtype, 1, 1, s->view_radius, s->viewer_attrs_dev};
 }

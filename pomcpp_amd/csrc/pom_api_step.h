@@ -6,10 +6,11 @@
 #ifndef POM_API_STEP_H_
 #define POM_API_STEP_H_
 
-#include "pom_api_observe.h"
+#include "pom_chain_host.h"
 
-/* closed-loop stepping: one tick for a range of whole tiles, one launch on the caller's stream, nothing forked or joined */
-static int range_args(PomBatch* h, const char* who, int64_t first, int64_t count, const int32_t* moves_dev)
+/* closed-loop stepping: one tick for a range of whole tiles, one launch on the caller's stream, nothing forked or joined
+ * (range_args: pom_host.h) */
+int range_args(PomBatch* h, const char* who, int64_t first, int64_t count, const int32_t* moves_dev)
 {
     if (int rc = check_range(h, who, first, count)) return rc;
     if (!moves_dev) return refuse(who, "moves_dev is NULL");

@@ -2,10 +2,17 @@
  * pom_batch.hip — the C-ABI of include/pom_batch.h (libpom_batch.so): every entry point the reference-side binding links
  * (INTEGRATION.md).  gfx950 only; there is no CPU path: without a HIP device pom_batch_create fails with POM_E_HIP.
  *
- * This file is the table of contents: one translation unit, its parts by concern.  The order is the order kernels are emitted in,
- * which reaches their register allocation (pom_issue.h step_kernel): pom_kernels.h and pom_chain.h first (through pom_handle.h),
- * then pom_set_word_kernel (pom_issue.h), the copy kernels, pom_bench_policy_kernel, and the search kernels last, each in front of
- * its entry point, pom_step_mixed_kernel behind them, then pom_reach_kernel, pom_view_memory_kernel, pom_imagine_kernel, and pom_deal_kernel the very last.  The entry points between them define no kernel.
+ * The library is several translation units: this one, the core, and one per kernel family — pom_search.hip, pom_mixed.hip,
+ * pom_memory.hip, pom_deal.hip — each holding its kernels with their entry points.  The units meet through pom_host.h (the handle and
+ * how a call starts, fails and refuses: defined here, hidden from the library's exports) and pom_device.h (what kernels are made of).
+ *
+ * This file is the core's table of contents, its parts by concern.  The rule that remains: THE ORDER INSIDE THIS UNIT IS PINNED.  The
+ * order is the order kernels are emitted in, and kernels of one unit that share a body reach each other's register allocation through
+ * it (pom_issue.h step_kernel): pom_kernels.h and pom_chain.h first (through pom_handle.h), then pom_set_word_kernel (pom_issue.h), the
+ * copy kernels, pom_bench_policy_kernel.  The headline kernels live here, so nothing is added to, taken from or moved inside this unit
+ * without comparing every kernel's instructions before and after (scripts/compare_kernel_isa.py).  A new kernel family does not come
+ * here: it gets a unit of its own (pom_host.h, pom_device.h, its kernel header, its entry points; __graft_entry__.HIP_UNITS), where
+ * it cannot disturb the code of another unit and no other can disturb its own.
  */
 #include "pom_handle.h"       /* the handle, its streams, how a call on it begins (begin_call) and how any call refuses (refuse) */
 #include "pom_issue.h"        /* a step as launches: the kernel table, runs and who issues them, parts, graphs, several-tick calls */
@@ -17,9 +24,3 @@
 #include "pom_api_step.h"     /* entry points: ticks from explicit moves, synthetic streams, SimpleAgent; the closed-loop range call */
 #include "pom_api_diag.h"     /* entry points: chain statistics and litmus, the diagnostic builds' readers, profiling, pom_bench_policy */
 #include "pom_api_one.h"      /* entry points: pom_step / pom_env_step on one State in host memory */
-#include "pom_api_search.h"   /* entry points: forecast, rollouts, expand, move safety — with their kernel headers */
-#include "pom_api_mixed.h"    /* entry point: pom_batch_step_mixed, the range call with SimpleAgent opponents — with its kernel header */
-#include "pom_reach.h"        /* pom_batch_reach's kernel and its launch (the entry point is pom_api_search.h's) */
-#include "pom_api_memory.h"   /* entry point: pom_batch_remember_view, the views merged into the agents' memory — with its kernel header */
-#include "pom_api_imagine.h"  /* entry point: pom_batch_imagine, games built from an agent's view memory — with its kernel header */
-#include "pom_api_deal.h"     /* entry point: pom_batch_deal, Pommerman's standard start boards dealt on the device — with its kernel header, LAST */

@@ -6,6 +6,8 @@
 #ifndef POM_BOUNDARY_H_
 #define POM_BOUNDARY_H_
 
+#include "pom_device.h"
+
 __global__ void pom_pack_kernel(const int32_t* __restrict__ aos, int64_t first, int64_t count, uint32_t* state, uint32_t* snap,
                                 int64_t np, int* first_bad)
 {

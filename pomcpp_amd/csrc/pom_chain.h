@@ -43,31 +43,8 @@
 #ifndef POM_CHAIN_H_
 #define POM_CHAIN_H_
 
-#include <vector>
-
-/* one chained call (or several that continue the same play back to back): everything needed to play any of its ticks again */
-struct PomChainCall {
-    uint32_t visit0 = 0, launches = 0; /* the tiles' visits visit0 .. visit0 + launches - 1 */
-    StepParams p;                      /* as launched: p.tick0 is the tick of visit p.chain_seq0 */
-    bool policy = false;
-};
-
-struct PomChain {
-    bool tried = false, ok = false;
-    unsigned long long* tile_seq = nullptr; /* device, one word per tile (pom_kernels.h: StepParams.tile_seq) */
-    uint32_t* aux = nullptr;                /* device: [0] the kernels' POM_CHAIN_E_* flags, [1] number of poisoned tiles, then (tile, stored) pairs */
-    uint32_t* aux_host = nullptr;           /* pinned: where chain_settle reads aux[0..1] */
-    int64_t tiles = 0;
-    uint32_t visits = 0;                    /* visits every tile has had since its word was last zeroed */
-    uint32_t turn = 0;                      /* which stream the next launch goes to */
-    bool unverified = false;                /* chained launches since the tiles' words were last checked (chain_settle) */
-    uint64_t wait_limit = 0;                /* StepParams.chain_wait_limit */
-    int64_t wave_slots = 0;                 /* wavefronts of the step kernel the device holds at once: 16 per CU (launch_many_chain's rotation) */
-    StepParams last_key;                    /* what the chained launches possibly still in flight were launched with (tick0 = the */
-    void (*last_kernel)(StepParams) = nullptr; /* offset between ticks and visits), and which instantiation */
-    std::vector<PomChainCall> log;          /* the chained calls since the last settle */
-    int64_t stat_launches = 0, stat_settles = 0, stat_tiles_recovered = 0, stat_ticks_replayed = 0; /* pom_batch_chain_stats */
-};
+#include "pom_host.h"    /* PomChain, PomChainCall */
+#include "pom_kernels.h" /* pom_chain_probe_kernel */
 
 static void chain_destroy(PomChain* c)
 {

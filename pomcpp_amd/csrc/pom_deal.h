@@ -27,8 +27,6 @@
  *   5  START: fresh agent memory, the whole tile out (store_tile16_x4) — every column that is not dealt leaves as it came.  NEXT stores
  *      no tile.
  * LDS: 5,120 B (the tile).  No scratch memory: nothing is indexed by a value that is not a compile-time constant after unrolling.
- *
- * Included by pom_batch.hip after every other kernel header (through pom_api_deal.h), so that every kernel before it is emitted as it was.
  */
 #ifndef POM_DEAL_H_
 #define POM_DEAL_H_
@@ -263,7 +261,7 @@ POM_HD uint32_t pom_deal_word(int attempts, int bad, int fallback)
 
 #if defined(__HIPCC__) /* ---- the kernel ---- */
 
-#include "pom_kernels.h"
+#include "pom_device.h"
 #include "pom_policy_wave.h"
 
 /* what the rule asks of a Q beyond pom_policy_body.h's list, for PomQuadLanes */

@@ -1,12 +1,11 @@
 /*
- * pom_api_deal.h — the entry point pom_batch_deal (pom_batch.h PomDealSpec): Pommerman's standard start boards dealt on the device, into
- * the envs' records and restart snapshots or into the snapshots alone.  Its kernel header is included right in front of it, after every
- * other kernel of the library: the order kernels are emitted in stays.
+ * pom_deal.hip — the deal unit of libpom_batch.so: pom_batch_deal (pom_batch.h PomDealSpec), Pommerman's standard start boards dealt on
+ * the device, into the envs' records and restart snapshots or into the snapshots alone, and its kernel.  What it shares with the other
+ * units: pom_host.h, pom_device.h.
  */
-#ifndef POM_API_DEAL_H_
-#define POM_API_DEAL_H_
+#include <cstddef>
 
-#include "pom_api_imagine.h"
+#include "pom_host.h"
 #include "pom_deal.h"
 
 static_assert(sizeof(PomDealSpec) == POM_DEAL_SPEC_SIZE && sizeof(PomBoardLayout) == 20, "pom_batch.h states the size");
@@ -56,5 +55,3 @@ extern "C" int pom_batch_deal(PomBatch* h, const PomDealSpec* s)
                            dim3(64), args, 0, s->stream ? (hipStream_t)s->stream : h->stream));
     return POM_OK;
 }
-
-#endif /* POM_API_DEAL_H_ */

@@ -29,8 +29,6 @@
  *
  * LDS: LDS_ROWS rows (7,424 B); OBS: the staging area of the fused export lies over the tick's scratch rows (the tick is over when
  * the observation begins), max(LDS_ROWS, POM_REC_DWORDS + the staging rows).
- *
- * Included after pom_rollout_policy.h, so that every kernel before it is emitted as it was.
  */
 #ifndef POM_EXPAND_H_
 #define POM_EXPAND_H_

@@ -6,8 +6,6 @@
  * it: after every tick it notes, per cell, the first tick that leaves the cell in flames, per agent the tick it died in, and the
  * tick's POM_UB_* flags.  Nothing of the batch is written — no record, no counter, no ticket word, no restart.
  *
- * Included after pom_kernels.h and after every other kernel of pom_batch.hip, so that the kernels before it are emitted as they were.
- *
  * LDS: the tick's LDS_ROWS rows (record, bomb destinations, frames / claim maps), and BEHIND them FC_STAGE_ROWS rows of staging —
  * a byte per cell and env in the board's own [cell][env] layout (byte c * 16 + el, pom_packed.h), 0 = not seen in flames yet.  The
  * staging lies behind LDS_ROWS and not over the tick's scratch rows as the policy's maps and the observation's staging area do in
@@ -17,7 +15,7 @@
 #ifndef POM_FORECAST_H_
 #define POM_FORECAST_H_
 
-#include "pom_kernels.h"
+#include "pom_device.h"
 
 struct ForecastParams {
     const uint32_t* state;

@@ -1,7 +1,8 @@
 /*
- * pom_handle.h — the batch handle and how a call on it starts: the error text and the one way to refuse (refuse), the handle
- * (PomBatch), its streams forked and joined, the start of every call on a handle (begin_call), and the parameters a step launch
- * takes from the handle (fill_params).  Who launches what: pom_issue.h.
+ * pom_handle.h — the batch handle at work, core unit only: the error text and the definitions of what pom_host.h declares for every
+ * unit (set_err, refuse, check_range, check_call, begin_call, ensure_agent_mem), the handle's streams forked and joined, and the
+ * parameters a step launch takes from the handle (fill_params).  The handle itself (PomBatch): pom_host.h.  Who launches what:
+ * pom_issue.h.
  */
 #ifndef POM_HANDLE_H_
 #define POM_HANDLE_H_
@@ -16,28 +17,17 @@
 #include <mutex>
 #include <new>
 #include <thread>
-#include <type_traits>
 
+#include "pom_host.h"
 #include "pom_kernels.h"
 #include "pom_chain.h"
 
-static thread_local char g_err[256] = "";
-static void set_err(const char* what, hipError_t e)
+static thread_local char g_err[256] = ""; /* the one error text of the library: every unit writes it through set_err and refuse */
+void set_err(const char* what, hipError_t e)
 {
     snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e));
 }
-#define HIPCHK(call)                      \
-    do {                                  \
-        hipError_t e_ = (call);           \
-        if (e_ != hipSuccess) {           \
-            set_err(#call, e_);           \
-            return POM_E_HIP;             \
-        }                                 \
-    } while (0)
-
-/* The one way to refuse a call: pom_last_error() reads "<call>: <what>", the call returns POM_E_ARG.  Every POM_E_ARG of every entry
- * point comes from here, so the text always names the call that refused. */
-__attribute__((format(printf, 2, 3))) static int refuse(const char* who, const char* fmt, ...)
+int refuse(const char* who, const char* fmt, ...)
 {
     const int at = snprintf(g_err, sizeof g_err, "%s: ", who);
     va_list ap;
@@ -46,87 +36,6 @@ __attribute__((format(printf, 2, 3))) static int refuse(const char* who, const c
     va_end(ap);
     return POM_E_ARG;
 }
-
-/* The head of every spec's check (pom_batch.h Pom*Spec): what is wrong with it, or nullptr.  SPEC_HEAD names the type for the text. */
-template <class S>
-static const char* spec_head(const S* s, const char* size_text)
-{
-    if (!s) return "the spec is NULL";
-    if (s->struct_size != (int32_t)sizeof(S)) return size_text;
-    if constexpr (std::is_array<decltype(S::reserved_)>::value) {
-        for (const auto r : s->reserved_)
-            if (r != 0) return "reserved_ must be 0";
-    } else if (s->reserved_ != 0) return "reserved_ must be 0";
-    return nullptr;
-}
-#define SPEC_HEAD(S, s) spec_head<S>(s, "struct_size is not sizeof(" #S ")")
-
-struct PomBatch {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    int64_t n = 0, n_pad = 0, n_waves = 0, env_offset = 0; /* n_waves: counter slots, sized for the smallest EPW */
-    int epw = 64;
-    bool quad = false; /* EPW 16 with four lanes per env (pom_step_kernel's G = 4) */
-    int mode = POM_MODE_ENV, auto_reset = 0, max_steps = 0;
-    uint32_t* state = nullptr;
-    uint32_t* snap = nullptr;       /* restart snapshot, array of structs */
-    uint32_t* terminal = nullptr;   /* POM_RESET_AT_END: final record of each env's last finished episode, array of structs */
-    int32_t* moves_dev = nullptr;   /* n_pad x 4 */
-    uint32_t* agent_mem = nullptr;  /* SimpleAgent memory, [2][4 * n_pad], allocated on first use */
-    uint32_t* episode = nullptr;    /* games started per env (fresh boards) */
-    uint64_t board_seed = 0;
-    int fresh = 0;
-    int32_t* staging = nullptr;     /* staging_envs x 251 dwords (AoS), also status scratch */
-    uint32_t* copy_scratch = nullptr; /* pom_batch_copy_envs: K1's image of state, agent memory, episode (and terminal), allocated on
-                                         first use (pom_copy.h) */
-    int64_t* copy_idx = nullptr;      /* ... and the host variant's indices on the device, n_pad int64 */
-    int64_t staging_envs = 0;
-    int64_t* wave_counters = nullptr;
-    int64_t* totals_dev = nullptr;
-    int* first_bad = nullptr;
-    uint64_t tick = 0;
-    /* A step is issued as `parts` kernels over contiguous tile ranges on internal streams: the launches are
-     * independent (envs never interact), so one part's HBM load / store phases overlap the others' compute
-     * instead of all wavefronts of the chip loading and storing in lock-step.  The caller's stream is forked
-     * into the sub-streams lazily and joined again before anything else touches the batch. */
-    enum { MAX_PARTS = 8, PROF_RING = 256 };
-    int parts = 1;
-    hipStream_t sub[MAX_PARTS] = {};
-    hipEvent_t ev_fork = nullptr, ev_join[MAX_PARTS] = {};
-    bool forked = false;
-    int forked_n = 0; /* how many streams (indices below it) the fork covers */
-    int main_part = 1; /* part 0 of a split step runs on the caller's stream itself, parts 1.. on sub-streams: one stream
-                          fewer for the same overlap (3 parts: 21.2 -> 20.6 us per step at 65,536 envs); POM_MAIN_PART=0: all
-                          parts on sub-streams */
-    /* how the launches of a several-tick call are issued (launch_many; PomBatchOptions.issue_mode) */
-    int issue_mode = POM_ISSUE_THREADS;
-    struct PomIssuer* issuers[MAX_PARTS] = {}; /* POM_ISSUE_THREADS: one helper thread per sub-stream part, created on first use */
-    bool issuers_failed = false;               /* a helper thread could not be started: the calling thread issues the rest */
-    int last_kind = 0;                         /* what has been launched on the streams since they were forked: POM_KIND_SPLIT / _CHAIN */
-    /* POM_ISSUE_GRAPH: multi-tick calls replay a captured chunk of launches (launch_many): POM_GRAPH_TICKS launches of every part as one HIP
-     * graph per part.  tick_words[k] is the tick part k's replay starts at, read by the graph's kernels (StepParams.tick_base;
-     * set by a one-lane kernel on the part's stream in front of each replay); tick_words[MAX_PARTS] stays 0 and is what every
-     * launch outside a graph points at. */
-    enum { MAX_GRAPHS = 4 };
-    struct PomStepGraph* graphs[MAX_GRAPHS] = {};
-    uint64_t graph_clock = 0;
-    uint32_t* tick_words = nullptr;
-    PomChain chain;          /* POM_ISSUE_CHAIN: the tiles' ticket words, set up on first use (pom_chain.h) */
-    int chain_parts = 3;     /* ... and how many streams the chained launches may rotate over */
-    bool chain_auto = true;  /* ... of which a call uses two if it is short and three if it is long (launch_many_chain) — unless the caller
-                                asked for a number of streams */
-    int chain_last_use = 2;  /* what the last chained call used (pom_batch_issue_info) */
-    bool fuse_policy = true; /* pom_batch_step_simple: policy and tick in one kernel (quad shape); POM_FUSE=0 keeps them apart */
-    /* optional per-launch timing (pom_batch_profile) */
-    bool profiling = false;
-    hipEvent_t prof_ev[2 * PROF_RING] = {};
-    int prof_n = 0;
-#if defined(POM_DIAG)
-    long long* diag = nullptr;
-    long long* diag_pol = nullptr;
-#endif
-};
 
 static void drop_graphs(PomBatch* h);
 static void stop_issuers(PomBatch* h);
@@ -143,24 +52,20 @@ static int quiesce(PomBatch* h)
     return join_parts(h);
 }
 
-static int check_range(const PomBatch* h, const char* who, int64_t first, int64_t count)
+int check_range(const PomBatch* h, const char* who, int64_t first, int64_t count)
 {
     if (!h || first < 0 || count < 0 || first + count > h->n)
         return refuse(who, "range [%lld, %lld) outside batch", (long long)first, (long long)(first + count));
     return POM_OK;
 }
 
-/* The start of every call on a handle.  Refuses a NULL handle, then `what` (what the caller found wrong with the other arguments, or
- * nullptr), both by the call's name and before any runtime call; selects the handle's device; and brings the handle to the state
- * the call needs: as it is (a call that only launches: launch_step settles for itself), the sub-streams joined into the caller's
- * stream, or settled (quiesce). */
-enum PomNeeds { POM_AS_IS, POM_JOINED, POM_SETTLED };
-static int check_call(const PomBatch* h, const char* who, const char* what = nullptr) /* (all of it for a call that only reads the handle) */
+/* the start of every call on a handle (pom_host.h) */
+int check_call(const PomBatch* h, const char* who, const char* what)
 {
     if (!h) return refuse(who, "the handle is NULL");
     return what ? refuse(who, "%s", what) : POM_OK;
 }
-static int begin_call(PomBatch* h, const char* who, PomNeeds needs, const char* what = nullptr)
+int begin_call(PomBatch* h, const char* who, PomNeeds needs, const char* what)
 {
     if (int rc = check_call(h, who, what)) return rc;
     HIPCHK(hipSetDevice(h->device));
@@ -241,7 +146,7 @@ static int join_parts(PomBatch* h)
     return POM_OK;
 }
 
-static int ensure_agent_mem(PomBatch* h)
+int ensure_agent_mem(PomBatch* h)
 {
     if (!h->agent_mem) {
         if (int jr = join_parts(h)) return jr; /* the next launch forks the sub-streams again, after this memset */
@@ -251,16 +156,6 @@ static int ensure_agent_mem(PomBatch* h)
     return POM_OK;
 }
 
-struct PomObserveOut { /* pom_batch_step_device_observe / _range: where the fused kernel writes the observation */
-    void* planes;
-    int32_t* agent_attrs;
-    int32_t* env_attrs;
-    int32_t dtype, per_agent;
-    /* the fogged views (pom_batch_step_device_observe_view / _range_view): view = 1 picks the VIEW kernels (launch_parts, launch_range),
-     * which write viewer_attrs and ignore agent_attrs / per_agent; the other kernels ignore these */
-    int32_t view, view_radius;
-    int32_t* viewer_attrs;
-};
 static int fill_params(PomBatch* h, StepParams& p, const int32_t* moves_dev, uint64_t seed, int dist, int ticks,
                        const PomObserveOut* obs = nullptr)
 {

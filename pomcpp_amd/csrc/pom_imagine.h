@@ -26,8 +26,6 @@
  *   6  the built records as dense snapshot records, and fresh agent memory, by the quad;
  *   7  the whole tile out (store_tile16_x4) — every column that is no built destination leaves as it came — and the result words.
  * LDS: 5,120 B (tile) + 11,712 B (16 views).  No scratch memory.
- *
- * Included by pom_batch.hip after every other kernel header (through pom_api_imagine.h), so that every kernel before it is emitted as it was.
  */
 #ifndef POM_IMAGINE_H_
 #define POM_IMAGINE_H_
@@ -247,7 +245,7 @@ POM_HD uint32_t pom_imagine_finish(const uint8_t* view, uint32_t* tile, int ec, 
 
 #if defined(__HIPCC__) /* ---- the kernel ---- */
 
-#include "pom_kernels.h"
+#include "pom_device.h"
 
 struct ImagineParams {
     uint32_t* state;

@@ -17,8 +17,6 @@
  * (max_ticks_per_launch).  The one-lane-per-env shapes: fresh boards or not.  Combinations without a kernel of their own are kept
  * away by max_ticks_per_launch, runs_chain and pom_batch_create. */
 typedef void (*PomStepKernel)(StepParams);
-static bool runs_fresh(const PomBatch* h) { return h->fresh && h->mode == POM_MODE_ENV && h->auto_reset; }
-static bool runs_at_end(const PomBatch* h) { return h->auto_reset == POM_RESET_AT_END && h->mode == POM_MODE_ENV; }
 static int max_ticks_per_launch(const PomBatch* h, bool policy)
 {
     return (!h->quad || (!policy && !runs_fresh(h) && !runs_at_end(h))) ? INT_MAX : 1;
@@ -33,7 +31,7 @@ static PomStepKernel step_kernel(const PomBatch* h, bool policy, int ticks_per_l
         PomStepKernel one_lane[3][2]; /* [64 / 32 / 16 envs per wavefront][fresh ? 0 : 1] */
         PomStepKernel observe[4];     /* [fresh * 2 + at_end] (explicit moves: no policy) */
         PomStepKernel chained[8];     /* as one_tick */
-        PomStepKernel view[4];        /* as observe: the fogged views (listed last: the kernels before it are emitted as they always were) */
+        PomStepKernel view[4];        /* as observe: the fogged views */
     } k = {
         {pom_step_kernel<16, 4, false, false, false, true>, pom_step_kernel<16, 4, false, false, true, true>,
          pom_step_kernel<16, 4, false, true, false, true>, pom_step_kernel<16, 4, false, true, true, true>,

@@ -1,13 +1,8 @@
 /*
- * pom_api_mixed.h — the entry point pom_batch_step_mixed (pom_batch.h PomMixedStepSpec): the closed-loop range call with SimpleAgent
- * for the agents of simple_mask.  Its kernel header is included right in front of it, after every other kernel of the library: the
- * order kernels are emitted in stays.
+ * pom_mixed.hip — the mixed-step unit of libpom_batch.so: pom_batch_step_mixed (pom_batch.h PomMixedStepSpec), the closed-loop range
+ * call with SimpleAgent for the agents of simple_mask, and its kernel.  What it shares with the other units: pom_host.h, pom_device.h.
  */
-#ifndef POM_API_MIXED_H_
-#define POM_API_MIXED_H_
-
-#include "pom_api_search.h"
-#include "pom_api_step.h"
+#include "pom_host.h"
 #include "pom_step_mixed.h"
 
 static_assert(sizeof(PomMixedStepSpec) == POM_MIXED_STEP_SPEC_SIZE, "pom_batch.h states the size");
@@ -93,5 +88,3 @@ extern "C" int pom_batch_step_mixed(PomBatch* h, const PomMixedStepSpec* s)
                            s->stream ? (hipStream_t)s->stream : h->stream));
     return POM_OK;
 }
-
-#endif /* POM_API_MIXED_H_ */

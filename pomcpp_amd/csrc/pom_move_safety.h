@@ -12,8 +12,6 @@
  * Nothing of the batch is written: no record, no counter, no ticket word, no restart.  The owner lane of every env stores one byte
  * per output.
  *
- * Included after pom_expand.h, the last kernel header of pom_batch.hip before it, so that every kernel before it is emitted as it was.
- *
  * LDS: the tick's LDS_ROWS rows and nothing more (no staging rows: both answers are registers).
  *
  * Grid: pom_rollout.h's — one dimension, workgroup b = v * tiles8 + slot with tiles8 the tile count rounded up to a multiple of 8, so
@@ -54,7 +52,7 @@ POM_HD typename Q::W pom_escape_grow(const Q& q, typename Q::W reach, typename Q
 
 #if defined(__HIPCC__) /* ---- the kernel ---- */
 
-#include "pom_kernels.h"
+#include "pom_device.h"
 #include "pom_policy_wave.h"
 
 struct MoveSafetyParams {

@@ -21,8 +21,6 @@
  * (pom_reach_flood; what differs between the device and the host is only "does any flood of the wavefront still grow"), so that the
  * same source is checked on the host against the compiled reference's maps (tests/emul/pom_reach_emul.cpp, tests/test_reach_host.py).
  *
- * Included by pom_batch.hip after every other kernel header, so that every kernel before it is emitted as it was.
- *
  * Work split: the grid of pom_move_safety.h — one wavefront per (tile of 16 envs, asked agent), workgroup b = v * tiles8 + slot, all
  * variants of a tile on one XCD.  Quad q of the wavefront runs the flood of (env q of the tile, the variant's agent).
  * LDS: the tile's first 40 rows (board, timeStep, agents: 2,560 B), and two staging areas of 16 rows x 128 bytes for the outputs, from
@@ -184,7 +182,7 @@ POM_HD uint32_t pom_reach_cells4(const uint32_t (&plane)[N], int j)
 
 #if defined(__HIPCC__) /* ---- the kernel ---- */
 
-#include "pom_kernels.h"
+#include "pom_device.h"
 #include "pom_policy_wave.h"
 
 struct ReachParams {
@@ -272,25 +270,6 @@ __global__ __launch_bounds__(64) void pom_reach_kernel(ReachParams p)
     obs_lds_order(); /* the lanes' staging writes are in LDS: no read below may be scheduled earlier */
     if (DIST) pom_reach_store(p.dist, stage, tile_id * 16, p.n, agent, lane);
     if (MOVE) pom_reach_store(p.move, stage + (DIST ? POM_REACH_STAGE_DWORDS : 0), tile_id * 16, p.n, agent, lane);
-}
-
-/* the launch, for pom_batch_reach (pom_api_search.h, which is compiled before this header and knows the kernel by this function only) */
-static void pom_reach_launch(const uint32_t* state, int64_t n, int32_t agent_mask, int32_t max_dist, uint8_t* dist, uint8_t* move,
-                             uint32_t tiles, uint32_t tiles8, hipStream_t stream)
-{
-    ReachParams p;
-    p.state = state;
-    p.dist = dist;
-    p.move = move;
-    p.n = n;
-    p.agent_mask = agent_mask;
-    p.max_dist = max_dist;
-    p.tiles = tiles;
-    p.tiles8 = tiles8;
-    const dim3 grid(tiles8 * (unsigned)__builtin_popcount((unsigned)agent_mask & 15u));
-    if (move && dist) pom_reach_kernel<true, true><<<grid, dim3(64), 0, stream>>>(p);
-    else if (move) pom_reach_kernel<true, false><<<grid, dim3(64), 0, stream>>>(p);
-    else pom_reach_kernel<false, true><<<grid, dim3(64), 0, stream>>>(p);
 }
 
 #endif /* __HIPCC__ */

@@ -9,8 +9,6 @@
  * (environment.cpp:125-128), and the wavefront leaves the loop when a ballot shows all of its envs done.  Nothing of the batch is
  * written: no record, no counter, no ticket word, no restart.  The owner lane of every env writes one result word.
  *
- * Included after pom_forecast.h, so that every kernel before it is emitted as it was.
- *
  * LDS: the tick's LDS_ROWS rows and nothing more (no staging rows: the result is a register).
  *
  * Grid: one dimension, workgroup b = r * tiles8 + slot with tiles8 the tile count rounded up to a multiple of 8, so that
@@ -20,7 +18,7 @@
 #ifndef POM_ROLLOUT_H_
 #define POM_ROLLOUT_H_
 
-#include "pom_kernels.h"
+#include "pom_device.h"
 
 struct RolloutParams {
     const uint32_t* state;

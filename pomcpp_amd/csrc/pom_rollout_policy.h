@@ -15,8 +15,6 @@
  *
  * POLICY = false (simple_mask == 0): an instantiation without any of the policy — pom_rollout_kernel with a per-agent first tick.
  *
- * Included after pom_rollout.h, so that every kernel before it is emitted as it was.
- *
  * LDS: max(LDS_ROWS, POM_REC_DWORDS + 44) rows: the danger map (32 rows of bytes) and the cell sets (12 rows) lie where the tick keeps
  * its bomb destinations and explosion frames — the policy of a tick is over before its tick begins.  Behind them 12 rows, three
  * dwords per lane: the agent's memory and its move of tick 1 wait there through the tick (in registers they cost 12 spilled VGPRs

@@ -1,18 +1,17 @@
 /*
- * pom_api_search.h — the search entry points: calls that play ahead on scratch copies and leave the batch as it is (forecast, the
- * three rollouts, move safety), and the expansion that copies listed games into slots and plays them one tick.  Each kernel header
- * is included right in front of its entry point, after every other kernel of the library: the order kernels are emitted in stays.
- * (pom_batch_reach's kernel came after pom_api_mixed.h's: pom_batch.hip includes pom_reach.h behind that, and the entry point here
- * reaches it through a launch function.)
+ * pom_search.hip — the search unit of libpom_batch.so: the kernels and entry points of the calls that play ahead on scratch copies and
+ * leave the batch as it is (forecast, the three rollouts, move safety, reach), and of the expansion that copies listed games into
+ * slots and plays them one tick.  What it shares with the other units: pom_host.h (host side), pom_device.h (device side).
  */
-#ifndef POM_API_SEARCH_H_
-#define POM_API_SEARCH_H_
-
-#include "pom_api_observe.h"
-
-/* ---- the forecast (pom_batch.h PomForecastSpec): K ticks ahead on a scratch copy of every tile.  Its kernel comes after every
- * other kernel of this file, so that those are emitted as they were without it ---- */
+#include "pom_host.h"
 #include "pom_forecast.h"
+#include "pom_rollout.h"
+#include "pom_rollout_policy.h"
+#include "pom_expand.h"
+#include "pom_move_safety.h"
+#include "pom_reach.h"
+
+/* ---- the forecast (pom_batch.h PomForecastSpec): K ticks ahead on a scratch copy of every tile ---- */
 
 static_assert(sizeof(PomForecastSpec) == POM_FORECAST_SPEC_SIZE, "pom_batch.h states the size");
 
@@ -40,12 +39,9 @@ extern "C" int pom_batch_forecast(PomBatch* h, const PomForecastSpec* s)
     return POM_OK;
 }
 
-/* ---- the rollout (pom_batch.h PomRolloutSpec): R random playouts of every env on scratch copies of its tile.  Its kernel comes
- * after the forecast's, so that every kernel before it is emitted as it was without it ---- */
-#include "pom_rollout.h"
-/* ---- the policy rollout (pom_batch.h PomRolloutPolicySpec): the rollout with SimpleAgent for the agents of simple_mask and a
- * per-agent first tick.  Its kernel comes after the rollout's, so that every kernel before it is emitted as it was without it ---- */
-#include "pom_rollout_policy.h"
+/* ---- the rollout (pom_batch.h PomRolloutSpec): R random playouts of every env on scratch copies of its tile; the policy rollout
+ * (PomRolloutPolicySpec): the same with SimpleAgent for the agents of simple_mask and a per-agent first tick; and the policy rollout
+ * for a list of jobs (PomRolloutJobsSpec) ---- */
 
 static_assert(sizeof(PomRolloutSpec) == POM_ROLLOUT_SPEC_SIZE, "pom_batch.h states the size");
 static_assert(sizeof(PomRolloutPolicySpec) == POM_ROLLOUT_POLICY_SPEC_SIZE, "pom_batch.h states the size");
@@ -176,9 +172,7 @@ extern "C" int pom_batch_rollout_jobs(PomBatch* h, const PomRolloutJobsSpec* s)
     return POM_OK;
 }
 
-/* ---- the expansion (pom_batch.h PomExpandSpec): listed games copied into slots and ticked once, one launch.  Its kernel comes after
- * the rollouts', so that every kernel before it is emitted as it was without it ---- */
-#include "pom_expand.h"
+/* ---- the expansion (pom_batch.h PomExpandSpec): listed games copied into slots and ticked once, one launch ---- */
 
 static_assert(sizeof(PomExpandSpec) == POM_EXPAND_SPEC_SIZE, "pom_batch.h states the size");
 
@@ -230,8 +224,7 @@ extern "C" int pom_batch_expand(PomBatch* h, const PomExpandSpec* s)
 }
 
 /* ---- the move safety (pom_batch.h PomMoveSafetySpec): every asked agent's six candidate moves played K ticks ahead on scratch copies
- * of its tile, one launch.  Its kernel comes after the expansion's, so that every kernel before it is emitted as it was without it ---- */
-#include "pom_move_safety.h"
+ * of its tile, one launch ---- */
 
 static_assert(sizeof(PomMoveSafetySpec) == POM_MOVE_SAFETY_SPEC_SIZE, "pom_batch.h states the size");
 
@@ -268,12 +261,7 @@ extern "C" int pom_batch_move_safety(PomBatch* h, const PomMoveSafetySpec* s)
     return POM_OK;
 }
 
-/* ---- the reach (pom_batch.h PomReachSpec): every asked agent's FillRMap distances and first moves, one launch.  Its kernel header,
- * pom_reach.h, is the last thing pom_batch.hip includes — behind pom_step_mixed.h, so that every kernel before it is emitted as it
- * was —: here the kernel is known by its launch function only ---- */
-static void pom_reach_launch(const uint32_t* state, int64_t n, int32_t agent_mask, int32_t max_dist, uint8_t* dist, uint8_t* move,
-                             uint32_t tiles, uint32_t tiles8, hipStream_t stream);
-
+/* ---- the reach (pom_batch.h PomReachSpec): every asked agent's FillRMap distances and first moves, one launch ---- */
 static_assert(sizeof(PomReachSpec) == POM_REACH_SPEC_SIZE, "pom_batch.h states the size");
 
 extern "C" int pom_batch_reach(PomBatch* h, const PomReachSpec* s)
@@ -292,9 +280,19 @@ extern "C" int pom_batch_reach(PomBatch* h, const PomReachSpec* s)
     /* settled, not only joined (as pom_batch_forecast): after chained launches a tile left behind is caught up first — the maps are
      * those of the state a download returns */
     if (int rc = begin_call(h, who, POM_SETTLED, what)) return rc;
-    pom_reach_launch(h->state, h->n, s->agent_mask, s->max_dist, s->dist_dev, s->move_dev, (uint32_t)tiles, (uint32_t)tiles8, h->stream);
+    ReachParams p;
+    p.state = h->state;
+    p.dist = s->dist_dev;
+    p.move = s->move_dev;
+    p.n = h->n;
+    p.agent_mask = s->agent_mask;
+    p.max_dist = s->max_dist;
+    p.tiles = (uint32_t)tiles;
+    p.tiles8 = (uint32_t)tiles8;
+    const dim3 grid(p.tiles8 * (unsigned)__builtin_popcount((unsigned)s->agent_mask & 15u));
+    if (p.move && p.dist) pom_reach_kernel<true, true><<<grid, dim3(64), 0, h->stream>>>(p);
+    else if (p.move) pom_reach_kernel<true, false><<<grid, dim3(64), 0, h->stream>>>(p);
+    else pom_reach_kernel<false, true><<<grid, dim3(64), 0, h->stream>>>(p);
     HIPCHK(hipGetLastError());
     return POM_OK;
 }
-
-#endif /* POM_API_SEARCH_H_ */

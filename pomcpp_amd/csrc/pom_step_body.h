@@ -52,6 +52,10 @@
 #ifndef POM_STEP_BODY_H_
 #define POM_STEP_BODY_H_
 
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h> /* the device side's intrinsics (__mul24, ...); the host build (tests/emul) takes the plain forms */
+#endif
+
 #include "pom_packed.h"
 
 #if defined(__clang__)

@@ -22,13 +22,11 @@
  * LDS: the policy's 44 overlay rows (danger map 32, cell sets 12) and the export's staging rows (38) lie over the SAME rows behind the
  * record, which are also the tick's scratch rows: the policy is over before the tick begins and the tick is over before the export
  * begins, so the largest of the three sizes the tile — max(LDS_ROWS, POM_REC_DWORDS + 44) rows, what the fused policy kernel has.
- *
- * Included last of all kernels (pom_batch.hip), so that every kernel before it is emitted as it was.
  */
 #ifndef POM_STEP_MIXED_H_
 #define POM_STEP_MIXED_H_
 
-#include "pom_move_safety.h"
+#include "pom_device.h"
 
 struct MixedStepParams {
     uint32_t* state;

@@ -9,9 +9,6 @@
  * (pom_view_memory_head, pom_view_memory_gone) are POM_HD, so that the same source is checked on the host against the numpy checker
  * (tests/emul/pom_view_memory_emul.cpp, tests/test_view_memory_host.py).
  *
- * Included by pom_batch.hip after every other kernel header (through pom_api_memory.h), so that every kernel before it is emitted as
- * it was.
- *
  * Work split: FOUR wavefronts per tile of 16 envs, one per pass of four envs that the export stages at a time (POM_MEM_SPLIT; with one
  * wavefront per tile, the export's split, 65,536 envs are one round of 4,096 wavefronts that each walk 16 envs one after the other:
  * 148 us against 123, profiles/view_memory_bench.txt).  The grid is the rollouts': the tiles rounded up to a multiple of 8, a tile's four
@@ -100,7 +97,7 @@ POM_HD void pom_view_memory_cell(int (&m)[POM_MEMORY_PLANES], const int (&now)[P
 
 #if defined(__HIPCC__) /* ---- the kernel ---- */
 
-#include "pom_kernels.h"
+#include "pom_device.h"
 
 struct ViewMemoryParams {
     const uint32_t* state;

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""scripts/kernel_asm_diff.py A.s B.s — two device assemblies of pom_batch.hip compared kernel by kernel: one line per kernel with its
+"""scripts/kernel_asm_diff.py A.s B.s — two device assemblies of one unit of the library compared kernel by kernel: one line per kernel with its
 lines in each and `identical` or `differs`.  It compares text and looks for no particular instruction.
 
-The inputs (about 2.5 minutes each):
-  hipcc -Os --offload-arch=gfx950 -std=c++17 -Iinclude -Ipomcpp_amd/csrc --cuda-device-only -S -o A.s pomcpp_amd/csrc/pom_batch.hip
+The inputs (the core unit takes about 2.5 minutes; the units: __graft_entry__.HIP_UNITS), compiled as the library is:
+  python -c "import subprocess, __graft_entry__ as ge; subprocess.run(ge.hip_compile_cmd('pom_batch', flags=['--cuda-device-only', '-S', '-o', 'A.s']), check=True)"
 A kernel is the text from its label to its .Lfunc_end; comments and the .loc / .file / .cfi lines are dropped.  Local labels and the
 numbered temporaries (.LBB12_3, .Ltmp40) carry the function's position in the file, which moves when an earlier function does: they
 are renumbered in the order the kernel's text names them."""

@@ -22,8 +22,8 @@ a = ap.parse_args()
 lib = os.environ.get("POM_TRUNC_LIB") or os.path.join(ROOT, "build", "libpom_batch_trunc.so")  # POM_TRUNC_LIB: a POM_TRUNC build made elsewhere (another commit's)
 if (a.build_only and "POM_TRUNC_LIB" not in os.environ) or not os.path.exists(lib):
     os.makedirs(os.path.dirname(lib), exist_ok=True)
-    subprocess.run(["hipcc", "-Os", "--offload-arch=gfx950", "-std=c++17", "-shared", "-fPIC", "-DPOM_TRUNC", "-I" + ROOT + "/include",
-                    "-I" + ROOT + "/pomcpp_amd/csrc", "-o", lib, ROOT + "/pomcpp_amd/csrc/pom_batch.hip"], check=True)
+    import __graft_entry__
+    __graft_entry__.build_hip(force=a.build_only, defines=["POM_TRUNC"], out=lib)  # every unit of the library with the define: the one way to build a variant
 if a.build_only:
     sys.exit(0)
 os.environ["POM_LIB"] = lib  # what pomcpp_amd loads (pomcpp_amd/_abi.py; assigning batch.library_path no longer reaches the loader)

@@ -18,8 +18,8 @@ ap.add_argument("--warm", type=int, default=100)
 a = ap.parse_args()
 lib = os.path.join(ROOT, "build", "libpom_batch_diag.so")
 os.makedirs(os.path.dirname(lib), exist_ok=True)
-subprocess.run(["hipcc", "-Os", "--offload-arch=gfx950", "-std=c++17", "-shared", "-fPIC", "-DPOM_DIAG", "-I" + ROOT + "/include",
-                "-I" + ROOT + "/pomcpp_amd/csrc", "-o", lib, ROOT + "/pomcpp_amd/csrc/pom_batch.hip"], check=True)
+import __graft_entry__
+__graft_entry__.build_hip(defines=["POM_DIAG"], out=lib)  # every unit of the library with the define: the one way to build a variant
 import pomcpp_amd.batch as B
 B.library_path = lambda: lib
 import pomcpp_amd as pa

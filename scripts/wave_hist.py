@@ -13,8 +13,8 @@ ap.add_argument("--lib", default="", help="a prebuilt POM_DIAG library (default:
 a = ap.parse_args()
 lib = a.lib or os.path.join(ROOT, "build", "libpom_batch_diag.so")
 if not a.lib:
-    subprocess.run(["hipcc", "-Os", "--offload-arch=gfx950", "-std=c++17", "-shared", "-fPIC", "-DPOM_DIAG", "-I" + ROOT + "/include",
-                    "-I" + ROOT + "/pomcpp_amd/csrc", "-o", lib, ROOT + "/pomcpp_amd/csrc/pom_batch.hip"], check=True)
+    import __graft_entry__
+    __graft_entry__.build_hip(defines=["POM_DIAG"], out=lib)  # every unit of the library with the define: the one way to build a variant
 os.environ["POM_LIB"] = lib  # what pomcpp_amd loads (pomcpp_amd/_abi.py)
 import pomcpp_amd.batch as B
 import pomcpp_amd as pa

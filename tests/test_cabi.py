@@ -24,6 +24,28 @@ def test_exports_match_header(hip_lib):
         assert hasattr(hip_lib, s), f"{s} declared in include/pom_batch.h but not exported"
 
 
+def test_exports_nothing_internal(hip_lib):
+    """The library is linked from several translation units that share host functions (pom_host.h): those are hidden.  Every defined
+    dynamic symbol is a call of include/pom_batch.h, a kernel (its handle, its launch stub, the compiler's per-unit id), or a weak
+    instantiation of the C++ library's templates and the implicit members of the two types they are instantiated over."""
+    from pomcpp_amd.batch import library_path
+    declared = set(_declared_symbols())
+    out = subprocess.run(["nm", "-D", "--defined-only", library_path()], capture_output=True, text=True, check=True).stdout
+    syms = [line.split()[1:] for line in out.splitlines()]
+    assert len(syms) > len(declared)
+    std = re.compile(r"_ZNK?(St|9__gnu_cxx)|_ZT[ISV]NSt")
+    internal = []
+    for kind, name in syms:
+        if kind == "T" and name in declared:
+            continue
+        if re.fullmatch(r"(_Z\d+)?(__device_stub__)?pom_[a-z_]+_kernel.*", name) or (kind == "B" and name.startswith("__hip_cuid_")):
+            continue
+        if kind in "WV" and (std.match(name) or name in ("_ZN8PomBatchC2Ev", "_ZN9PomIssuerD2Ev")):
+            continue
+        internal.append((kind, name))
+    assert not internal, internal
+
+
 def test_library_is_a_gfx950_code_object(hip_lib):
     from pomcpp_amd.batch import library_path
     out = subprocess.run(["/opt/rocm/lib/llvm/bin/clang-offload-bundler", "--list", "--type=o", f"--input={library_path()}"],
@@ -82,6 +104,16 @@ def test_every_refusing_call_names_itself(hip_lib):
         if rc != 1 or not text.startswith(s + ": "):
             wrong.append((s, rc, text))
     assert not wrong, f"{len(wrong)} of {len(syms)}:\n" + "\n".join(map(str, wrong))
+
+
+def test_one_error_text_across_the_library_s_units(hip_lib):
+    """pom_last_error reads ONE text, whichever translation unit wrote it: a call of the core unit fails, then a call of a kernel
+    family's unit, then one of the core again — each time the text is the last call's"""
+    lib = hip_lib
+    _fail_another_call(lib)                                                     # pom_batch.hip
+    for family in ("pom_batch_forecast", "pom_batch_step_mixed", "pom_batch_imagine", "pom_batch_deal"):   # one per family unit
+        assert getattr(lib, family)(None, None) == 1 and lib.pom_last_error().decode().startswith(family + ": ")
+        _fail_another_call(lib)
 
 
 def test_create_refuses_bad_options_by_name_before_it_needs_a_device(hip_lib):

@@ -218,7 +218,7 @@ def test_dealt_states_are_playable(oracle, emul, boards):
     assert ((s["board"] >> 8) == 2).sum() < ((start["board"] >> 8) == 2).sum() and (s["agents"]["bombStrength"] > 1).any() and (s["aliveAgents"] < 4).any()
 
 
-# ---- the library's refusals that need no device: pom_api_deal.h checks the spec before the handle ----------------------------------------
+# ---- the library's refusals that need no device: pom_deal.hip checks the spec before the handle ----------------------------------------
 def _spec_of(**kw):
     fields = dict(mode=0, which=0, reserved_=0, first=0, count=4, seed=1, layout=DO.STANDARD, reserved2_=0, games_dev=0x1000, which_dev=None,
                   result_dev=0x4000, stream=None)

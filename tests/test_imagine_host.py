@@ -196,7 +196,7 @@ def test_host_build_equals_the_checker_on_played_games_and_the_states_are_playab
     assert np.array_equal(again_words, words[order]) and _same(again, states[order])
 
 
-# ---- the library's refusals that need no device: pom_api_imagine.h checks the spec before the handle -------------------------------
+# ---- the library's refusals that need no device: pom_memory.hip checks the spec before the handle -------------------------------
 def test_library_refuses_a_bad_spec_by_name(hip_lib):
     lib = hip_lib
 
