@@ -10,7 +10,10 @@ Three kinds of input:
   C  hand-made states for what the corpus never holds (hand_states()).
 A Queries object holds the distinct states of one batch with their next moves, the placement of tests/test_record_edges._batch — state i
 at env 3i, states i + 7 and i + 13 beside it, a short tail to 15 mod 16 — and computes every checker once per distinct state; the rows
-are gathered by the placement (`order`).  The rollouts' draws are keyed by the env, so their checkers run on the placed batch."""
+are gathered by the placement (`order`).  The rollouts' draws are keyed by the env, so their checkers run on the placed batch.
+Queries(..., order=) takes another placement — any int array naming the state of every env, tests/mates_queries.py passes the chosen
+wavefronts of tests/tile_mates.py —: env_of(), jobs() and expand() then speak of "an env that holds state j", and of the states the
+order holds at all."""
 import functools
 import importlib.util
 import os
@@ -223,14 +226,18 @@ class Queries:
     """the distinct states of one batch, the moves each plays next, the placement, and every checker's answer (computed on first use,
     kept, never written again)"""
 
-    def __init__(self, oracle, names, states, moves):
+    def __init__(self, oracle, names, states, moves, order=None):
         self.oracle, self.names = oracle, list(names)
         self.states = np.ascontiguousarray(states, dtype=STATE_DTYPE)
         self.moves = np.ascontiguousarray(moves, dtype=np.int32).reshape(-1, 4)
         self.d = self.states.size
         assert len(self.names) == self.d == len(self.moves)
-        self.order = placement(self.d)
+        self.order = placement(self.d) if order is None else np.array(order, dtype=np.int64)
+        assert self.order.ndim == 1 and self.order.size and 0 <= self.order.min() and self.order.max() < self.d
         self.n = len(self.order)
+        # a given order: the envs of every state, in the batch's order, and the states it holds (the default holds every state thrice)
+        self._envs = None if order is None else [np.nonzero(self.order == j)[0] for j in range(self.d)]
+        self.held = np.arange(self.d) if order is None else np.unique(self.order)
         self.placed, self.placed_moves = self.states[self.order], self.moves[self.order]
         self._kept = {}
 
@@ -244,7 +251,10 @@ class Queries:
         return self._kept[key]
 
     def env_of(self, j, r):
-        """the env that holds state j as the r-th of its triple (r = 0, 1, 2: i, i + 7, i + 13)"""
+        """the env that holds state j as the r-th of its triple (r = 0, 1, 2: i, i + 7, i + 13); under a given order: an env that holds
+        state j, the r-th of them (counted round)"""
+        if self._envs is not None:
+            return int(self._envs[j][r % len(self._envs[j])])
         return 3 * ((j - (0, 7, 13)[r]) % self.d) + r
 
     def name_of_env(self, k):
@@ -278,11 +288,11 @@ class Queries:
         """a source list that names every distinct state once (at one of its three envs, by turns) and every fifth a second time at
         another, in a fixed shuffled order; the moves of a job: its state's next moves, for the second naming all BOMB.
         -> (src int64 [m], moves int32 [m, 4], words uint32 [ROLLOUT_R, m])"""
-        first = np.array([self.env_of(j, j % 3) for j in range(self.d)], dtype=np.int64)
-        again = np.array([self.env_of(j, (j + 1) % 3) for j in range(0, self.d, 5)], dtype=np.int64)
+        first = np.array([self.env_of(j, j % 3) for j in self.held], dtype=np.int64)
+        again = np.array([self.env_of(j, (j + 1) % 3) for j in self.held[::5]], dtype=np.int64)
         src = np.concatenate([first, again])
-        mv = np.concatenate([self.moves, np.full((len(again), 4), 5, dtype=np.int32)])
-        assert np.array_equal(self.order[first], np.arange(self.d)) and np.array_equal(self.order[again], np.arange(0, self.d, 5))
+        mv = np.concatenate([self.moves[self.held], np.full((len(again), 4), 5, dtype=np.int32)])
+        assert np.array_equal(self.order[first], self.held) and np.array_equal(self.order[again], self.held[::5])
         perm = np.random.default_rng(7).permutation(len(src))
         src, mv = src[perm], np.ascontiguousarray(mv[perm])
         words = self._once("jobs", lambda: JO.rollout_jobs(self.oracle, self.placed, None, src, ROLLOUT_K, ROLLOUT_R, SEED, RO.DIST_STRESS, JOBS_SIMPLE,
@@ -291,14 +301,15 @@ class Queries:
 
     # ---- expand: env n + j becomes the child of one env of state j under the state's next moves
     def expand(self, mode):
-        """-> (src int64 [d], the whole batch of n + d states after the call, its statuses, words, FLAME_QUEUE_RANGE raised per child)"""
-        src = np.array([self.env_of(j, (j + 2) % 3) for j in range(self.d)], dtype=np.int64)
-        assert np.array_equal(self.order[src], np.arange(self.d))
+        """-> (src int64 [d], the whole batch of n + d states after the call, its statuses, words, FLAME_QUEUE_RANGE raised per child);
+        under a given order d counts the states it holds"""
+        src = np.array([self.env_of(j, (j + 2) % 3) for j in self.held], dtype=np.int64)
+        assert np.array_equal(self.order[src], self.held)
 
         def make():
-            both = np.concatenate([self.placed, np.zeros(self.d, dtype=STATE_DTYPE)])
-            want, status, words, ticks, _ = XO.expand(self.oracle, both, None, src, self.moves, self.n, mode)
-            assert ticks == self.d
+            both = np.concatenate([self.placed, np.zeros(len(src), dtype=STATE_DTYPE)])
+            want, status, words, ticks, _ = XO.expand(self.oracle, both, None, src, self.moves[self.held], self.n, mode)
+            assert ticks == len(src)
             return want, status, words
         return (src,) + self._once(("expand", mode), make)
 

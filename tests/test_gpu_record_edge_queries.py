@@ -1,6 +1,6 @@
 """The search, reach and view calls at the limits of the packed record.  The directed corpus of tests/edge_states.py has so far met the
 step kernels, the plain observation and the SimpleAgent policy only; every call below embeds the tick in a kernel of its own or reads the
-record directly, and has been fed hand-made cases of ordinary size and played games.  Here pom_batch_forecast, _move_safety, _rollout
+record directly (pom_batch_step_mixed, the closed loop's call, among them: test_step_mixed), and has been fed hand-made cases of ordinary size and played games.  Here pom_batch_forecast, _move_safety, _rollout
 (both forms), _rollout_jobs, _expand, _reach, _observe_view and _remember_view answer for (tests/edge_queries.py)
   A  the 1,337 uploadable states the corpus reaches at ticks 0, 1, 2, 3, 5, 8, 13, 24 and at each entry's end, with the moves its script
      plays next: 4,015 envs, every state in three tile columns, the last tile short;
@@ -26,6 +26,7 @@ from tests import move_safety_oracle as MO
 from tests import rollout_oracle as RO
 from tests import view_oracle as VO
 from tests.edge_states import FATAL, UB_FLAME_QUEUE_RANGE, narrow_field_entries
+from tests.mixed_model import MixedModel
 from tests.test_emul import emul_bins  # noqa: F401  (the host builds of the device tick, built as test_emul.py builds them)
 from tests.test_record_edges import _pack_roundtrip, assert_tick_matches
 
@@ -482,3 +483,121 @@ def test_remember_view(hip_lib, sets, which):
         env.sync()
         _same(q, "call 1: memory", memory, m1[q.order])
         _same(q, "call 1: stamp", stamp, s1[q.order])
+
+
+# ---------------------------------------------------------------------------------------------------------------- pom_batch_step_mixed
+MIXED_MASKS = (0, 0b1010, 0xF)
+MIXED_RADIUS = 4
+MIXED_HELD = {"A": 245, "C": 3}                       # envs whose tick raises FLAME_QUEUE_RANGE, under every mask (81 states of A, 1 of C)
+MIXED_FATAL = {"A": {0: 9, 0b1010: 9, 0xF: 0}}         # envs whose tick raises a fatal flag: compared in full
+
+
+class _RawTicks:
+    """MixedModel (tests/mixed_model.py) for a MODE_RAW handle: Environment::Step's bookkeeping left out, the tick alone"""
+
+    def __init__(self, oracle):
+        self.simple_policy, self.boardgen, self._step = oracle.simple_policy, oracle.boardgen, oracle.step
+
+    def env_step(self, state, moves, status):
+        return self._step(state, moves)
+
+
+def _mixed_views(states):
+    ob = EQ.observe_oracle()
+    _, attrs, env2 = ob.observe(states)
+    return VO.view_codes(ob.observe_codes(states), attrs, MIXED_RADIUS), VO.viewer_attrs(attrs, env2[:, 0]), env2
+
+
+def _mixed_outputs(n):
+    import torch
+    out = (torch.full((n, 4, 5, 11, 11), 0xEE, dtype=torch.uint8, device="cuda"), torch.full((n, 4, 12), -7, dtype=torch.int32, device="cuda"),
+           torch.full((n, 4), -7, dtype=torch.int32, device="cuda"))
+    torch.cuda.synchronize()   # the sentinels are in place before the handle's stream writes
+    return out
+
+
+def _mixed_matches(q, what, env, model, outs, first, count, env0=0):
+    """envs [first, first + count) of the handle after ONE mixed tick against the model's: state, status, flags, memory, and the fused
+    fogged codes.  An env whose tick raised FLAME_QUEUE_RANGE may differ in EQ.QUEUE_BYTES only (assert_tick_matches' exemption); its
+    views are then the oracles' of the model's State with the record's queue bytes in it (as test_remember_view).  -> envs held"""
+    rows = slice(first, first + count)
+    got, st = env.get_state()[rows], env.status()
+    want = model.states[rows].copy()
+    held = (model.ubflags[rows] & UB_FLAME_QUEUE_RANGE) != 0
+    g, w = got.view(np.uint8).reshape(-1, 1004), want.view(np.uint8).reshape(-1, 1004)
+    differs = g != w
+    differs[held, EQ.QUEUE_BYTES] = False
+    bad = np.nonzero(differs.any(axis=1))[0]
+    assert bad.size == 0, f"{what}: {len(bad)} states differ, first {q.name_of_env(env0 + bad[0])}: bytes {np.nonzero(differs[bad[0]])[0][:12].tolist()}"
+    assert (got["flames_count"][held] == np.minimum(want["flames_count"][held], 255)).all() and (got["flames_queue"]["timeLeft"][held] >= -128).all()
+    for k, mine in (("done", model.done), ("winner", model.winner), ("draw", model.draw), ("ubflags", model.ubflags)):
+        _same(q, f"{what}: status {k}", np.asarray(st[k][rows]).astype(mine.dtype), mine[rows])
+    _same(q, f"{what}: memory", env.policy_memory()[rows], model.mems[rows])
+    w[held, EQ.QUEUE_BYTES] = g[held, EQ.QUEUE_BYTES]
+    for name, got_t, want_a in zip(("codes", "viewer_attrs", "env_attrs"), outs, _mixed_views(want)):
+        got_a = got_t.cpu().numpy()[rows]
+        _same(q, f"{what}: fused fogged {name}", got_a[:, :2] if name == "env_attrs" else got_a, want_a)
+    return held
+
+
+@gpu
+@pytest.mark.parametrize("which", SETS)
+def test_step_mixed(hip_lib, oracle, sets, which):
+    """one tick of pom_batch_step_mixed on every state with its next moves: the scripts alone (mask 0), SimpleAgents in seats 1 and 3, and
+    in all four — fresh agents, seed EQ.SEED, the fused fogged codes of radius 4 — against tests/mixed_model.py.  A and C: a MODE_ENV
+    handle per mask.  B: the MODE_RAW handle that plays the entries holds every env a second time behind the batch; after every tick of
+    the walk the records are copied there (copy_envs: the record as it stands, fields beyond upload's bounds included) and ticked once
+    under each mask, the model's tick being Oracle.step alone."""
+    from pomcpp_amd.batch import MODE_ENV, MODE_RAW, RESET_OFF, BatchEnvironment
+    qs = sets(which)
+    if which in UPLOADED:
+        q = qs[0]
+        models = {}
+        for mask in MIXED_MASKS:
+            models[mask] = MixedModel(oracle, q.placed)
+            models[mask].tick_mixed(0, q.n, q.placed_moves, mask, EQ.SEED, 0)
+        for mask in MIXED_MASKS:
+            with BatchEnvironment(q.n, mode=MODE_ENV, auto_reset=RESET_OFF) as env:
+                env.make_game(q.placed)
+                env.sync()
+                outs = _mixed_outputs(q.n)
+                env.step_mixed(0, q.n, _dev(q.placed_moves), mask, EQ.SEED, 0, None, codes=outs[0], view_radius=MIXED_RADIUS, viewer_attrs=outs[1],
+                               env_attrs=outs[2])
+                env.sync()
+                held = _mixed_matches(q, f"mask {mask:#x}", env, models[mask], outs, 0, q.n)
+                assert int(held.sum()) == MIXED_HELD[which] and 0 < len(set(q.order[held].tolist())) <= q.d // 8
+                fatal = (models[mask].ubflags & FATAL) != 0
+                assert int(fatal.sum()) == MIXED_FATAL.get(which, {}).get(mask, 0)
+                assert np.array_equal(env.counters(), models[mask].counters)
+        return
+    n = qs[0].n
+    back = n + (-n) % 16                                 # the copies start on a tile of their own
+    raw = _RawTicks(oracle)
+    models = []                                          # [tick][mask]: the model of the whole handle, its second part ticked once
+    for t, q in enumerate(qs):
+        both = np.concatenate([q.placed, np.zeros(back - n, dtype=STATE_DTYPE), q.placed])
+        mv = np.concatenate([q.placed_moves, np.zeros((back - n, 4), dtype=np.int32), q.placed_moves])
+        row = {}
+        for mask in MIXED_MASKS:
+            row[mask] = MixedModel(raw, both)
+            row[mask].tick_mixed(back, n, mv, mask, EQ.SEED, t)
+        models.append((mv, row))
+    asked = 0
+    with BatchEnvironment(back + n, mode=MODE_RAW) as env:
+        env.make_game(np.concatenate([qs[0].placed, np.zeros(back - n + n, dtype=STATE_DTYPE)]))
+        env.step_mixed(0, 0, None, 0xF, EQ.SEED, 0)   # (allocates the agents' memory: copy_envs then copies the walk's fresh agents)
+        outs = _mixed_outputs(back + n)
+        for t, q in enumerate(qs):
+            if t:
+                env.step_mixed(0, back, _dev(models[t - 1][0]), 0, EQ.SEED, t - 1)   # the walk itself: the scripts through the mixed kernel
+                env.sync()
+            assert env.get_state(0, n).tobytes() == q.placed.tobytes(), f"tick {t}: the record is not the oracle's state"
+            mv, row = models[t]
+            for mask in MIXED_MASKS:
+                env.copy_envs(np.arange(n, dtype=np.int64), first=back)
+                env.step_mixed(back, n, _dev(mv), mask, EQ.SEED, t, None, codes=outs[0], view_radius=MIXED_RADIUS, viewer_attrs=outs[1], env_attrs=outs[2])
+                env.sync()
+                _mixed_matches(q, f"tick {t}, mask {mask:#x}", env, row[mask], outs, back, n)
+                asked += int(row[mask].mems[back:].any(axis=(1, 2)).sum())
+            assert env.get_state(0, n).tobytes() == q.placed.tobytes(), f"tick {t}: the copies' ticks changed the batch"
+    assert asked > len(qs) * n   # SimpleAgents were asked on the states beyond upload's bounds too

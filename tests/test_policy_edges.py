@@ -210,6 +210,14 @@ def test_gpu_replays_the_reference_games(hip_lib, fx, shape, fused):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("mask", [0xF, 0b0101], ids=["mask_1111", "mask_0101"])
+def test_gpu_mixed_step_replays_the_reference_games(hip_lib, fx, mask):
+    """the same 117 games through pom_batch_step_mixed: with 0b0101 agents 1 and 3 take the Moves the fixture recorded, so any mask
+    must reproduce the same game — the masked agents' memory is the fixture's, the state a step_simple twin's, every tick"""
+    assert _replay_on_gpu(fx, via="mixed", mask=mask) > (10000 if mask == 0xF else 5000)
+
+
+@pytest.mark.gpu
 def test_gpu_replays_a_ragged_prefix(hip_lib, fx):
     """the first 16 * 3 + 1 games only: the last wavefront holds one env"""
     sub = dict(fx)

@@ -24,7 +24,10 @@ wavefront's own LDS tile are used (GPU tests failing here / in test_record_edges
   the restart from the snapshot writes column ec_u ^ 1                                                 10 /  1 / 2
   the fresh board of a restart is drawn into column ec_u ^ 1                                            4 /  0 / 0
   the end-of-tick restart writes column ec_u ^ 1                                                        1 /  1 / 0
-  bdest() / put_bdest() of columns el and el ^ 1 share their rows                                      13 /  0 / 2"""
+  bdest() / put_bdest() of columns el and el ^ 1 share their rows                                      13 /  0 / 2
+
+The GPU part here runs pom_step_kernel only.  The kernels that embed the same tick in an LDS array of their own — the mixed step, the
+rollouts, forecast, move_safety, expand, the fogged export — meet this module's batch in tests/test_gpu_mates_queries.py."""
 import ctypes as C
 import os
 
