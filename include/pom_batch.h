@@ -429,6 +429,82 @@ typedef struct PomMixedStepSpec {
 int pom_batch_step_mixed(PomBatch* h, const PomMixedStepSpec* spec);
 
 /*
+ * STEP EVENTS: pom_batch_step_mixed that also says what the tick did — one word per agent, and per env an outcome word and a count of
+ * burnt wood, written by the same launch.  What a learner on the device needs and the state after the tick no longer holds: with
+ * POM_RESET_AT_END the finishing tick has already put the env on its next start state, and the move a SimpleAgent played is written
+ * nowhere.  `step` is pom_batch_step_mixed's spec, unchanged, and the call does everything pom_batch_step_mixed(h, step) does, bit for
+ * bit — records, status, episodes, counters, ubflags, terminal records, agent memory, observation — as ONE launch on step->stream, with
+ * no runtime call once the handle is settled (the one exception is pom_batch_step_mixed's: the first call that needs the agents'
+ * memory).  simple_mask == 0 makes it pom_batch_step_device_range(_view) with events.
+ * The three arrays are caller-owned device memory sized for the WHOLE batch and indexed by the env's number in it, as moves_dev is;
+ * only the rows of [first, first + count) are written.
+ * THE RULE, per env e of the range, is a pure function of
+ *          S0  the env's state when its tick begins: after the restart at the start, if one happened (POM_RESET_AT_START);
+ *          m   the four moves handed to the tick, as the tick's clamp leaves them (0..5, anything else 6 — which moves nobody);
+ *          S1  the state the tick and Environment::Step's bookkeeping leave, BEFORE the restart at the end (POM_RESET_AT_END).
+ * events[e][a], for an env that played a tick in this call:
+ *          POM_EV_MOVE       bits 0..2   m[a]: the policy's move for a live agent of simple_mask, IDLE for a dead one, the caller's
+ *                                        clamped entry for an agent outside the mask, dead or alive
+ *          POM_EV_PLAYED     bit 3       the env was ticked by this call
+ *          POM_EV_ALIVE      bit 4       !S1.agents[a].dead
+ *          POM_EV_DIED       bit 5       alive in S0, dead in S1
+ *          POM_EV_MOVED      bit 6       alive in S0 and (x, y) differ between S0 and S1
+ *          POM_EV_LAID       bit 7       alive in S0, m[a] == BOMB and S0.bombCount < S0.maxBombCount: exactly when step.cpp:52-55
+ *                                        reaches PlantBombModifiedLife and bboard.cpp:127-130 does not return (not a heuristic)
+ *          POM_EV_GAIN_BOMB / _GAIN_RANGE / _GAIN_KICK   bits 8 / 9 / 10
+ *                                        maxBombCount grew / bombStrength grew / canKick went false -> true: attribute differences,
+ *                                        so a kick picked up by an agent that can already kick is not an event
+ *          POM_EV_RESTARTED  bit 11      the env restarted at the start of this call, so S0 is a start state (POM_RESET_AT_START)
+ *          POM_EV_EXPLODED   bits 12..15 clamp(S0.bombCount + LAID - S1.bombCount, 0, 15): own bombs that went off, counted for a
+ *                                        dead owner too (ExplodeBombAt does not ask, bboard.cpp:116)
+ *          POM_EV_END        bit 16      POM_MODE_ENV: this tick finished the episode
+ *          POM_EV_WON / _DRAW / _TIMEOUT  bits 17 / 18 / 19   with END: winner == a / POM_ST_DRAW / POM_ST_TIMEOUT of S1's status
+ *          POM_EV_UB         bit 20      this tick raised a POM_UB_* flag in the env (pom_state.h)
+ *          An env of the range that is NOT ticked (finished, POM_MODE_ENV, not restarted) gets POM_EV_ALIVE alone in its four words.
+ *          POM_MODE_RAW: bits 16..19 are never set.
+ * outcome[e] (nullable): the POM_RO_* word (pom_batch_rollout) of S1 — the alive mask, POM_RO_DONE / _DRAW / _TIMEOUT, POM_RO_UB if
+ *          THIS tick raised a flag, winner + 1 — with min(S1.timeStep, 65535) in the length field.  On an END tick under
+ *          POM_RESET_AT_END it is what pom_batch_last_results reports for that env, without the host.  An env that is not ticked: the
+ *          word of the state as it stands.
+ * wood[e] (nullable): the number of cells that are wood (with or without a hidden item) in S0 and not wood in S1, saturating at 255;
+ *          0 for an env that is not ticked.
+ * POM_E_ARG (with a pom_last_error text naming pom_batch_step_events; nothing is launched): whatever pom_batch_step_mixed refuses of
+ *          `step`, then a null `ev`, struct_size != sizeof(PomStepEventsSpec) (POM_STEP_EVENTS_SPEC_SIZE), nonzero flags or reserved_,
+ *          a null events_dev, events_dev or outcome_dev not 4-byte aligned.
+ * Not here: whose bomb killed an agent or burnt a wood (flames carry no owner in the reference: EXPLODED beside DIED / wood is what
+ *          a caller splits credit with), kick events, a reward function, a host-pointer form.
+ */
+enum {
+    POM_EV_MOVE = 0x7,
+    POM_EV_PLAYED = 1 << 3,
+    POM_EV_ALIVE = 1 << 4,
+    POM_EV_DIED = 1 << 5,
+    POM_EV_MOVED = 1 << 6,
+    POM_EV_LAID = 1 << 7,
+    POM_EV_GAIN_BOMB = 1 << 8,
+    POM_EV_GAIN_RANGE = 1 << 9,
+    POM_EV_GAIN_KICK = 1 << 10,
+    POM_EV_RESTARTED = 1 << 11,
+    POM_EV_EXPLODED_SHIFT = 12, /* 4 bits */
+    POM_EV_EXPLODED = 0xF << 12,
+    POM_EV_END = 1 << 16,
+    POM_EV_WON = 1 << 17,
+    POM_EV_DRAW = 1 << 18,
+    POM_EV_TIMEOUT = 1 << 19,
+    POM_EV_UB = 1 << 20
+};
+enum { POM_STEP_EVENTS_SPEC_SIZE = 40 }; /* 2 x int32, 3 pointers, int64: no implicit padding on an LP64 target */
+typedef struct PomStepEventsSpec {
+    int32_t struct_size;       /*  0  = sizeof(PomStepEventsSpec) */
+    int32_t flags;             /*  4  must be 0 */
+    uint32_t* events_dev;      /*  8  required: uint32 [n][4], one word per agent */
+    uint32_t* outcome_dev;     /* 16  nullable: uint32 [n], one POM_RO_* word per env */
+    uint8_t* wood_dev;         /* 24  nullable: uint8 [n], wood cells burnt this tick */
+    int64_t reserved_;         /* 32  must be 0 */
+} PomStepEventsSpec;
+int pom_batch_step_events(PomBatch* h, const PomMixedStepSpec* step, const PomStepEventsSpec* ev);
+
+/*
  * FORECAST: where will the fire be, and when — flames and deaths K ticks ahead, without touching the batch.  The reference's own
  * answer is strategy::IsInDanger (src/bboard/strategy.cpp:229-249), the smallest timer over the bombs whose cross covers a cell; its
  * comment says "TODO: add consideration for chained bomb explosions", and it knows nothing of walls, wood or moving bombs either.

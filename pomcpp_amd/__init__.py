@@ -18,4 +18,6 @@ from .state import (  # noqa: F401
 from .boards import make_boards  # noqa: F401
 from .batch import (BatchEnvironment, PomError, library_path, load_library, decode_rollout, move_towards, new_view_memory, decode_imagine,  # noqa: F401
                     BoardLayout, new_games, decode_deal,
-                    RESET_OFF, RESET_AT_START, RESET_AT_END)
+                    RESET_OFF, RESET_AT_START, RESET_AT_END, decode_step_events,
+                    EV_MOVE, EV_PLAYED, EV_ALIVE, EV_DIED, EV_MOVED, EV_LAID, EV_GAIN_BOMB, EV_GAIN_RANGE, EV_GAIN_KICK, EV_RESTARTED,
+                    EV_EXPLODED_SHIFT, EV_EXPLODED, EV_END, EV_WON, EV_DRAW, EV_TIMEOUT, EV_UB)

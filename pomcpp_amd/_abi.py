@@ -29,6 +29,10 @@ DEAL_DEALT, DEAL_FALLBACK, DEAL_ATTEMPTS_SHIFT, DEAL_BAD_SHIFT = 1, 2, 8, 16  # 
 RO_NONE = 0  # POM_RO_NONE: rollout_jobs' word of an entry without a job
 # the result word of a rollout (the header's POM_RO_*)
 RO_ALIVE, RO_DONE, RO_DRAW, RO_TIMEOUT, RO_UB, RO_WINNER_SHIFT, RO_WINNER_MASK, RO_LENGTH_SHIFT = 0xF, 0x10, 0x20, 0x40, 0x80, 8, 0x700, 16
+# a step's event word (the header's POM_EV_*, PomStepEventsSpec)
+(EV_MOVE, EV_PLAYED, EV_ALIVE, EV_DIED, EV_MOVED, EV_LAID, EV_GAIN_BOMB, EV_GAIN_RANGE, EV_GAIN_KICK, EV_RESTARTED, EV_EXPLODED_SHIFT,
+ EV_EXPLODED, EV_END, EV_WON, EV_DRAW, EV_TIMEOUT, EV_UB) = (0x7, 1 << 3, 1 << 4, 1 << 5, 1 << 6, 1 << 7, 1 << 8, 1 << 9, 1 << 10, 1 << 11, 12,
+                                                                0xF << 12, 1 << 16, 1 << 17, 1 << 18, 1 << 19, 1 << 20)
 
 
 class PomError(RuntimeError):
@@ -157,9 +161,19 @@ class _MixedStepSpec(C.Structure):
     ]
 
 
+class _StepEventsSpec(C.Structure):
+    """PomStepEventsSpec (include/pom_batch.h): where pom_batch_step_events writes the agents' event words, the envs' outcome words and
+    the burnt-wood counts"""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("flags", C.c_int32), ("events_dev", C.c_void_p), ("outcome_dev", C.c_void_p), ("wood_dev", C.c_void_p),
+        ("reserved_", C.c_int64),
+    ]
+
+
 STRUCTURES = {"PomBatchOptions": _Options, "PomViewSpec": _ViewSpec, "PomForecastSpec": _ForecastSpec,
               "PomMoveSafetySpec": _MoveSafetySpec, "PomReachSpec": _ReachSpec, "PomMemorySpec": _MemorySpec, "PomImagineSpec": _ImagineSpec, "PomDealSpec": _DealSpec, "PomRolloutSpec": _RolloutSpec,
-              "PomRolloutPolicySpec": _RolloutPolicySpec, "PomRolloutJobsSpec": _RolloutJobsSpec, "PomExpandSpec": _ExpandSpec, "PomMixedStepSpec": _MixedStepSpec}  # the header's name of each
+              "PomRolloutPolicySpec": _RolloutPolicySpec, "PomRolloutJobsSpec": _RolloutJobsSpec, "PomExpandSpec": _ExpandSpec, "PomMixedStepSpec": _MixedStepSpec,
+              "PomStepEventsSpec": _StepEventsSpec}  # the header's name of each
 
 
 def _ptr(t):
@@ -191,6 +205,7 @@ PROTOTYPES = (  # (name, argtypes or None: no parameters, restype or None: int)
     ("pom_batch_step_device_observe_view", [_P, _VP, C.POINTER(_ViewSpec)], None),
     ("pom_batch_step_device_range_view", [_P, _I64, _I64, _VP, _VP, C.POINTER(_ViewSpec)], None),
     ("pom_batch_step_mixed", [_P, C.POINTER(_MixedStepSpec)], None),
+    ("pom_batch_step_events", [_P, C.POINTER(_MixedStepSpec), C.POINTER(_StepEventsSpec)], None),
     ("pom_batch_forecast", [_P, C.POINTER(_ForecastSpec)], None),
     ("pom_batch_rollout", [_P, C.POINTER(_RolloutSpec)], None),
     ("pom_batch_rollout_policy", [_P, C.POINTER(_RolloutPolicySpec)], None),

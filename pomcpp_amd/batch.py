@@ -31,7 +31,8 @@ from ._abi import (  # noqa: F401 (the binding's names are this module's too: ca
     _MoveSafetySpec, _ReachSpec, _MemorySpec, _ImagineSpec, _RolloutSpec, IMAGINE_SAMPLE, IMAGINE_PASSAGE, IMAGINE_BUILT, IMAGINE_DROPPED_BOMBS,
     IMAGINE_DROPPED_FLAMES, IMAGINE_NO_ROOM, IMAGINE_UNKNOWN_SHIFT, IMAGINE_DRAWN_SHIFT, _BoardLayout, _DealSpec, DEAL_START, DEAL_NEXT, DEAL_ALL,
     DEAL_MASK, DEAL_RESTARTED, DEAL_DONE, LAYOUT_NO_LANES, DEAL_DEALT, DEAL_FALLBACK, DEAL_ATTEMPTS_SHIFT, DEAL_BAD_SHIFT,
-    _RolloutPolicySpec, _RolloutJobsSpec, _ExpandSpec, _MixedStepSpec, _ptr, _spec, _view_spec, _forecast_spec, library_path, load_library, _check)
+    _RolloutPolicySpec, _RolloutJobsSpec, _ExpandSpec, _MixedStepSpec, _StepEventsSpec, EV_MOVE, EV_PLAYED, EV_ALIVE, EV_DIED, EV_MOVED, EV_LAID,
+    EV_GAIN_BOMB, EV_GAIN_RANGE, EV_GAIN_KICK, EV_RESTARTED, EV_EXPLODED_SHIFT, EV_EXPLODED, EV_END, EV_WON, EV_DRAW, EV_TIMEOUT, EV_UB, _ptr, _spec, _view_spec, _forecast_spec, library_path, load_library, _check)
 from .state import STATE_DTYPE
 
 
@@ -110,6 +111,25 @@ def decode_rollout(result) -> dict:
         bits, i32 = w[..., None] >> torch.arange(4, device=w.device) & 1, lambda a: a.to(torch.int32)  # noqa: E731
     return {"alive": bits != 0, "done": (w & RO_DONE) != 0, "draw": (w & RO_DRAW) != 0, "timeout": (w & RO_TIMEOUT) != 0,
             "ub": (w & RO_UB) != 0, "winner": i32(((w & RO_WINNER_MASK) >> RO_WINNER_SHIFT) - 1), "length": i32(w >> RO_LENGTH_SHIFT)}
+
+
+def decode_step_events(word) -> dict:
+    """The fields of step_events()'s event words (torch tensor or numpy array of any shape [...], int32 or uint32; PomStepEventsSpec in
+    include/pom_batch.h states the rule): `move` and `exploded` (own bombs that went off) int32 [...]; `played`, `alive`, `died`, `moved`,
+    `laid`, `gain_bomb`, `gain_range`, `gain_kick`, `restarted`, `end`, `won`, `draw`, `timeout`, `ub` bool [...]; the same kind of array
+    as the input, on its device.  The outcome words are rollout()'s: decode_rollout()."""
+    w = word
+    if isinstance(w, np.ndarray):
+        w, i32 = w.astype(np.int64) & 0xFFFFFFFF, lambda a: a.astype(np.int32)  # noqa: E731
+    else:
+        import torch
+        w, i32 = w.to(torch.int64) & 0xFFFFFFFF, lambda a: a.to(torch.int32)  # noqa: E731
+    out = {"move": i32(w & EV_MOVE), "exploded": i32((w & EV_EXPLODED) >> EV_EXPLODED_SHIFT)}
+    for name, bit in (("played", EV_PLAYED), ("alive", EV_ALIVE), ("died", EV_DIED), ("moved", EV_MOVED), ("laid", EV_LAID),
+                      ("gain_bomb", EV_GAIN_BOMB), ("gain_range", EV_GAIN_RANGE), ("gain_kick", EV_GAIN_KICK), ("restarted", EV_RESTARTED),
+                      ("end", EV_END), ("won", EV_WON), ("draw", EV_DRAW), ("timeout", EV_TIMEOUT), ("ub", EV_UB)):
+        out[name] = (w & bit) != 0
+    return out
 
 
 def decode_imagine(word) -> dict:
@@ -562,18 +582,9 @@ class BatchEnvironment:
         else:
             self._call("pom_batch_step_device_range", first, count, ptr, st, _ptr(out), code, int(per_agent), _ptr(agent_attrs), _ptr(env_attrs))
 
-    def step_mixed(self, first: int, count: int, moves, simple, seed: int, tick: int, stream=None, codes=None, planes=None,
-                   view_radius: Optional[int] = None, viewer_attrs=None, env_attrs=None, *, per_agent: Optional[bool] = None,
-                   agent_attrs=None) -> None:
-        """step_device_range() with SimpleAgent opponents (pom_batch_step_mixed): one tick for the envs [first, first + count) — whole
-        tiles of 16 — as ONE launch on `stream`, in which the agents of `simple` (a mask int 0..15 or an iterable of agent ids) are
-        played by SimpleAgent inside the launch — asked as policy_simple(seed) asks them at handle tick `tick` (0..2^32-1), their memory
-        (policy_memory()) moved on — and the others take `moves[e][a]` (int32[n, 4] device tensor or address, indexed by env; None only
-        if all four agents are SimpleAgents).  The ranges of a closed loop advance on their own, so the caller counts each range's
-        `tick`; the handle's tick, its move buffer and the envs outside the range are left alone.  The observation arguments, the
-        checks (a ValueError before anything is launched, no runtime call) and the ordering are step_device_range()'s.  The first call
-        with a non-empty `simple` on a handle that has run no policy yet allocates the agents' memory and synchronises the handle's
-        stream once: make it — count 0 does only that — before capturing mixed steps into a graph."""
+    def _mixed_step_spec(self, first, count, moves, simple, seed, tick, stream, codes, planes, view_radius, viewer_attrs, env_attrs, per_agent,
+                         agent_attrs) -> _MixedStepSpec:
+        """step_mixed()'s arguments checked, as the PomMixedStepSpec that step_mixed() and step_events() hand to the library"""
         first, count = self._in_batch(first, count)
         mask, tick = _agent_mask(simple, "simple"), _bounded(tick, "tick", 0, 0xFFFFFFFF)
         out, code, per_agent, view, _width, _shape, _dtype = self._observation(codes, planes, per_agent, view_radius, viewer_attrs, agent_attrs,
@@ -589,7 +600,50 @@ class BatchEnvironment:
         else:
             spec = _spec(_MixedStepSpec, mask, first, count, ptr, _u64(seed), tick, st, None, _ptr(out), code if out is not None else 0,
                          int(per_agent), _ptr(agent_attrs), _ptr(env_attrs), 0, 0)
-        self._call("pom_batch_step_mixed", C.byref(spec))
+        return spec
+
+    def step_mixed(self, first: int, count: int, moves, simple, seed: int, tick: int, stream=None, codes=None, planes=None,
+                   view_radius: Optional[int] = None, viewer_attrs=None, env_attrs=None, *, per_agent: Optional[bool] = None,
+                   agent_attrs=None) -> None:
+        """step_device_range() with SimpleAgent opponents (pom_batch_step_mixed): one tick for the envs [first, first + count) — whole
+        tiles of 16 — as ONE launch on `stream`, in which the agents of `simple` (a mask int 0..15 or an iterable of agent ids) are
+        played by SimpleAgent inside the launch — asked as policy_simple(seed) asks them at handle tick `tick` (0..2^32-1), their memory
+        (policy_memory()) moved on — and the others take `moves[e][a]` (int32[n, 4] device tensor or address, indexed by env; None only
+        if all four agents are SimpleAgents).  The ranges of a closed loop advance on their own, so the caller counts each range's
+        `tick`; the handle's tick, its move buffer and the envs outside the range are left alone.  The observation arguments, the
+        checks (a ValueError before anything is launched, no runtime call) and the ordering are step_device_range()'s.  The first call
+        with a non-empty `simple` on a handle that has run no policy yet allocates the agents' memory and synchronises the handle's
+        stream once: make it — count 0 does only that — before capturing mixed steps into a graph."""
+        self._call("pom_batch_step_mixed", C.byref(self._mixed_step_spec(first, count, moves, simple, seed, tick, stream, codes, planes, view_radius,
+                                                                         viewer_attrs, env_attrs, per_agent, agent_attrs)))
+
+    def _events_tensor(self, t, what: str, dtypes, shape):
+        """an array step_events() writes: a device tensor of one of the element types named in `dtypes` and of `shape`, or a raw
+        device address the caller vouches for; returns its address (None: NULL)"""
+        if t is None or not hasattr(t, "data_ptr"):
+            return None if t is None else int(t)
+        name = _dtype_name(getattr(t, "dtype", ""))
+        return self._device_tensor(t, what, name if name in dtypes else dtypes[0], shape).data_ptr()
+
+    def step_events(self, first: int, count: int, moves, simple, seed: int, tick: int, events, outcome=None, wood=None, stream=None,
+                    codes=None, planes=None, view_radius: Optional[int] = None, viewer_attrs=None, env_attrs=None, *,
+                    per_agent: Optional[bool] = None, agent_attrs=None) -> None:
+        """step_mixed() that also says what the tick did (pom_batch_step_events; the rule is PomStepEventsSpec's in include/pom_batch.h):
+        the same ONE launch on `stream`, everything step_mixed() leaves bit for bit, and for the envs of the range `events` — uint32 or
+        int32 [n, 4], one word per agent: the move it played (a SimpleAgent's included), whether it died, moved, laid a bomb, gained a
+        power-up, how many of its bombs went off, and whether the tick ended the episode and how (decode_step_events(); the EV_*
+        constants) —, `outcome` (optional, uint32 or int32 [n]: decode_rollout()'s word of the state the tick left BEFORE a restart at
+        the end — on an END tick under RESET_AT_END what last_results() reports, without the host) and `wood` (optional, uint8 [n]: wood
+        cells burnt by this tick).  The arrays are sized for the whole batch and indexed by env, as `moves` is; rows outside the range are
+        not touched.  Every other argument, check and ordering rule is step_mixed()'s; no runtime call is made here."""
+        spec = self._mixed_step_spec(first, count, moves, simple, seed, tick, stream, codes, planes, view_radius, viewer_attrs, env_attrs,
+                                     per_agent, agent_attrs)
+        if events is None:
+            raise ValueError("events is None: step_events() writes the event words there (step_mixed() is the call without them)")
+        ev = _spec(_StepEventsSpec, 0, self._events_tensor(events, "events", ("uint32", "int32"), (self.n, 4)),
+                   self._events_tensor(outcome, "outcome", ("uint32", "int32"), (self.n,)),
+                   self._events_tensor(wood, "wood", ("uint8",), (self.n,)), 0)
+        self._call("pom_batch_step_events", C.byref(spec), C.byref(ev))
 
     def chain_stats(self) -> dict:
         """chained launches since creation: launches issued, checks run, tiles found left behind, ticks replayed for them"""

@@ -2,7 +2,7 @@
  * pom_batch.hip — the C-ABI of include/pom_batch.h (libpom_batch.so): every entry point the reference-side binding links
  * (INTEGRATION.md).  gfx950 only; there is no CPU path: without a HIP device pom_batch_create fails with POM_E_HIP.
  *
- * The library is several translation units: this one, the core, and one per kernel family — pom_search.hip, pom_mixed.hip,
+ * The library is several translation units: this one, the core, and one per kernel family — pom_search.hip, pom_mixed.hip, pom_events.hip,
  * pom_memory.hip, pom_deal.hip — each holding its kernels with their entry points.  The units meet through pom_host.h (the handle and
  * how a call starts, fails and refuses: defined here, hidden from the library's exports) and pom_device.h (what kernels are made of).
  *
