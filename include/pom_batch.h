@@ -362,6 +362,41 @@ int pom_batch_observe_view(PomBatch* h, const PomViewSpec* spec);
 int pom_batch_step_device_observe_view(PomBatch* h, const int32_t* moves_dev, const PomViewSpec* spec);
 int pom_batch_step_device_range_view(PomBatch* h, int64_t first, int64_t count, const int32_t* moves_dev, void* stream,
                                      const PomViewSpec* spec);
+/*
+ * COMPACT VIEWS: only the asked viewers, cropped to their window — the code-plane views for a caller that plays some of the agents and
+ * reads only their views (the closed loop: the learner is agent 0, the others are SimpleAgents that never read theirs), as a dense
+ * batch.  A longer spec handed through the same `const PomViewSpec*` arguments (pass &spec.view): view.struct_size == 40 is the
+ * four-view form above, bit for bit; == sizeof(PomCompactViewSpec) (POM_COMPACT_VIEW_SPEC_SIZE) is this one; anything else is refused.
+ * Served by pom_batch_observe_view (one launch) and by the views of pom_batch_step_mixed and pom_batch_step_events (the tick's own
+ * launch; simple_mask == 0 is the range call).  pom_batch_step_device_observe_view and pom_batch_step_device_range_view refuse it.
+ * THE RULE.  k = popcount(viewer_mask), the chosen viewers v_0 < .. < v_{k-1}; r = view.view_radius (0..10); F[e][v][p][y][x] the byte
+ *          the four-view form (POM_OBS_CODES) writes for the same state and radius; (x_v, y_v) viewer v's position as viewer_attrs
+ *          reports it (a dead agent looks out from where it died).
+ *   flags == 0:        S = 11.  planes is uint8 [n][k][5][11][11], planes[e][j][p][y][x] = F[e][v_j][p][y][x].
+ *   POM_VIEW_CENTRED:  S = 2 r + 1.  planes is uint8 [n][k][5][S][S]; byte [e][j][p][dy][dx] is F[e][v_j][p][y_v - r + dy][x_v - r + dx]
+ *                      where that cell is on the board, off the board 5 (Item::FOG) in plane 0 and 0 in planes 1..4.  An on-board cell of
+ *                      the crop is always inside the window, so 5 in plane 0 means "off the board" and nothing else.
+ *   viewer_attrs (nullable): int32 [n][k][12], 16-byte aligned; row j is the row the four-view form writes for viewer v_j.
+ *   env_attrs (nullable): unchanged.
+ *   planes_dev: 4-byte aligned, dense, no padding between envs (an env's row is k * 5 * S * S bytes, odd for odd k).  Not one byte
+ *                      before planes_dev or from planes_dev + n * k * 5 * S * S on is written; a range call writes the rows of
+ *                      [first, first + count) only.
+ * Everything else follows the four-view form: ordering, settling, POM_RESET_AT_END showing the next start state, "nothing else changes".
+ * POM_E_ARG (with a pom_last_error text naming the call; nothing is written): viewer_mask outside 1..15, unknown flags bits, nonzero
+ *          reserved2_ or view.reserved_, view.dtype != POM_OBS_CODES, planes_dev null or not 4-byte aligned, viewer_attrs_dev or
+ *          env_attrs_dev not 16-byte aligned, whatever PomViewSpec refuses.
+ * Not here: the 16-plane dtypes; a mask per env; the compact form in the core unit's fused calls (pom_batch_step_device_observe_view,
+ *          pom_batch_step_device_range_view) and in pom_batch_expand; pom_batch_imagine and pom_batch_remember keep their four-row
+ *          viewer_attrs (PomMemorySpec writes its own).
+ */
+enum { POM_VIEW_CENTRED = 1 };
+enum { POM_COMPACT_VIEW_SPEC_SIZE = 56 };
+typedef struct PomCompactViewSpec {
+    PomViewSpec view;     /*  0  view.struct_size = sizeof(PomCompactViewSpec); view.dtype = POM_OBS_CODES; view.reserved_ = 0 */
+    int32_t viewer_mask;  /* 40  bit v: viewer v's view is written; 1..15 */
+    int32_t flags;        /* 44  0 or POM_VIEW_CENTRED */
+    int64_t reserved2_;   /* 48  must be 0 */
+} PomCompactViewSpec;
 
 /*
  * MIXED STEP: the closed-loop range call with SimpleAgent opponents — "my network plays some of the agents, agents::SimpleAgent the

@@ -1,4 +1,4 @@
-"""The ctypes mirror of include/pom_batch.h, and nothing else: its constants, its thirteen spec structures with their builders, the
+"""The ctypes mirror of include/pom_batch.h, and nothing else: its constants, its spec structures with their builders, the
 prototype of every function it declares (PROTOTYPES) and the loading of libpom_batch.so.  Whatever is written here is written a
 second time in the header; tests/test_abi_mirror.py compares the two, field by field and argument by argument, without the library.
 """
@@ -26,6 +26,7 @@ DEAL_START, DEAL_NEXT = 0, 1  # POM_DEAL_*: what a dealt env receives (PomDealSp
 DEAL_ALL, DEAL_MASK, DEAL_RESTARTED, DEAL_DONE = 0, 1, 2, 3  # which envs of the range are dealt (PomDealSpec.which)
 LAYOUT_NO_LANES = 1  # POM_LAYOUT_NO_LANES
 DEAL_DEALT, DEAL_FALLBACK, DEAL_ATTEMPTS_SHIFT, DEAL_BAD_SHIFT = 1, 2, 8, 16  # pom_batch_deal's result word
+VIEW_CENTRED = 1  # POM_VIEW_CENTRED (PomCompactViewSpec.flags)
 RO_NONE = 0  # POM_RO_NONE: rollout_jobs' word of an entry without a job
 # the result word of a rollout (the header's POM_RO_*)
 RO_ALIVE, RO_DONE, RO_DRAW, RO_TIMEOUT, RO_UB, RO_WINNER_SHIFT, RO_WINNER_MASK, RO_LENGTH_SHIFT = 0xF, 0x10, 0x20, 0x40, 0x80, 8, 0x700, 16
@@ -57,6 +58,12 @@ class _ViewSpec(C.Structure):
         ("struct_size", C.c_int32), ("dtype", C.c_int32), ("view_radius", C.c_int32), ("reserved_", C.c_int32),
         ("planes_dev", C.c_void_p), ("viewer_attrs_dev", C.c_void_p), ("env_attrs_dev", C.c_void_p),
     ]
+
+
+class _CompactViewSpec(C.Structure):
+    """PomCompactViewSpec (include/pom_batch.h): a PomViewSpec whose struct_size says 56, then whose views are written and how.  It
+    grows PomViewSpec and has no struct_size member of its own, so STRUCTURES — the specs that begin with one — does not list it"""
+    _fields_ = [("view", _ViewSpec), ("viewer_mask", C.c_int32), ("flags", C.c_int32), ("reserved2_", C.c_int64)]
 
 
 class _ForecastSpec(C.Structure):
@@ -186,8 +193,13 @@ def _spec(cls, *fields):
     return cls(C.sizeof(cls), *fields)
 
 
-def _view_spec(code: int, radius: int, planes, viewer_attrs=None, env_attrs=None) -> _ViewSpec:
-    return _spec(_ViewSpec, code, int(radius), 0, _ptr(planes), _ptr(viewer_attrs), _ptr(env_attrs))
+def _view_spec(code: int, radius: int, planes, viewer_attrs=None, env_attrs=None, compact=None) -> _ViewSpec:
+    """the spec of the fogged views; `compact` = (viewer_mask, flags): the PomViewSpec a PomCompactViewSpec begins with (&spec.view,
+    which keeps the whole spec alive)"""
+    if compact is None:
+        return _spec(_ViewSpec, code, int(radius), 0, _ptr(planes), _ptr(viewer_attrs), _ptr(env_attrs))
+    head = _ViewSpec(C.sizeof(_CompactViewSpec), code, int(radius), 0, _ptr(planes), _ptr(viewer_attrs), _ptr(env_attrs))
+    return _CompactViewSpec(head, int(compact[0]), int(compact[1]), 0).view
 
 
 def _forecast_spec(horizon: int, moves, flame_tick, agent_tick=None, ubflags=None) -> _ForecastSpec:

@@ -31,7 +31,7 @@ from ._abi import (  # noqa: F401 (the binding's names are this module's too: ca
     _MoveSafetySpec, _ReachSpec, _MemorySpec, _ImagineSpec, _RolloutSpec, IMAGINE_SAMPLE, IMAGINE_PASSAGE, IMAGINE_BUILT, IMAGINE_DROPPED_BOMBS,
     IMAGINE_DROPPED_FLAMES, IMAGINE_NO_ROOM, IMAGINE_UNKNOWN_SHIFT, IMAGINE_DRAWN_SHIFT, _BoardLayout, _DealSpec, DEAL_START, DEAL_NEXT, DEAL_ALL,
     DEAL_MASK, DEAL_RESTARTED, DEAL_DONE, LAYOUT_NO_LANES, DEAL_DEALT, DEAL_FALLBACK, DEAL_ATTEMPTS_SHIFT, DEAL_BAD_SHIFT,
-    _RolloutPolicySpec, _RolloutJobsSpec, _ExpandSpec, _MixedStepSpec, _StepEventsSpec, EV_MOVE, EV_PLAYED, EV_ALIVE, EV_DIED, EV_MOVED, EV_LAID,
+    _RolloutPolicySpec, _RolloutJobsSpec, _ExpandSpec, _MixedStepSpec, _StepEventsSpec, _CompactViewSpec, VIEW_CENTRED, EV_MOVE, EV_PLAYED, EV_ALIVE, EV_DIED, EV_MOVED, EV_LAID,
     EV_GAIN_BOMB, EV_GAIN_RANGE, EV_GAIN_KICK, EV_RESTARTED, EV_EXPLODED_SHIFT, EV_EXPLODED, EV_END, EV_WON, EV_DRAW, EV_TIMEOUT, EV_UB, _ptr, _spec, _view_spec, _forecast_spec, library_path, load_library, _check)
 from .state import STATE_DTYPE
 
@@ -80,6 +80,18 @@ def _agent_mask(v, name: str) -> int:
     if any(not 0 <= a <= 3 for a in ids):
         raise ValueError(f"{name} must be a mask 0..15 or an iterable of agent ids 0..3")
     return sum(1 << a for a in set(ids))
+
+
+def _compact_views(viewers, centred):
+    """observe()'s, step_mixed()'s and step_events()'s `viewers` / `centred`: None for the four-view form (neither given), else the
+    PomCompactViewSpec's (viewer_mask, flags) — `viewers` a mask int or an iterable of agent ids as `agents=` is elsewhere, not empty;
+    None with `centred`: all four"""
+    if viewers is None and not centred:
+        return None
+    mask = 15 if viewers is None else _agent_mask(viewers, "viewers")
+    if mask == 0:
+        raise ValueError("viewers names no agent: a compact view has at least one viewer")
+    return mask, VIEW_CENTRED if centred else 0
 
 
 def _rollout_args(horizon, samples, dist, moves, simple, first, fresh_agents, policy: bool = True):
@@ -365,9 +377,9 @@ class BatchEnvironment:
         torch, dev = self._torch_device()
         return torch.empty(shape, dtype=getattr(torch, dtype), device=dev)
 
-    def _new_attrs(self, width: int):
-        """new (agent_attrs or viewer_attrs, env_attrs) for an observation"""
-        return self._new((self.n, 4, width), "int32"), self._new((self.n, 4), "int32")
+    def _new_attrs(self, width: int, rows: int = 4):
+        """new (agent_attrs or viewer_attrs, env_attrs) for an observation (`rows`: the compact views' viewers)"""
+        return self._new((self.n, rows, width), "int32"), self._new((self.n, 4), "int32")
 
     def _out_tensor(self, out, shape, dtype, what: str = "out"):
         """the tensor a call writes its result to: a new one, or the caller's `out` of an earlier call, checked"""
@@ -385,7 +397,7 @@ class BatchEnvironment:
         return res
 
     def _observation(self, codes=None, planes=None, per_agent=None, view_radius=None, viewer_attrs=None, agent_attrs=None,
-                     env_attrs=None, *, raw: bool = False, dtype=None, out=None):
+                     env_attrs=None, *, raw: bool = False, dtype=None, out=None, compact=None):
         """The rules of an observation request (pom_api_observe.h's observe_args and view_args), stated once for observe(),
         step_device_observe(), step_device_range() and expand().  The layout is given as `codes` or `planes` (the element type is the
         tensor's, read by name), or as observe()'s `dtype` name with an optional `out`; with `raw` anything that is no tensor is a
@@ -393,7 +405,9 @@ class BatchEnvironment:
         no torch, no runtime call.  Returns a plain tuple, what every caller needs first (this is on the closed loop's host path, where
         a named tuple costs half a microsecond a call): (the tensor or address the planes go to — None: to be allocated, or no
         observation —, the library's dtype code, per_agent, view: these are the fogged views, the width of agent_attrs (8) or
-        viewer_attrs (12) — int32 [n, 4, width], env_attrs int32 [n, 4] —, the planes' shape, their element type by name)."""
+        viewer_attrs (12) — int32 [n, 4, width], env_attrs int32 [n, 4] —, the planes' shape, their element type by name).
+        `compact` (_compact_views: the viewers' mask and flags): the compact views — codes only, uint8 [n, k, 5, S, S] with S = 11 or,
+        centred, 2 view_radius + 1, and viewer_attrs int32 [n, k, 12]."""
         view = view_radius is not None
         if codes is not None and planes is not None:
             raise ValueError("codes and planes are two forms of one observation: pass one")
@@ -420,10 +434,18 @@ class BatchEnvironment:
             raise ValueError("agent_attrs are written with the plain observation only: the fogged views have viewer_attrs")
         per_agent, depth, width = bool(per_agent) or view, 5 if is_codes else 16, 12 if view else 8
         shape = (self.n, 4, depth, 11, 11) if per_agent else (self.n, depth, 11, 11)
+        viewers = 4
+        if compact is not None:
+            if not view:
+                raise ValueError("viewers and centred choose among the fogged views: pass view_radius")
+            if not is_codes:
+                raise ValueError("viewers and centred are for the codes layout only (the 16-plane views are always four, uncropped)")
+            viewers, side = bin(compact[0]).count("1"), 2 * int(view_radius) + 1 if compact[1] & VIEW_CENTRED else 11
+            shape = (self.n, viewers, depth, side, side)
         if checked:
             self._device_tensor(out, name, dtype, shape)
         if viewer_attrs is not None or agent_attrs is not None or env_attrs is not None:
-            for t, what, want in ((viewer_attrs, "viewer_attrs", (self.n, 4, width)), (agent_attrs, "agent_attrs", (self.n, 4, width)),
+            for t, what, want in ((viewer_attrs, "viewer_attrs", (self.n, viewers, width)), (agent_attrs, "agent_attrs", (self.n, 4, width)),
                                   (env_attrs, "env_attrs", (self.n, 4))):
                 if hasattr(t, "data_ptr"):
                     self._device_tensor(t, what, "int32", want)
@@ -583,19 +605,19 @@ class BatchEnvironment:
             self._call("pom_batch_step_device_range", first, count, ptr, st, _ptr(out), code, int(per_agent), _ptr(agent_attrs), _ptr(env_attrs))
 
     def _mixed_step_spec(self, first, count, moves, simple, seed, tick, stream, codes, planes, view_radius, viewer_attrs, env_attrs, per_agent,
-                         agent_attrs) -> _MixedStepSpec:
+                         agent_attrs, viewers=None, centred=False) -> _MixedStepSpec:
         """step_mixed()'s arguments checked, as the PomMixedStepSpec that step_mixed() and step_events() hand to the library"""
         first, count = self._in_batch(first, count)
-        mask, tick = _agent_mask(simple, "simple"), _bounded(tick, "tick", 0, 0xFFFFFFFF)
+        mask, tick, compact = _agent_mask(simple, "simple"), _bounded(tick, "tick", 0, 0xFFFFFFFF), _compact_views(viewers, centred)
         out, code, per_agent, view, _width, _shape, _dtype = self._observation(codes, planes, per_agent, view_radius, viewer_attrs, agent_attrs,
-                                                                                env_attrs, raw=True)
+                                                                                env_attrs, raw=True, compact=compact)
         if out is None and (per_agent or agent_attrs is not None or env_attrs is not None):
             raise ValueError("view_radius, per_agent, agent_attrs and env_attrs belong to an observation: pass `codes` or `planes`")
         if moves is None and mask != 15:
             raise ValueError("moves is None, but simple leaves agents to it")
         ptr, st = self._moves(moves, raw=True), getattr(stream, "cuda_stream", stream)
         if view:
-            vs = _view_spec(code, view_radius, out, viewer_attrs, env_attrs)
+            vs = _view_spec(code, view_radius, out, viewer_attrs, env_attrs, compact)
             spec = _spec(_MixedStepSpec, mask, first, count, ptr, _u64(seed), tick, st, C.pointer(vs), None, 0, 0, None, None, 0, 0)
         else:
             spec = _spec(_MixedStepSpec, mask, first, count, ptr, _u64(seed), tick, st, None, _ptr(out), code if out is not None else 0,
@@ -604,7 +626,7 @@ class BatchEnvironment:
 
     def step_mixed(self, first: int, count: int, moves, simple, seed: int, tick: int, stream=None, codes=None, planes=None,
                    view_radius: Optional[int] = None, viewer_attrs=None, env_attrs=None, *, per_agent: Optional[bool] = None,
-                   agent_attrs=None) -> None:
+                   agent_attrs=None, viewers=None, centred: bool = False) -> None:
         """step_device_range() with SimpleAgent opponents (pom_batch_step_mixed): one tick for the envs [first, first + count) — whole
         tiles of 16 — as ONE launch on `stream`, in which the agents of `simple` (a mask int 0..15 or an iterable of agent ids) are
         played by SimpleAgent inside the launch — asked as policy_simple(seed) asks them at handle tick `tick` (0..2^32-1), their memory
@@ -613,9 +635,13 @@ class BatchEnvironment:
         `tick`; the handle's tick, its move buffer and the envs outside the range are left alone.  The observation arguments, the
         checks (a ValueError before anything is launched, no runtime call) and the ordering are step_device_range()'s.  The first call
         with a non-empty `simple` on a handle that has run no policy yet allocates the agents' memory and synchronises the handle's
-        stream once: make it — count 0 does only that — before capturing mixed steps into a graph."""
+        stream once: make it — count 0 does only that — before capturing mixed steps into a graph.
+        `viewers` (a mask int or an iterable of agent ids) and `centred`, with `view_radius` and `codes`: the compact views
+        (PomCompactViewSpec) — only those k agents' views, `codes` uint8[n, k, 5, 11, 11], or centred each cropped to its window,
+        uint8[n, k, 5, S, S] with S = 2 view_radius + 1 (fog = off the board), and `viewer_attrs` int32[n, k, 12].  A single learner
+        reads `viewers=[0], centred=True`: a sixth of the four views' bytes, already a dense batch."""
         self._call("pom_batch_step_mixed", C.byref(self._mixed_step_spec(first, count, moves, simple, seed, tick, stream, codes, planes, view_radius,
-                                                                         viewer_attrs, env_attrs, per_agent, agent_attrs)))
+                                                                         viewer_attrs, env_attrs, per_agent, agent_attrs, viewers, centred)))
 
     def _events_tensor(self, t, what: str, dtypes, shape):
         """an array step_events() writes: a device tensor of one of the element types named in `dtypes` and of `shape`, or a raw
@@ -627,7 +653,7 @@ class BatchEnvironment:
 
     def step_events(self, first: int, count: int, moves, simple, seed: int, tick: int, events, outcome=None, wood=None, stream=None,
                     codes=None, planes=None, view_radius: Optional[int] = None, viewer_attrs=None, env_attrs=None, *,
-                    per_agent: Optional[bool] = None, agent_attrs=None) -> None:
+                    per_agent: Optional[bool] = None, agent_attrs=None, viewers=None, centred: bool = False) -> None:
         """step_mixed() that also says what the tick did (pom_batch_step_events; the rule is PomStepEventsSpec's in include/pom_batch.h):
         the same ONE launch on `stream`, everything step_mixed() leaves bit for bit, and for the envs of the range `events` — uint32 or
         int32 [n, 4], one word per agent: the move it played (a SimpleAgent's included), whether it died, moved, laid a bomb, gained a
@@ -637,7 +663,7 @@ class BatchEnvironment:
         cells burnt by this tick).  The arrays are sized for the whole batch and indexed by env, as `moves` is; rows outside the range are
         not touched.  Every other argument, check and ordering rule is step_mixed()'s; no runtime call is made here."""
         spec = self._mixed_step_spec(first, count, moves, simple, seed, tick, stream, codes, planes, view_radius, viewer_attrs, env_attrs,
-                                     per_agent, agent_attrs)
+                                     per_agent, agent_attrs, viewers, centred)
         if events is None:
             raise ValueError("events is None: step_events() writes the event words there (step_mixed() is the call without them)")
         ev = _spec(_StepEventsSpec, 0, self._events_tensor(events, "events", ("uint32", "int32"), (self.n, 4)),
@@ -718,7 +744,7 @@ class BatchEnvironment:
         return self.observe(per_agent=per_agent, dtype=dtype, attrs=attrs, out=out, view_radius=view_radius, _step_moves=moves)
 
     def observe(self, per_agent: Optional[bool] = None, dtype: str = "uint8", attrs: bool = True, out=None,
-                view_radius: Optional[int] = None, _step_moves=None):
+                view_radius: Optional[int] = None, _step_moves=None, *, viewers=None, centred: bool = False):
         """Planes of every env as torch tensors on the handle's device, written by one kernel on the handle's stream
         (pom_batch_observe; plane list in include/pom_batch.h).  Returns (planes, agent_attrs, env_attrs): planes
         [n,16,11,11] or [n,4,16,11,11]; agent_attrs int32 [n,4,8]; env_attrs int32 [n,4] (None, None if attrs=False).
@@ -728,16 +754,23 @@ class BatchEnvironment:
         view_radius (0..10; 4 = Pommerman's 9x9 window): partial observability (pom_batch_observe_view) — every agent's view through
         the window around itself, fog elsewhere.  Returns (planes, viewer_attrs, env_attrs): planes [n,4,16,11,11], all-zero cells
         outside the window, or for "codes" [n,4,5,11,11] with board code 5 (fog) outside it; viewer_attrs int32 [n,4,12] = the
-        viewer's own agent_attrs row, the alive flags of the next three agents, the time step.  per_agent is implied."""
-        out, code, per_agent, view, width, shape, elem = self._observation(per_agent=per_agent, view_radius=view_radius, dtype=dtype, out=out)
+        viewer's own agent_attrs row, the alive flags of the next three agents, the time step.  per_agent is implied.
+        `viewers` (a mask int or an iterable of agent ids) and `centred`, with view_radius and dtype "codes": the compact views
+        (PomCompactViewSpec) — only those k agents' views, planes [n,k,5,11,11], or centred each cropped to its window: [n,k,5,S,S],
+        S = 2 view_radius + 1, byte [dy][dx] the cell (x_v - r + dx, y_v - r + dy), code 5 off the board; viewer_attrs [n,k,12]."""
+        compact = _compact_views(viewers, centred)
+        if compact is not None and _step_moves is not None:
+            raise ValueError("step_device_observe() has no compact views: step_mixed() with simple=0 is the fused call that serves them")
+        out, code, per_agent, view, width, shape, elem = self._observation(per_agent=per_agent, view_radius=view_radius, dtype=dtype, out=out,
+                                                                            compact=compact)
         if out is None:
             out = self._new(shape, elem)
-        a_attrs, e_attrs = self._new_attrs(width) if attrs else (None, None)
+        a_attrs, e_attrs = self._new_attrs(width, shape[1] if compact else 4) if attrs else (None, None)
         step = () if _step_moves is None else (self._moves(_step_moves),)
         name = "pom_batch_observe" if _step_moves is None else "pom_batch_step_device_observe"
         with self._ordered():
             if view:
-                self._call(name + "_view", *step, C.byref(_view_spec(code, view_radius, out, a_attrs, e_attrs)))
+                self._call(name + "_view", *step, C.byref(_view_spec(code, view_radius, out, a_attrs, e_attrs, compact)))
             else:
                 self._call(name, *step, out.data_ptr(), code, int(per_agent), _ptr(a_attrs), _ptr(e_attrs))
         return out, a_attrs, e_attrs

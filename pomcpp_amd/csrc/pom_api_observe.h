@@ -29,7 +29,7 @@ const char* observe_args(const void* planes_dev, int32_t dtype, int32_t per_agen
 
 /* the export kernels' arguments for the whole batch (pom_host.h) */
 ObserveParams observe_params(const PomBatch* h, void* planes_dev, int32_t dtype, int32_t per_agent, int32_t* agent_attrs_dev,
-                             int32_t* env_attrs_dev, int32_t* viewer_attrs_dev, int32_t view_radius)
+                             int32_t* env_attrs_dev, int32_t* viewer_attrs_dev, int32_t view_radius, int32_t view_compact)
 {
     ObserveParams p;
     p.state = h->state;
@@ -43,14 +43,23 @@ ObserveParams observe_params(const PomBatch* h, void* planes_dev, int32_t dtype,
     p.per_agent = per_agent ? 1 : 0;
     p.viewer_attrs = viewer_attrs_dev;
     p.view_radius = view_radius;
+    p.view_compact = view_compact;
     return p;
 }
 
 /* ---- the fogged views (pom_batch.h PomViewSpec): the observation calls with the four agents' windows ---- */
 static_assert(sizeof(PomViewSpec) == POM_VIEW_SPEC_SIZE, "pom_batch.h states the size");
+static_assert(sizeof(PomCompactViewSpec) == POM_COMPACT_VIEW_SPEC_SIZE && offsetof(PomCompactViewSpec, view) == 0, "pom_batch.h states the size; a caller passes &spec.view");
 const char* view_args(const PomViewSpec* s)
 {
-    if (const char* head = SPEC_HEAD(PomViewSpec, s)) return head;
+    if (s && s->struct_size == POM_COMPACT_VIEW_SPEC_SIZE) { /* the ABI grows by struct_size: the compact form's own fields first */
+        const PomCompactViewSpec* c = reinterpret_cast<const PomCompactViewSpec*>(s);
+        if (s->reserved_ != 0) return "reserved_ must be 0";
+        if (c->reserved2_ != 0) return "reserved2_ must be 0";
+        if (c->viewer_mask < 1 || c->viewer_mask > 15) return "viewer_mask must be 1..15";
+        if (c->flags & ~(int32_t)POM_VIEW_CENTRED) return "unknown flags (POM_VIEW_CENTRED is the only one)";
+        if (s->dtype != POM_OBS_CODES) return "the compact views are code planes: dtype must be POM_OBS_CODES";
+    } else if (const char* head = SPEC_HEAD(PomViewSpec, s)) return head;
     if (s->dtype < POM_OBS_U8 || s->dtype > POM_OBS_CODES) return "unknown dtype";
     if (s->view_radius < 0 || s->view_radius > POM_VIEW_RADIUS_MAX) return "view_radius must be 0..10";
     if (!s->planes_dev) return "planes_dev is NULL";
@@ -60,7 +69,9 @@ const char* view_args(const PomViewSpec* s)
 }
 PomObserveOut view_out(const PomViewSpec* s)
 {
-    return PomObserveOut{s->planes_dev, nullptr, s->env_attrs_dev, s->dtype, 1, 1, s->view_radius, s->viewer_attrs_dev};
+    const PomCompactViewSpec* c = reinterpret_cast<const PomCompactViewSpec*>(s);
+    return PomObserveOut{s->planes_dev, nullptr, s->env_attrs_dev, s->dtype, 1, 1, s->view_radius, s->viewer_attrs_dev,
+                         view_is_compact(s) ? obs_compact_word(c->viewer_mask, c->flags) : 0};
 }
 
 extern "C" {
@@ -93,15 +104,19 @@ int pom_batch_step_device_observe(PomBatch* h, const int32_t* moves_dev, void* p
 int pom_batch_observe_view(PomBatch* h, const PomViewSpec* spec)
 {
     if (int rc = begin_call(h, "pom_batch_observe_view", POM_SETTLED, view_args(spec))) return rc; /* (settled: as pom_batch_observe) */
-    const ObserveParams p = observe_params(h, spec->planes_dev, spec->dtype, 1, nullptr, spec->env_attrs_dev, spec->viewer_attrs_dev, spec->view_radius);
-    pom_observe_view_kernel<<<dim3((unsigned)((h->n + 15) / 16)), dim3(64), 0, h->stream>>>(p);
+    const ObserveParams p = observe_params(h, spec->planes_dev, spec->dtype, 1, nullptr, spec->env_attrs_dev, spec->viewer_attrs_dev, spec->view_radius,
+                                           view_out(spec).view_compact);
+    if (view_is_compact(spec)) pom_observe_compact_kernel<<<dim3((unsigned)((h->n + 15) / 16)), dim3(64), 0, h->stream>>>(p);
+    else pom_observe_view_kernel<<<dim3((unsigned)((h->n + 15) / 16)), dim3(64), 0, h->stream>>>(p);
     HIPCHK(hipGetLastError());
     return POM_OK;
 }
 
 int pom_batch_step_device_observe_view(PomBatch* h, const int32_t* moves_dev, const PomViewSpec* spec)
 {
-    if (int rc = begin_call(h, "pom_batch_step_device_observe_view", POM_AS_IS, !moves_dev ? "moves_dev is NULL" : view_args(spec))) return rc;
+    const char* what = !moves_dev ? "moves_dev is NULL" : view_args(spec);
+    if (!what && view_is_compact(spec)) what = POM_COMPACT_VIEW_ELSEWHERE;
+    if (int rc = begin_call(h, "pom_batch_step_device_observe_view", POM_AS_IS, what)) return rc;
     if (!h->quad) { /* the one-lane-per-env shapes have no fused twin: the two launches */
         if (int rc = pom_batch_step_device(h, moves_dev)) return rc;
         return pom_batch_observe_view(h, spec);

@@ -156,6 +156,7 @@ int pom_batch_step_device_range_view(PomBatch* h, int64_t first, int64_t count, 
     if (!spec) return step_range(h, who, first, count, moves_dev, stream, nullptr, 0, 0, nullptr, nullptr); /* NULL: no observation */
     if (int rc = range_args(h, who, first, count, moves_dev)) return rc;
     if (const char* what = view_args(spec)) return refuse(who, "%s", what);
+    if (view_is_compact(spec)) return refuse(who, "%s", POM_COMPACT_VIEW_ELSEWHERE);
     const PomObserveOut obs = view_out(spec);
     return launch_range(h, who, first, count, moves_dev, stream, &obs);
 }

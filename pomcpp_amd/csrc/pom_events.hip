@@ -12,7 +12,7 @@ typedef void (*PomEventsKernel)(MixedStepParams, StepEventsOut);
 extern "C" int pom_batch_step_events(PomBatch* h, const PomMixedStepSpec* s, const PomStepEventsSpec* ev)
 {
     static const char who[] = "pom_batch_step_events";
-    static const PomEventsKernel k[3][4] = POM_MIXED_KERNEL_TABLE(pom_step_events_kernel);
+    static const PomEventsKernel k[4][4] = POM_MIXED_KERNEL_TABLE(pom_step_events_kernel, pom_step_events_compact_kernel);
     PomObserveOut obs;
     if (int rc = mixed_step_args(h, who, s, obs)) return rc;
     const char* what = !ev ? "the events spec is NULL" : SPEC_HEAD(PomStepEventsSpec, ev);
@@ -27,7 +27,7 @@ extern "C" int pom_batch_step_events(PomBatch* h, const PomMixedStepSpec* s, con
     if (int rc = mixed_step_begin(h, who, s, obs, p, launch)) return rc;
     if (!launch) return POM_OK;
     StepEventsOut eo{ev->events_dev, ev->outcome_dev, ev->wood_dev};
-    const void* kernel = reinterpret_cast<const void*>(k[mixed_kernel_row(s->view || s->planes_dev, s->view != nullptr)][mixed_kernel_column(h)]);
+    const void* kernel = reinterpret_cast<const void*>(k[mixed_kernel_row(s)][mixed_kernel_column(h)]);
     void* args[2] = {&p, &eo};
     HIPCHK(hipLaunchKernel(kernel, mixed_step_grid(s), dim3(64), args, 0, s->stream ? (hipStream_t)s->stream : h->stream));
     return POM_OK;

@@ -176,15 +176,25 @@ struct PomObserveOut { /* pom_batch_step_device_observe / _range: where the fuse
      * which write viewer_attrs and ignore agent_attrs / per_agent; the other kernels ignore these */
     int32_t view, view_radius;
     int32_t* viewer_attrs;
+    /* the compact views (PomCompactViewSpec): pom_observe_compact.h's obs_compact_word, 0 for the four-view form.  Only
+     * pom_batch_observe_view and the mixed step's units serve it */
+    int32_t view_compact;
 };
 
 /* what every call with a plain observation asks of its outputs: what is wrong, or nullptr */
 POM_INTERNAL const char* observe_args(const void* planes_dev, int32_t dtype, int32_t per_agent, const int32_t* agent_attrs_dev, const int32_t* env_attrs_dev);
 /* the export kernels' arguments for the whole batch (viewer_attrs / view_radius: the fogged views only) */
 POM_INTERNAL ObserveParams observe_params(const PomBatch* h, void* planes_dev, int32_t dtype, int32_t per_agent, int32_t* agent_attrs_dev,
-                                          int32_t* env_attrs_dev, int32_t* viewer_attrs_dev = nullptr, int32_t view_radius = 0);
-/* the fogged views (pom_batch.h PomViewSpec): what is wrong with the spec, or nullptr; and the outputs it names */
+                                          int32_t* env_attrs_dev, int32_t* viewer_attrs_dev = nullptr, int32_t view_radius = 0,
+                                          int32_t view_compact = 0);
+/* the fogged views (pom_batch.h PomViewSpec, or the PomCompactViewSpec it begins: both sizes pass): what is wrong with the spec, or
+ * nullptr; and the outputs it names */
 POM_INTERNAL const char* view_args(const PomViewSpec* s);
 POM_INTERNAL PomObserveOut view_out(const PomViewSpec* s);
+/* a spec that passed view_args is the longer one */
+inline bool view_is_compact(const PomViewSpec* s) { return s->struct_size == POM_COMPACT_VIEW_SPEC_SIZE; }
+/* what the calls that do not serve the compact form say */
+#define POM_COMPACT_VIEW_ELSEWHERE \
+    "a PomCompactViewSpec is served by pom_batch_observe_view, pom_batch_step_mixed and pom_batch_step_events, not by this call"
 
 #endif /* POM_HOST_H_ */

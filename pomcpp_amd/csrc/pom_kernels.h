@@ -674,6 +674,19 @@ __device__ __forceinline__ void pom_observe_alone(const ObserveParams& p)
 }
 __global__ __launch_bounds__(64) void pom_observe_kernel(ObserveParams p) { pom_observe_alone<false>(p); }
 __global__ __launch_bounds__(64) void pom_observe_view_kernel(ObserveParams p) { pom_observe_alone<true>(p); }
+/* pom_batch_observe_view with a PomCompactViewSpec: the same, with pom_observe_tile_compact as the way out.  A kernel of its own and
+ * not a branch in the one above, which stays what it was */
+__global__ __launch_bounds__(64) void pom_observe_compact_kernel(ObserveParams p)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t tile[POM_REC_DWORDS * 16];
+    __shared__ uint4 stage[obs_stage_vecs(OBS_PASS_ENVS_ALONE)];
+    const int lane = threadIdx.x;
+    const int64_t tile_id = p.block0 + pom_xcd_tile_order(blockIdx.x, gridDim.x);
+    load_tile16_x4(p.state + tile_id * POM_TILE_DWORDS, tile, lane);
+    __builtin_amdgcn_s_waitcnt(0x0F70); /* as pom_observe_alone */
+    asm volatile("" ::: "memory");
+    pom_observe_tile_compact(p, tile, stage, tile_id, lane);
+}
 
 /* every env's first board (episode 0) into its state and snapshot columns, through an LDS tile so that the records leave in
  * the tick's coalesced row groups */

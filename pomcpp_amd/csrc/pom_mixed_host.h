@@ -11,12 +11,14 @@
 
 static_assert(sizeof(PomMixedStepSpec) == POM_MIXED_STEP_SPEC_SIZE, "pom_batch.h states the size");
 
-/* which of the kernel's twelve instantiations a launch runs: [none / plain / views][fresh * 2 + at_end] (as step_kernel's table) */
-#define POM_MIXED_KERNEL_TABLE(K)                                                                                                    \
+/* which of the kernel's sixteen instantiations a launch runs: [none / plain / views / compact views][fresh * 2 + at_end] (as
+ * step_kernel's table); KC: the COMPACT kernel */
+#define POM_MIXED_KERNEL_TABLE(K, KC)                                                                                                 \
     {{K<false, false, false, false>, K<false, true, false, false>, K<true, false, false, false>, K<true, true, false, false>},       \
      {K<false, false, true, false>, K<false, true, true, false>, K<true, false, true, false>, K<true, true, true, false>},           \
-     {K<false, false, true, true>, K<false, true, true, true>, K<true, false, true, true>, K<true, true, true, true>}}
-inline int mixed_kernel_row(bool observe, bool view) { return view ? 2 : observe ? 1 : 0; }
+     {K<false, false, true, true>, K<false, true, true, true>, K<true, false, true, true>, K<true, true, true, true>},               \
+     {KC<false, false>, KC<false, true>, KC<true, false>, KC<true, true>}}
+inline int mixed_kernel_row(const PomMixedStepSpec* s) { return s->view ? (view_is_compact(s->view) ? 3 : 2) : s->planes_dev ? 1 : 0; }
 inline int mixed_kernel_column(const PomBatch* h) { return 2 * (runs_fresh(h) ? 1 : 0) + (runs_at_end(h) ? 1 : 0); }
 
 /* The checks: the spec's own fields first, then the handle and what depends on it.  POM_OK, with the observation's outputs in `obs`, or
@@ -86,6 +88,7 @@ static int mixed_step_begin(PomBatch* h, const char* who, const PomMixedStepSpec
     p.obs_dtype = observe ? obs.dtype : 0;
     p.obs_per_agent = observe ? obs.per_agent : 0;
     p.obs_view_radius = s->view ? obs.view_radius : 0;
+    p.obs_view_compact = s->view ? obs.view_compact : 0;
     launch = true;
     return POM_OK;
 }

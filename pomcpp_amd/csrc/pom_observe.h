@@ -2,7 +2,8 @@
  * pom_observe.h — the observation export of one tile of 16 envs as it lies in LDS (device side only): the planes, the code
  * planes, the four agents' fogged views and the attribute rows (row f4, pom_batch.h pom_batch_observe, PomViewSpec).  Used by the
  * two stand-alone observe kernels, by the OBS / VIEW instantiations of pom_step_kernel (pom_kernels.h) and by the expansion
- * (pom_expand.h); all of them call pom_observe_tile.
+ * (pom_expand.h); all of them call pom_observe_tile.  The compact views (PomCompactViewSpec: chosen viewers, cropped) are a second entry,
+ * pom_observe_tile_compact at the end, used by pom_observe_compact_kernel and the COMPACT kernels of the mixed step (pom_step_mixed.h).
  *
  * A wavefront takes a tile of 16 envs into LDS as the tick does,
  * then env by env: zero a 1936-byte staging area, scatter one byte per cell / bomb (each cell sets exactly one
@@ -15,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pom_batch.h"
+#include "pom_observe_compact.h"
 #include "pom_packed.h"
 #include "pom_step_body.h"
 
@@ -35,7 +37,11 @@ struct ObserveParams {
     /* the fogged views (VIEW instantiations only: pom_batch.h PomViewSpec) */
     int32_t* viewer_attrs;
     int32_t view_radius;
+    /* the compact views (pom_observe_tile_compact only: PomCompactViewSpec): obs_compact_word, 0 for every other export.  It lies
+     * in what was the struct's tail padding: no kernel argument moves */
+    int32_t view_compact;
 };
+static_assert(sizeof(ObserveParams) == 80, "view_compact fills the tail padding");
 
 /* four staged bytes starting at byte offset `b` of the staging area (any alignment): two aligned dwords and a byte funnel */
 __device__ __forceinline__ uint32_t obs_bytes4(const uint32_t* stage_w, int b)
@@ -506,5 +512,57 @@ __device__ __forceinline__ void pom_observe_tile(const ObserveParams& p, const u
             make_int4((int)tile[POM_REC_TIMESTEP * 16 + lane], pom_sext8(m), status, (int)((st >> POM_ST_WINNER_SHIFT) & 7) - 1);
     }
 }
+
+/* The compact views (pom_batch.h PomCompactViewSpec): uint8 [n][k][5][S][S], only the viewers of the mask, cropped to their window
+ * if centred.  The same passes of four envs, staged once.  A pass's output is a dense run of 4 x k x 5 x S^2 bytes that starts on a
+ * dword (e0 is a multiple of 4) and, for a full pass, ends on one: it leaves as dword stores, 64 consecutive ones per round, each
+ * dword gathered byte by byte from the staged planes (pom_observe_compact.h says which byte).  Only the batch's last pass can be
+ * short and end off a dword: its last one to three bytes leave as bytes.  A tile's 16 x k x 5 x S^2 bytes are a multiple of 16, so
+ * no two wavefronts share a dword.  Then viewer_attrs [n][k][12] — the chosen viewers' rows — and env_attrs: the rows
+ * pom_observe_tile<VIEW> ends with, written a second time here (as pom_view_memory.h does: that tail moved into a function changes
+ * the OBS step kernels). */
+__device__ __forceinline__ void pom_observe_tile_compact(const ObserveParams& p, const uint32_t* tile, uint4* stage, int64_t tile_id, int lane)
+{
+    const ObsCompact g = obs_compact_geom(p.view_compact, p.view_radius); /* wave-uniform */
+    const uint8_t* stage_b = reinterpret_cast<const uint8_t*>(stage);
+    for (int q = 0; q < 16 / OBS_CODE_PASS_ENVS; q++) {
+        const int64_t e0 = tile_id * 16 + q * OBS_CODE_PASS_ENVS;
+        if (e0 >= p.n) break;
+        const int64_t left = p.n - e0;
+        pom_observe_stage<true, 1>(tile, stage, q, lane);
+        const auto pos = [tile, q](int ei, int id) { return (int)(tile[(POM_REC_AGENTS + 2 * id) * 16 + q * OBS_CODE_PASS_ENVS + ei] & 0xFFu); };
+        uint8_t* out_b = reinterpret_cast<uint8_t*>(p.planes) + e0 * (int64_t)g.row;
+        uint32_t* out_w = reinterpret_cast<uint32_t*>(out_b);
+        const uint32_t bytes = (uint32_t)(left < OBS_CODE_PASS_ENVS ? left : OBS_CODE_PASS_ENVS) * g.row;
+        POM_NOUNROLL
+        for (uint32_t i = (uint32_t)lane; i < (bytes >> 2); i += 64) out_w[i] = obs_compact_dword(g, i, pos, stage_b);
+        if ((uint32_t)lane < (bytes & 3u)) {
+            const uint32_t b = (bytes & ~3u) + (uint32_t)lane;
+            out_b[b] = (uint8_t)obs_compact_byte(g, obs_compact_at(g, b), pos, stage_b);
+        }
+        obs_lds_order();
+    }
+    const int ec = lane >> 2, id = lane & 3, rank = obs_compact_rank(p.view_compact, id);
+    const int64_t e = tile_id * 16 + ec;
+    if (e < p.n && p.viewer_attrs && rank >= 0) {
+        const uint32_t a0 = tile[(POM_REC_AGENTS + 2 * id) * 16 + ec], a1 = tile[(POM_REC_AGENTS + 2 * id + 1) * 16 + ec];
+        const int bc = ag_bombcount((int)a0), mx = ag_max_bombs((int)a1);
+        int alive[3];
+#pragma unroll
+        for (int k = 1; k < 4; k++) alive[k - 1] = !ag_dead((int)tile[(POM_REC_AGENTS + 2 * ((id + k) & 3)) * 16 + ec]);
+        int4* o = reinterpret_cast<int4*>(p.viewer_attrs + (e * g.k + rank) * POM_OBS_VIEWER_ATTRS);
+        obs_attr_rows(o, a0, a1, bc, mx);
+        o[2] = make_int4(alive[0], alive[1], alive[2], (int)tile[POM_REC_TIMESTEP * 16 + ec]);
+    }
+    if (lane < 16 && tile_id * 16 + lane < p.n && p.env_attrs) {
+        const uint32_t m = pom_rec_meta(tile + lane, 16), st = (pom_rec_meta2(tile + lane, 16) >> 8) & 0xFF;
+        const int status = (int)((st & POM_ST_DONE) ? 1 : 0) | (int)((st & POM_ST_DRAW) ? 2 : 0) | (int)((st & POM_ST_TIMEOUT) ? 4 : 0) |
+                           (int)((st & POM_ST_RESTARTED) ? 8 : 0);
+        reinterpret_cast<int4*>(p.env_attrs)[tile_id * 16 + lane] =
+            make_int4((int)tile[POM_REC_TIMESTEP * 16 + lane], pom_sext8(m), status, (int)((st >> POM_ST_WINNER_SHIFT) & 7) - 1);
+    }
+}
+static_assert(OBS_CV_ENV_BYTES == OBS_CODE_ENV_BYTES && OBS_CV_PASS_ENVS == OBS_CODE_PASS_ENVS && OBS_CV_PLANES == OBS_CODE_PLANES &&
+              OBS_CV_CELLS == POM_CELLS && OBS_CV_N == POM_N, "pom_observe_compact.h restates the staging's sizes");
 
 #endif /* POM_OBSERVE_H_ */

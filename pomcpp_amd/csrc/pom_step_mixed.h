@@ -54,8 +54,13 @@ struct MixedStepParams {
     int32_t* obs_env_attrs;
     int32_t* obs_viewer_attrs;
     int32_t obs_dtype, obs_per_agent, obs_view_radius;
+    /* the COMPACT kernels only (PomCompactViewSpec): ObserveParams' view_compact.  It lies in what was the struct's tail padding: no
+     * kernel argument moves, StepEventsOut behind it included */
+    int32_t obs_view_compact;
 };
+static_assert(sizeof(MixedStepParams) == 176, "obs_view_compact fills the tail padding");
 
+#define POM_STEP_MIXED_COMPACT 0
 template <bool FRESH, bool ATEND, bool OBS, bool VIEW>
 __global__ __launch_bounds__(64, 4) void pom_step_mixed_kernel(MixedStepParams p)
 {
@@ -72,5 +77,27 @@ __global__ __launch_bounds__(64, 4) void pom_step_events_kernel(MixedStepParams 
 #include "pom_step_mixed_body.inc"
 #undef POM_STEP_MIXED_EVENTS
 }
+#undef POM_STEP_MIXED_COMPACT
+
+/* COMPACT: the two kernels once more with the compact views (pom_batch.h PomCompactViewSpec) as their observation — the body's one
+ * other way out, pom_observe_tile_compact.  Kernels of their own, by name: the text of the sixteen above is what it was */
+#define POM_STEP_MIXED_COMPACT 1
+template <bool FRESH, bool ATEND>
+__global__ __launch_bounds__(64, 4) void pom_step_mixed_compact_kernel(MixedStepParams p)
+{
+    constexpr bool OBS = true, VIEW = true;
+#define POM_STEP_MIXED_EVENTS 0
+#include "pom_step_mixed_body.inc"
+#undef POM_STEP_MIXED_EVENTS
+}
+template <bool FRESH, bool ATEND>
+__global__ __launch_bounds__(64, 4) void pom_step_events_compact_kernel(MixedStepParams p, StepEventsOut eo)
+{
+    constexpr bool OBS = true, VIEW = true;
+#define POM_STEP_MIXED_EVENTS 1
+#include "pom_step_mixed_body.inc"
+#undef POM_STEP_MIXED_EVENTS
+}
+#undef POM_STEP_MIXED_COMPACT
 
 #endif /* POM_STEP_MIXED_H_ */

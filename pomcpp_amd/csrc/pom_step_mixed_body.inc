@@ -230,9 +230,15 @@
         /* the observation of what the tick left in the tile, while the record's stores are on their way (they have been read out of LDS
          * into registers; the staging area lies behind the record rows, where the policy's maps were) */
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#if POM_STEP_MIXED_COMPACT
+        const ObserveParams opc{nullptr, p.n, p.n_pad, 0, p.obs_planes, nullptr, p.obs_env_attrs, p.obs_dtype, 1, p.obs_viewer_attrs, p.obs_view_radius,
+                                p.obs_view_compact};
+        pom_observe_tile_compact(opc, tile, reinterpret_cast<uint4*>(tile + POM_REC_DWORDS * EPW), tile_id, lane);
+#else
         const ObserveParams op{nullptr, p.n, p.n_pad, 0, p.obs_planes, p.obs_agent_attrs, p.obs_env_attrs, p.obs_dtype, p.obs_per_agent,
                                VIEW ? p.obs_viewer_attrs : nullptr, VIEW ? p.obs_view_radius : 0};
         pom_observe_tile<OBS_PASS_ENVS_FUSED, VIEW>(op, tile, reinterpret_cast<uint4*>(tile + POM_REC_DWORDS * EPW), tile_id, lane);
+#endif
     }
     if (lane == 0) { /* each wavefront owns its slot; returnless atomics because those are fire-and-forget (pom_step_kernel) */
         unsigned long long* wc = reinterpret_cast<unsigned long long*>(p.wave_counters + tile_id * POM_CNT_N);
