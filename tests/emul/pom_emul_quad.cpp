@@ -100,7 +100,12 @@ struct QuadLaneEnv {
             q->why = why;
             q->why_addr = addr;
             q->why_round = round;
-            if (getenv("POM_EMUL_QUAD_VERBOSE") && why != 1)
+            if (!getenv("POM_EMUL_QUAD_VERBOSE") || why == 1) return;
+            const int c = addr % 10000; /* 10000 + c, 20000 + c: not an address, the counter of cell c (merge(), claims()) */
+            if (addr >= 10000 && c < 124)
+                fprintf(stderr, "quad model: cell counter %d committed %d; lanes counted/cleared: %d/%d %d/%d %d/%d %d/%d\n", c, q->claim_mem[c], q->claim_add[0][c],
+                        q->claim_clear[0], q->claim_add[1][c], q->claim_clear[1], q->claim_add[2][c], q->claim_clear[2], q->claim_add[3][c], q->claim_clear[3]);
+            else if (addr >= 0 && addr < N_ADDR)
                 fprintf(stderr, "quad model: address %d committed %x; lanes kind/value: %d/%x %d/%x %d/%x %d/%x\n", addr, q->mem[addr], q->kind[0][addr],
                         q->ov[0][addr], q->kind[1][addr], q->ov[1][addr], q->kind[2][addr], q->ov[2][addr], q->kind[3][addr], q->ov[3][addr]);
         }

@@ -8,6 +8,7 @@ import re
 import subprocess
 
 from pomcpp_amd import _abi
+from tests import host_build
 from tests.test_cabi import ROOT, _declared_symbols
 
 
@@ -37,12 +38,13 @@ def layout_differences(structures, tmp_path):
     for name, cls in structures.items():
         lines.append(f'printf("{name} %zu\\n", sizeof({name}));')
         lines += [f'printf("{name}.{f} %zu %zu\\n", offsetof({name}, {f}), sizeof((({name}*)0)->{f}));' for f, *_ in cls._fields_]
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src = tmp_path / "layout.c"
     src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "pom_batch.h"\nint main(void) {\n' + "\n".join(lines) + "\nreturn 0; }\n")
-    cc = subprocess.run(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], capture_output=True, text=True)
-    if cc.returncode != 0:   # a field the header lacks
-        return ["the header does not compile against the mirror's field names: " + cc.stderr.strip().splitlines()[0]]
-    c_side = dict(line.split(" ", 1) for line in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines())
+    try:
+        exe = host_build.program(str(src))
+    except subprocess.CalledProcessError as e:   # a field the header lacks
+        return ["the header does not compile against the mirror's field names: " + e.stderr.strip().splitlines()[0]]
+    c_side = dict(line.split(" ", 1) for line in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines())
     mirror = {}
     for name, cls in structures.items():
         mirror[name] = str(C.sizeof(cls))

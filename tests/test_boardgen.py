@@ -4,15 +4,13 @@ pom_batch_generate and fresh boards on auto-reset through the C-ABI, bit-exact a
 play, every kernel shape."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from pomcpp_amd.state import Item, STATE_DTYPE, is_wood
+from tests.host_build import ROOT, shared_lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INC = ["-I" + os.path.join(ROOT, p) for p in ("include", "pomcpp_amd/csrc", "oracle")]
 CORNERS = [0, 10, 120, 110]
 
 
@@ -154,11 +152,7 @@ def test_exact_number_of_flags_before_the_corners(oracle):
 
 
 def test_device_generator_body_matches_oracle(oracle):
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    so = os.path.join(ROOT, "build", "libpom_boardgen_emul.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-fPIC", "-shared", *INC,
-                    "tests/emul/pom_boardgen_emul.cpp", "-o", so], check=True, cwd=ROOT)
-    lib = C.CDLL(so)
+    lib = C.CDLL(shared_lib("tests/emul/pom_boardgen_emul.cpp"))
     lib.pom_emul_boardgen.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p]
     lib.pom_emul_boardgen.restype = None
     rng = np.random.default_rng(8)

@@ -8,7 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.host_build import ROOT, syntax_check
 
 
 def _declared_symbols():
@@ -55,11 +55,9 @@ def test_library_is_a_gfx950_code_object(hip_lib):
 
 
 def test_header_compiles_as_c_and_cpp(tmp_path):
-    src = tmp_path / "t.c"
-    src.write_text('#include "pom_batch.h"\nint main(void){ PomBatchOptions o; o.struct_size = sizeof o; return o.struct_size == 0; }\n')
+    text = '#include "pom_batch.h"\nint main(void){ PomBatchOptions o; o.struct_size = sizeof o; return o.struct_size == 0; }\n'
     for cc, std in (("gcc", "-std=c11"), ("g++", "-std=c++17")):
-        subprocess.run([cc, std, "-x", "c" if cc == "gcc" else "c++", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                        "-c", str(src), "-o", str(tmp_path / "t.o")], check=True)
+        syntax_check(text, tmp_path, cc, std)
 
 
 def test_state_layout_matches_reference_offsets():

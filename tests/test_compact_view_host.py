@@ -3,7 +3,6 @@ states, every expectation written out; the kernel's byte mapping (pomcpp_amd/csr
 (tests/emul/pom_compact_view_emul.cpp) against the checker for every mask, radius and form at batch sizes with every pass length and
 tail; that build as a stand-alone program under the host sanitizers; the struct's layout, its mirror and the wrapper's argument rules."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
@@ -12,16 +11,13 @@ import pytest
 from pomcpp_amd import _abi
 from pomcpp_amd.batch import BatchEnvironment, _CompactViewSpec, _MixedStepSpec, _ViewSpec
 from tests import compact_view_oracle as co
+from tests import host_build
 from tests import view_oracle as vo
 from tests import wrapper_standin as W
 from tests.compact_view_cases import PLACES, hand_states
 from tests.test_observe_view import _case, _ob
 from tests.wrapper_standin import Duck
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "build")
-EMUL_FLAGS = ["-std=c++17", "-Wall", "-Wextra", "-Werror", "-Wno-unknown-pragmas"]
-EMUL_INC = ["-I" + os.path.join(ROOT, p) for p in ("include", "pomcpp_amd/csrc", "tests/emul")]
 EMUL_SRC = "tests/emul/pom_compact_view_emul.cpp"
 RADII = (0, 1, 4, 5, 10)
 I32, U8, N = W.I32, W.U8, W.N
@@ -125,10 +121,7 @@ def test_radius_0_and_radius_10(hand):
 # ---- the kernel's byte mapping, built for the host --------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def emul():
-    os.makedirs(BUILD, exist_ok=True)
-    path = os.path.join(BUILD, "libpom_compact_view_emul.so")
-    subprocess.run(["g++", "-O2", *EMUL_FLAGS, "-shared", "-fPIC", *EMUL_INC, EMUL_SRC, "-o", path], check=True, cwd=ROOT)
-    lib = C.CDLL(path)
+    lib = C.CDLL(host_build.shared_lib(EMUL_SRC))
     lib.pom_emul_compact_views.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pom_emul_compact_views.restype = C.c_int64
     lib.pom_emul_compact_rank.argtypes = [C.c_int32] * 3
@@ -183,11 +176,9 @@ def test_viewer_attrs_rows(emul):
             assert [lib.pom_emul_compact_rank(mask, centred, v) for v in range(4)] == [ids.index(v) if v in ids else -1 for v in range(4)]
 
 
-def test_the_byte_mapping_under_the_host_sanitizers(tmp_path):
+def test_the_byte_mapping_under_the_host_sanitizers():
     """the stand-alone program: the same sweep between guard bytes in exactly-sized heap blocks, under ASan and UBSan"""
-    exe = str(tmp_path / "compact_view_emul")
-    subprocess.run(["g++", "-O1", "-g", *EMUL_FLAGS, "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DPOM_COMPACT_VIEW_EMUL_MAIN",
-                    *EMUL_INC, EMUL_SRC, "-o", exe], check=True, cwd=ROOT)
+    exe = host_build.program(EMUL_SRC, name="pom_compact_view_emul_asan", extra=["-DPOM_COMPACT_VIEW_EMUL_MAIN"], sanitize=True)
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0 and r.stdout.startswith("ok: "), r.stdout + r.stderr
 
@@ -195,14 +186,14 @@ def test_the_byte_mapping_under_the_host_sanitizers(tmp_path):
 # ---- the ABI ----------------------------------------------------------------------------------------------------------------------
 def test_the_structs_layout(tmp_path):
     """size 56, the offsets 40 / 44 / 48, the PomViewSpec first — as gcc sees the header; and the mirror"""
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src = tmp_path / "layout.c"
     src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "pom_batch.h"\n'
                    '_Static_assert(sizeof(PomCompactViewSpec) == POM_COMPACT_VIEW_SPEC_SIZE, "size");\n'
                    'int main(void) { printf("%zu %zu %zu %zu %zu %d %d\\n", sizeof(PomCompactViewSpec), offsetof(PomCompactViewSpec, view),\n'
                    '  offsetof(PomCompactViewSpec, viewer_mask), offsetof(PomCompactViewSpec, flags), offsetof(PomCompactViewSpec, reserved2_),\n'
                    '  (int)POM_VIEW_CENTRED, (int)POM_VIEW_SPEC_SIZE); return 0; }\n')
-    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    assert subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split() == ["56", "0", "40", "44", "48", "1", "40"]
+    exe = host_build.program(str(src))
+    assert subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split() == ["56", "0", "40", "44", "48", "1", "40"]
     assert C.sizeof(_CompactViewSpec) == 56 and _abi.VIEW_CENTRED == 1
     assert [(f, getattr(_CompactViewSpec, f).offset, getattr(_CompactViewSpec, f).size) for f, _ in _CompactViewSpec._fields_] == \
         [("view", 0, 40), ("viewer_mask", 40, 4), ("flags", 44, 4), ("reserved2_", 48, 8)]

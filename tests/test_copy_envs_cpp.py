@@ -4,19 +4,12 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "build")
-LINK = ["-L" + os.path.join(ROOT, "pomcpp_amd"), "-lpom_batch", "-Wl,-rpath," + os.path.join(ROOT, "pomcpp_amd"),
-        "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib", "-lamdhip64", "-pthread"]
+from tests.host_build import POM_BATCH, program
 
 
 @pytest.fixture(scope="module")
 def copy_games_exe(hip_lib):
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, "copy_games")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(ROOT, "include"),
-                    "-I/opt/rocm/include", os.path.join(ROOT, "tests", "cpp", "copy_games.cpp"), "-o", exe] + LINK, check=True)
-    return exe
+    return program("tests/cpp/copy_games.cpp", extra=["-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"], link=POM_BATCH)
 
 
 def test_copy_games_program_builds(copy_games_exe):

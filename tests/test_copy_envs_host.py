@@ -4,13 +4,12 @@ layout written out in numpy."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "build")
+from tests.host_build import ROOT, shared_lib
+
 TILE_DWORDS, REC_DWORDS, BOARD_BYTES = 1280, 80, 124
 
 HARNESS = r"""
@@ -25,14 +24,10 @@ int h_items(void) { return POM_COL_ITEMS; }
 
 
 @pytest.fixture(scope="module")
-def helpers():
-    os.makedirs(BUILD, exist_ok=True)
-    src, lib = os.path.join(BUILD, "copy_helpers.cpp"), os.path.join(BUILD, "libcopy_helpers.so")
-    with open(src, "w") as f:
-        f.write(HARNESS)
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-fPIC", "-shared", "-I" + os.path.join(ROOT, "include"),
-                    "-I" + os.path.join(ROOT, "pomcpp_amd", "csrc"), src, "-o", lib], check=True)
-    h = C.CDLL(lib)
+def helpers(tmp_path_factory):
+    src = tmp_path_factory.mktemp("copy_helpers") / "copy_helpers.cpp"
+    src.write_text(HARNESS)
+    h = C.CDLL(shared_lib(str(src)))
     h.h_col_copy.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     h.h_rec_to_col.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     h.h_col_to_rec.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]

@@ -19,34 +19,22 @@ import numpy as np
 import pytest
 
 from pomcpp_amd.state import STATE_DTYPE
+from tests.host_build import POM_BATCH, ROOT, program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "build")
-EXE = os.path.join(BUILD, "dropin_test")
 REF = "/root/reference"
 REF_OUT = os.path.join(ROOT, "oracle", "_ref")  # binaries built from reference sources live only here (git-ignored)
-LINK = ["-L" + os.path.join(ROOT, "pomcpp_amd"), "-lpom_batch", "-Wl,-rpath," + os.path.join(ROOT, "pomcpp_amd"),
-        "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib", "-lamdhip64", "-pthread"]
-INC = ["-I" + os.path.join(ROOT, "tests", "cpp", "shim"), "-I" + os.path.join(ROOT, "include")]
 
 have_reference = os.path.isdir(os.path.join(REF, "src", "bboard"))
 
 
 @pytest.fixture(scope="module")
 def dropin_exe(hip_lib):
-    os.makedirs(BUILD, exist_ok=True)
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "cpp", "dropin_test.cpp"), "-o", EXE] + LINK, check=True)
-    return EXE
+    return program("tests/cpp/dropin_test.cpp", extra=["-O1"], link=POM_BATCH)
 
 
 @pytest.fixture(scope="module")
 def env_game_exe(hip_lib):
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, "env_game")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror"] + INC +
-                   [os.path.join(ROOT, "tests", "cpp", "env_game.cpp"), "-o", exe] + LINK, check=True)
-    return exe
+    return program("tests/cpp/env_game.cpp", extra=["-O1", "-I" + os.path.join(ROOT, "tests", "cpp", "shim")], link=POM_BATCH)
 
 
 def test_reference_style_code_compiles_against_the_drop_in_header(dropin_exe):
@@ -56,11 +44,7 @@ def test_reference_style_code_compiles_against_the_drop_in_header(dropin_exe):
 def test_reference_general_vectors_on_the_drop_in_fixed_queue(hip_lib):
     """unit_test/bboard/general_test.cpp:8-61 ("[general]": FixedQueue fill / PopElem / RemoveAt with the ring starting at 0, 5, 2)
     against include/pom_bboard.hpp's FixedQueue, the one drop-in agents compile against; pure host code, runs without a GPU"""
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, "general_test")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "cpp", "general_test.cpp"), "-o", exe] + LINK, check=True)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    out = subprocess.run([program("tests/cpp/general_test.cpp", extra=["-O1"], link=POM_BATCH)], capture_output=True, text=True, timeout=60)
     assert out.returncode == 0 and "general ok" in out.stdout, out.stdout + out.stderr
 
 

@@ -3,7 +3,6 @@
 host (tests/emul/pom_deal_emul.cpp) equal the checker byte for byte; dealt States are playable by the reference's rules; the library's and
 the wrapper's refusals; the header's struct; the rule functions under the host sanitizers, as a stand-alone program."""
 import ctypes as C
-import os
 import subprocess
 import sys
 from collections import deque
@@ -16,27 +15,21 @@ import pomcpp_amd as pa
 from pomcpp_amd.batch import BatchEnvironment, _BoardLayout, _DealSpec
 from pomcpp_amd.state import STATE_DTYPE, Item
 from tests import deal_oracle as DO
+from tests import host_build
 from tests import wrapper_standin as W
 from tests.wrapper_standin import Duck
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "build")
 SEED = 20261020
 N_STANDARD = 2000
 # (layout, boards): the standard one; no rigid wall and only the lanes' woods; every wood hides an item and nothing is rejected; crowded, without
 # lanes — an attempt is accepted about one time in three, so that some boards run out of attempts
 CURRICULA = [((0, 12, 0, 4, 0), 600), ((20, 36, 36, 121, 0), 600), ((56, 24, 10, 4, DO.NO_LANES), 2000)]
-EMUL_FLAGS = ["-std=c++17", "-Wall", "-Wextra", "-Werror", "-Wno-unknown-pragmas"]
-EMUL_INC = ["-I" + os.path.join(ROOT, p) for p in ("include", "pomcpp_amd/csrc", "tests/emul")]
 
 
 @pytest.fixture(scope="module")
 def emul():
     """the kernel's rule functions (pomcpp_amd/csrc/pom_deal.h) built for the host: deal(...) as DO.deal_many, refused(states)"""
-    os.makedirs(BUILD, exist_ok=True)
-    path = os.path.join(BUILD, "libpom_deal_emul.so")
-    subprocess.run(["g++", "-O2", *EMUL_FLAGS, "-shared", "-fPIC", *EMUL_INC, "tests/emul/pom_deal_emul.cpp", "-o", path], check=True, cwd=ROOT)
-    lib = C.CDLL(path)
+    lib = C.CDLL(host_build.shared_lib("tests/emul/pom_deal_emul.cpp"))
     lib.pom_emul_deal.argtypes = [C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pom_emul_deal_refused.argtypes = [C.c_int, C.c_void_p]
     lib.pom_emul_deal_layout_bad.argtypes, lib.pom_emul_deal_layout_bad.restype = [C.c_void_p], C.c_char_p
@@ -350,19 +343,14 @@ int use(PomBatch* h, int32_t* games)
 
 @pytest.mark.parametrize("compiler,std", [("gcc", "-std=c99"), ("g++", "-std=c++17")])
 def test_header_compiles_with_the_spec(tmp_path, compiler, std):
-    src = tmp_path / ("spec.c" if compiler == "gcc" else "spec.cpp")
-    src.write_text(SPEC_PROGRAM)
-    subprocess.run([compiler, std, "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), str(src)], check=True)
+    host_build.syntax_check(SPEC_PROGRAM, tmp_path, compiler, std)
     assert C.sizeof(_DealSpec) == 96 and C.sizeof(_BoardLayout) == 20
     assert [(f, getattr(_DealSpec, f).offset) for f in ("layout", "reserved2_", "games_dev", "stream")] == [("layout", 40), ("reserved2_", 60), ("games_dev", 64), ("stream", 88)]
 
 
 # ---- the rule functions under the host sanitizers: a stand-alone program, run as a child process --------------------------------------
-def test_rule_functions_under_the_sanitizers(tmp_path):
-    exe = tmp_path / "pom_deal_emul_asan"
-    # (the sanitizers' runtimes linked into the program itself: nothing about how the process is started matters to them)
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
-                    "-DPOM_DEAL_EMUL_MAIN", *EMUL_FLAGS, *EMUL_INC, "tests/emul/pom_deal_emul.cpp", "-o", str(exe)], check=True, cwd=ROOT)
-    r = subprocess.run([str(exe), "20000"], capture_output=True, text=True)
+def test_rule_functions_under_the_sanitizers():
+    exe = host_build.program("tests/emul/pom_deal_emul.cpp", name="pom_deal_emul_asan", extra=["-DPOM_DEAL_EMUL_MAIN"], sanitize=True)
+    r = subprocess.run([exe, "20000"], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "20000 boards of 4 layouts ok" in r.stdout and "runtime error" not in r.stderr, r.stdout + r.stderr

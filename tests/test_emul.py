@@ -11,23 +11,15 @@ import pytest
 
 import pomcpp_amd as pa
 from pomcpp_amd.state import STATE_DTYPE, Item
+from tests import host_build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "build")
-INC = ["-I" + os.path.join(ROOT, p) for p in ("include", "pomcpp_amd/csrc", "oracle")]
+EMUL = ["tests/emul/pom_emul.cpp", "tests/emul/pom_emul_quad.cpp"]   # the tick body, one lane per env and four
 
 
 @pytest.fixture(scope="module")
 def emul_bins():
-    os.makedirs(BUILD, exist_ok=True)
-    run = lambda *a: subprocess.run(list(a), check=True, cwd=ROOT)
-    run("g++", "-O2", "-std=c++17", "-Wno-unknown-pragmas", "-fPIC", *INC, "-c", "tests/emul/pom_emul.cpp", "-o", "build/pom_emul.o")
-    run("gcc", "-O2", "-std=c11", "-fPIC", *INC, "-c", "oracle/pom_oracle.c", "-o", "build/pom_oracle.o")
-    run("g++", "-O2", "-std=c++17", "-Wno-unknown-pragmas", "-fPIC", "-pthread", *INC, "-c", "tests/emul/pom_emul_quad.cpp", "-o", "build/pom_emul_quad.o")
-    run("g++", "-O2", "-std=c++17", "-Wno-unknown-pragmas", "-pthread", *INC, "tests/emul/emul_fuzz.cpp", "build/pom_emul.o", "build/pom_emul_quad.o",
-        "build/pom_oracle.o", "-o", "build/emul_fuzz")
-    run("g++", "-shared", "-pthread", "-o", "build/libpom_emul.so", "build/pom_emul.o", "build/pom_emul_quad.o")
-    lib = C.CDLL(os.path.join(BUILD, "libpom_emul.so"))
+    host_build.program(["tests/emul/emul_fuzz.cpp", *EMUL, "oracle/pom_oracle.c"], extra=["-pthread"])
+    lib = C.CDLL(host_build.shared_lib(EMUL, extra=["-pthread"]))
     for fn in (lib.pom_emul_step, lib.pom_emul_quad_step, lib.pom_emul_step_one):
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         fn.restype = C.c_uint32
@@ -42,7 +34,7 @@ def _over20(stdout):
 
 @pytest.mark.parametrize("scenario", [0, 1, 2, 3, 4])
 def test_device_tick_body_matches_oracle_under_random_play(emul_bins, scenario):
-    out = subprocess.run([os.path.join(BUILD, "emul_fuzz"), str(scenario), "150000", "5"], capture_output=True, text=True)
+    out = subprocess.run([os.path.join(host_build.BUILD, "emul_fuzz"), str(scenario), "150000", "5"], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout[-3000:]
     assert "0 mismatches" in out.stdout
     if scenario == 4:  # the scenario is there to queue more than 20 flames
@@ -53,7 +45,7 @@ def test_device_tick_body_matches_oracle_under_random_play(emul_bins, scenario):
 def test_quad_tick_body_matches_oracle_under_random_play(emul_bins, scenario):
     """the shipped shape, four lanes per env: states equal the oracle's and the lanes never break what the device assumes of them
     (same cross-lane operation reached by all four, no conflicting writes, replicated registers identical)"""
-    out = subprocess.run([os.path.join(BUILD, "emul_fuzz"), str(scenario), "60000", "11", "quad"], capture_output=True, text=True)
+    out = subprocess.run([os.path.join(host_build.BUILD, "emul_fuzz"), str(scenario), "60000", "11", "quad"], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout[-3000:]
     assert "0 mismatches" in out.stdout and "four lanes per env" in out.stdout
     if scenario == 4:
@@ -130,7 +122,7 @@ def test_device_tick_body_reproduces_every_reference_step_case(emul_bins, oracle
     reach (out-of-order timers, full queues, dependency cycles)"""
     from tests.case_api import HostAPI
     from tests.step_cases import ALL_CASES
-    golden = np.load(os.path.join(ROOT, "tests", "golden", "step_cases.npz"))
+    golden = np.load(os.path.join(host_build.ROOT, "tests", "golden", "step_cases.npz"))
 
     for step_fn in (emul_bins.pom_emul_step, emul_bins.pom_emul_quad_step):  # one lane per env; four (the shipped shape)
         def stepper(state, moves):

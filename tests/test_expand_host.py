@@ -4,15 +4,14 @@ spec's checks answer before the handle is touched, and the checker (tests/expand
 (tests/golden/step_cases.npz): every `__before` with its `__moves` gives `__after`."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from pomcpp_amd.state import STATE_DTYPE
 from tests import expand_oracle as XO
+from tests.host_build import ROOT, syntax_check
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "step_cases.npz")
 
 OFFSETS = dict(struct_size=0, flags=4, first=8, count=16, src_dev=24, moves_dev=32, result_dev=40, planes_dev=48, dtype=56, per_agent=60,
@@ -43,15 +42,12 @@ int use(PomBatch* h, const int64_t* src, const int32_t* moves, uint32_t* out, vo
 
 @pytest.mark.parametrize("compiler,std", [("gcc", "-std=c99"), ("g++", "-std=c++17")])
 def test_header_compiles_with_the_spec(tmp_path, compiler, std):
-    src = tmp_path / ("spec.c" if compiler == "gcc" else "spec.cpp")
-    src.write_text(SPEC_PROGRAM)
-    subprocess.run([compiler, std, "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), str(src)], check=True)
+    syntax_check(SPEC_PROGRAM, tmp_path, compiler, std)
 
 
 def test_cpp_wrapper_has_the_call(tmp_path):
-    src = tmp_path / "wrap.cpp"
-    src.write_text('#include "pom_bboard.hpp"\nvoid use(bboard::BatchEnvironment& b, const PomExpandSpec& s) { b.Expand(s); }\n')
-    subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), str(src)], check=True)
+    syntax_check('#include "pom_bboard.hpp"\nvoid use(bboard::BatchEnvironment& b, const PomExpandSpec& s) { b.Expand(s); }\n',
+                            tmp_path, "g++", "-std=c++17")
 
 
 def test_wrapper_structure_is_the_headers():

@@ -2,8 +2,6 @@
 a copy) equals the compiled reference's answers (tests/golden/forecast.npz, tests/golden/gen_forecast.py) on every case, the
 hand-made cases give the planes written out by hand below, and the header's spec compiles as C and C++ at the size it states."""
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,8 +9,8 @@ import pytest
 from pomcpp_amd.state import STATE_DTYPE
 from tests import forecast_cases as FC
 from tests.forecast_oracle import forecast
+from tests.host_build import ROOT, header_constant, syntax_check
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "forecast.npz")
 
 
@@ -124,11 +122,8 @@ int use(PomBatch* h)
 
 @pytest.mark.parametrize("compiler,std", [("gcc", "-std=c99"), ("g++", "-std=c++17")])
 def test_header_compiles_with_the_spec(tmp_path, compiler, std):
-    src = tmp_path / ("spec.c" if compiler == "gcc" else "spec.cpp")
-    src.write_text(SPEC_PROGRAM)
-    subprocess.run([compiler, std, "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), str(src)], check=True)
-    header = open(os.path.join(ROOT, "include", "pom_batch.h")).read()
-    assert int(re.search(r"POM_FORECAST_SPEC_SIZE = (\d+)", header).group(1)) == 48
+    syntax_check(SPEC_PROGRAM, tmp_path, compiler, std)
+    assert header_constant("POM_FORECAST_SPEC_SIZE") == 48
 
 
 def test_wrapper_structure_is_the_headers():

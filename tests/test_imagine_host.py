@@ -5,7 +5,6 @@ checker's States are playable by the reference's rules; the library's and the wr
 import ctypes as C
 import importlib.util
 import os
-import subprocess
 import sys
 from types import SimpleNamespace
 
@@ -19,11 +18,10 @@ from tests import imagine_cases as IC
 from tests import imagine_oracle as IO
 from tests import view_memory_oracle as VM
 from tests import wrapper_standin as W
+from tests.host_build import ROOT, shared_lib, syntax_check
 from tests.view_oracle import viewer_attrs
 from tests.wrapper_standin import Duck
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "build")
 UNKNOWN = {"sample": IO.SAMPLE, "passage": IO.PASSAGE}
 CASES = IC.cases()
 
@@ -39,12 +37,7 @@ def obs():
 @pytest.fixture(scope="module")
 def emul():
     """the kernel's rule functions (pomcpp_amd/csrc/pom_imagine.h) built for the host: imagine(...) as IO.imagine, refused(states)"""
-    os.makedirs(BUILD, exist_ok=True)
-    inc = ["-I" + os.path.join(ROOT, p) for p in ("include", "pomcpp_amd/csrc")]
-    path = os.path.join(BUILD, "libpom_imagine_emul.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-Wno-unknown-pragmas", "-shared", "-fPIC", *inc,
-                    "tests/emul/pom_imagine_emul.cpp", "-o", path], check=True, cwd=ROOT)
-    lib = C.CDLL(path)
+    lib = C.CDLL(shared_lib("tests/emul/pom_imagine_emul.cpp"))
     lib.pom_emul_imagine.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
     lib.pom_emul_imagine_refused.argtypes = [C.c_int, C.c_void_p]
 
@@ -308,8 +301,6 @@ int use(PomBatch* h, const int32_t* view, const uint8_t* memory, const int32_t* 
 
 @pytest.mark.parametrize("compiler,std", [("gcc", "-std=c99"), ("g++", "-std=c++17")])
 def test_header_compiles_with_the_spec(tmp_path, compiler, std):
-    src = tmp_path / ("spec.c" if compiler == "gcc" else "spec.cpp")
-    src.write_text(SPEC_PROGRAM)
-    subprocess.run([compiler, std, "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), str(src)], check=True)
+    syntax_check(SPEC_PROGRAM, tmp_path, compiler, std)
     assert (pa.batch.IMAGINE_BUILT, pa.batch.IMAGINE_DROPPED_BOMBS, pa.batch.IMAGINE_DROPPED_FLAMES, pa.batch.IMAGINE_NO_ROOM) == \
         (IO.BUILT, IO.DROPPED_BOMBS, IO.DROPPED_FLAMES, IO.NO_ROOM) == (1, 2, 4, 8)

@@ -4,8 +4,6 @@ tests/golden/gen_move_safety.py) on every case, the hand-made cases give the row
 as C and C++ at the size it states, and the kernel's two set functions, compiled for the host, equal the checker's boolean arrays."""
 import ctypes as C
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,11 +12,10 @@ import pomcpp_amd as pa
 from pomcpp_amd.state import STATE_DTYPE
 from tests import forecast_cases as FC
 from tests import move_safety_cases as MC
+from tests.host_build import ROOT, header_constant, shared_lib, syntax_check
 from tests.move_safety_oracle import free_cells, grow, move_safety
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "move_safety.npz")
-BUILD = os.path.join(ROOT, "build")
 
 # What agent 0 of each hand-made case of tests/move_safety_cases.py must get, (death_tick row, escape_tick row), the columns IDLE, UP,
 # DOWN, LEFT, RIGHT, BOMB; reasoned from the reference's rules: UP is y - 1 and a move off the board or into a wall leaves the agent
@@ -120,11 +117,8 @@ int use(PomBatch* h)
 
 @pytest.mark.parametrize("compiler,std", [("gcc", "-std=c99"), ("g++", "-std=c++17")])
 def test_header_compiles_with_the_spec(tmp_path, compiler, std):
-    src = tmp_path / ("spec.c" if compiler == "gcc" else "spec.cpp")
-    src.write_text(SPEC_PROGRAM)
-    subprocess.run([compiler, std, "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), str(src)], check=True)
-    header = open(os.path.join(ROOT, "include", "pom_batch.h")).read()
-    assert int(re.search(r"POM_MOVE_SAFETY_SPEC_SIZE = (\d+)", header).group(1)) == 48
+    syntax_check(SPEC_PROGRAM, tmp_path, compiler, std)
+    assert header_constant("POM_MOVE_SAFETY_SPEC_SIZE") == 48
 
 
 def test_wrapper_structure_is_the_headers():
@@ -137,12 +131,7 @@ def test_wrapper_structure_is_the_headers():
 @pytest.fixture(scope="module")
 def emul():
     """the kernel's two set functions (pomcpp_amd/csrc/pom_move_safety.h) built for the host"""
-    os.makedirs(BUILD, exist_ok=True)
-    inc = ["-I" + os.path.join(ROOT, p) for p in ("include", "pomcpp_amd/csrc")]
-    lib = os.path.join(BUILD, "libpom_move_safety_emul.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wno-unknown-pragmas", "-shared", "-fPIC", *inc, "tests/emul/pom_move_safety_emul.cpp", "-o", lib],
-                   check=True, cwd=ROOT)
-    lib = C.CDLL(lib)
+    lib = C.CDLL(shared_lib("tests/emul/pom_move_safety_emul.cpp"))
     lib.pom_emul_escape_grow.argtypes = [C.c_void_p] * 3
     lib.pom_emul_escape_grow.restype = None
     lib.pom_emul_free_words.argtypes = [C.c_void_p] * 2

@@ -5,7 +5,6 @@ import ctypes as C
 import functools
 import importlib.util
 import os
-import re
 
 import numpy as np
 import pytest
@@ -13,8 +12,8 @@ import pytest
 import pomcpp_amd as pa
 from pomcpp_amd.state import Item, new_states
 from tests import view_oracle as vo
+from tests.host_build import ROOT, header_constant
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KINDS = [("ffa", 0), ("ffa", 57), ("stress", 23)]
 SIZES = [5, 16, 67, 200, 1001]
 RADII = [0, 1, 4, 10]
@@ -141,10 +140,8 @@ def test_symbols_and_spec_size(hip_lib):
     from pomcpp_amd.batch import _ViewSpec
     for name in ("pom_batch_observe_view", "pom_batch_step_device_observe_view", "pom_batch_step_device_range_view"):
         assert hasattr(hip_lib, name), name
-    header = open(os.path.join(ROOT, "include", "pom_batch.h")).read()
-    stated = int(re.search(r"POM_VIEW_SPEC_SIZE = (\d+)", header).group(1))
-    assert stated == C.sizeof(_ViewSpec) == 40
-    assert int(re.search(r"POM_OBS_VIEWER_ATTRS = (\d+)", header).group(1)) == 12
+    assert header_constant("POM_VIEW_SPEC_SIZE") == C.sizeof(_ViewSpec) == 40
+    assert header_constant("POM_OBS_VIEWER_ATTRS") == 12
     assert _ViewSpec.planes_dev.offset == 16 and _ViewSpec.viewer_attrs_dev.offset == 24 and _ViewSpec.env_attrs_dev.offset == 32
 
 

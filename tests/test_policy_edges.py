@@ -8,7 +8,6 @@ GPU: the games replayed through policy_simple + step_policy (moves and memory ev
 tick), in the default 16 x 4 shape and the one-lane shapes, against the fixture."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,12 +15,11 @@ import pytest
 from pomcpp_amd.state import STATE_DTYPE
 from tests.edge_states import BOMBCOUNT_MAX, BOMBCOUNT_MIN, MAXBOMBS_MAX
 from tests.edge_states import uploadable as _uploadable
+from tests.host_build import ROOT, shared_lib
 from tests.policy_edge_states import check_memory
 from tests.test_policy_fixtures import _replay_on_gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIX = os.path.join(ROOT, "tests", "golden", "policy_edges.npz")
-INC = ["-I" + os.path.join(ROOT, p) for p in ("include", "pomcpp_amd/csrc", "oracle")]
 
 
 @pytest.fixture(scope="module")
@@ -166,11 +164,7 @@ def test_oracle_replays_the_games(fx, oracle):
 
 @pytest.fixture(scope="module")
 def policy_emul():
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    so = os.path.join(ROOT, "build", "libpom_policy_emul_edges.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wno-unknown-pragmas", "-fPIC", "-shared", *INC, "tests/emul/pom_policy_emul.cpp",
-                    "-o", so], check=True, cwd=ROOT)
-    lib = C.CDLL(so)
+    lib = C.CDLL(shared_lib("tests/emul/pom_policy_emul.cpp"))
     lib.pom_emul_simple_act.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     lib.pom_emul_simple_act.restype = C.c_int
     return lib

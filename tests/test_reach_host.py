@@ -5,8 +5,6 @@ in all three of the kernel's forms and for every max_dist, and equal the oracle 
 the wrapper's refusals; the header's spec."""
 import ctypes as C
 import os
-import re
-import subprocess
 import sys
 
 import numpy as np
@@ -17,11 +15,10 @@ from pomcpp_amd.batch import BatchEnvironment, _ReachSpec
 from pomcpp_amd.state import STATE_DTYPE, Item
 from tests import reach_cases as RC
 from tests import wrapper_standin as W
+from tests.host_build import ROOT, header_constant, shared_lib, syntax_check
 from tests.wrapper_standin import Duck
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "reach.npz")
-BUILD = os.path.join(ROOT, "build")
 MAX_DISTS = (1, 2, 10, 63, 64, 120)
 
 
@@ -40,12 +37,7 @@ def fill_rmap(oracle):
 @pytest.fixture(scope="module")
 def emul():
     """the kernel's level functions (pomcpp_amd/csrc/pom_reach.h) built for the host"""
-    os.makedirs(BUILD, exist_ok=True)
-    inc = ["-I" + os.path.join(ROOT, p) for p in ("include", "pomcpp_amd/csrc")]
-    path = os.path.join(BUILD, "libpom_reach_emul.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wno-unknown-pragmas", "-shared", "-fPIC", *inc, "tests/emul/pom_reach_emul.cpp", "-o", path],
-                   check=True, cwd=ROOT)
-    lib = C.CDLL(path)
+    lib = C.CDLL(shared_lib("tests/emul/pom_reach_emul.cpp"))
     lib.pom_emul_reach.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
 
     def run(states, max_dist=120, mask=15, dist=True, move=True, fill=0):
@@ -269,9 +261,6 @@ int use(PomBatch* h)
 
 @pytest.mark.parametrize("compiler,std", [("gcc", "-std=c99"), ("g++", "-std=c++17")])
 def test_header_compiles_with_the_spec(tmp_path, compiler, std):
-    src = tmp_path / ("spec.c" if compiler == "gcc" else "spec.cpp")
-    src.write_text(SPEC_PROGRAM)
-    subprocess.run([compiler, std, "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), str(src)], check=True)
-    header = open(os.path.join(ROOT, "include", "pom_batch.h")).read()
-    assert int(re.search(r"POM_REACH_SPEC_SIZE = (\d+)", header).group(1)) == 40
-    assert int(re.search(r"POM_REACH_MAX_DIST = (\d+)", header).group(1)) == 120 == pa.batch.REACH_MAX_DIST
+    syntax_check(SPEC_PROGRAM, tmp_path, compiler, std)
+    assert header_constant("POM_REACH_SPEC_SIZE") == 40
+    assert header_constant("POM_REACH_MAX_DIST") == 120 == pa.batch.REACH_MAX_DIST

@@ -3,8 +3,6 @@ reference's playouts (tests/golden/rollout.npz, tests/golden/gen_rollout.py) on 
 the hand-made entries give the words written out by hand below, the header's spec compiles as C and C++ at the size it states, and
 the wrapper's structure and decoder agree with it."""
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,8 +10,8 @@ import pytest
 from pomcpp_amd.state import STATE_DTYPE
 from tests import rollout_cases as RC
 from tests import rollout_oracle as RO
+from tests.host_build import ROOT, header_constant, syntax_check
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "rollout.npz")
 
 # What the hand-made entries of tests/rollout_cases.py must give in every sample, reasoned from the reference's rules.
@@ -126,11 +124,8 @@ int use(PomBatch* h, uint32_t* out)
 
 @pytest.mark.parametrize("compiler,std", [("gcc", "-std=c99"), ("g++", "-std=c++17")])
 def test_header_compiles_with_the_spec(tmp_path, compiler, std):
-    src = tmp_path / ("spec.c" if compiler == "gcc" else "spec.cpp")
-    src.write_text(SPEC_PROGRAM)
-    subprocess.run([compiler, std, "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), str(src)], check=True)
-    header = open(os.path.join(ROOT, "include", "pom_batch.h")).read()
-    assert int(re.search(r"POM_ROLLOUT_SPEC_SIZE = (\d+)", header).group(1)) == 48
+    syntax_check(SPEC_PROGRAM, tmp_path, compiler, std)
+    assert header_constant("POM_ROLLOUT_SPEC_SIZE") == 48
 
 
 def test_wrapper_structure_is_the_headers():

@@ -4,7 +4,6 @@ header's spec compiles as C and C++ at the size and offsets it states, the wrapp
 the call, and the spec's checks answer before the handle is touched."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,8 +13,8 @@ from tests import forecast_cases as FC
 from tests import rollout_jobs_oracle as JO
 from tests import rollout_oracle as RO
 from tests import rollout_policy_oracle as PO
+from tests.host_build import ROOT, syntax_check
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "rollout_policy.npz")
 
 
@@ -82,15 +81,12 @@ int use(PomBatch* h, const int64_t* src, const int32_t* moves, uint32_t* out)
 
 @pytest.mark.parametrize("compiler,std", [("gcc", "-std=c99"), ("g++", "-std=c++17")])
 def test_header_compiles_with_the_spec(tmp_path, compiler, std):
-    src = tmp_path / ("spec.c" if compiler == "gcc" else "spec.cpp")
-    src.write_text(SPEC_PROGRAM)
-    subprocess.run([compiler, std, "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), str(src)], check=True)
+    syntax_check(SPEC_PROGRAM, tmp_path, compiler, std)
 
 
 def test_cpp_wrapper_has_the_call(tmp_path):
-    src = tmp_path / "wrap.cpp"
-    src.write_text('#include "pom_bboard.hpp"\nvoid use(bboard::BatchEnvironment& b, const PomRolloutJobsSpec& s) { b.RolloutJobs(s); }\n')
-    subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), str(src)], check=True)
+    syntax_check('#include "pom_bboard.hpp"\nvoid use(bboard::BatchEnvironment& b, const PomRolloutJobsSpec& s) { b.RolloutJobs(s); }\n',
+                            tmp_path, "g++", "-std=c++17")
 
 
 def test_wrapper_structure_is_the_headers():

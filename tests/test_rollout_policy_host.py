@@ -3,8 +3,6 @@ equals the compiled reference's playouts (tests/golden/rollout_policy.npz, tests
 SimpleAgents it is the rollout's checker, with four fresh ones it is Oracle.run_simple plus the bookkeeping, the header's spec compiles
 as C and C++ at the size and offsets it states, and the wrapper's structure agrees with it."""
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,8 +12,8 @@ from tests import forecast_cases as FC
 from tests import rollout_oracle as RO
 from tests import rollout_policy_cases as PC
 from tests import rollout_policy_oracle as PO
+from tests.host_build import ROOT, header_constant, syntax_check
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "rollout_policy.npz")
 
 
@@ -131,11 +129,8 @@ int use(PomBatch* h, uint32_t* out, const int32_t* moves)
 
 @pytest.mark.parametrize("compiler,std", [("gcc", "-std=c99"), ("g++", "-std=c++17")])
 def test_header_compiles_with_the_spec(tmp_path, compiler, std):
-    src = tmp_path / ("spec.c" if compiler == "gcc" else "spec.cpp")
-    src.write_text(SPEC_PROGRAM)
-    subprocess.run([compiler, std, "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), str(src)], check=True)
-    header = open(os.path.join(ROOT, "include", "pom_batch.h")).read()
-    assert int(re.search(r"POM_ROLLOUT_POLICY_SPEC_SIZE = (\d+)", header).group(1)) == 56
+    syntax_check(SPEC_PROGRAM, tmp_path, compiler, std)
+    assert header_constant("POM_ROLLOUT_POLICY_SPEC_SIZE") == 56
 
 
 def test_wrapper_structure_is_the_headers():

@@ -2,14 +2,13 @@
 and — second half of this file — against the DEVICE tick body's own preparation functions (PomStepper::prep_positions /
 prep_dependencies of pomcpp_amd/csrc/pom_step_body.h, host build of tests/emul; on the GPU they are pinned through Step)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import pomcpp_amd.state as S
 from pomcpp_amd.state import Move
+from tests.test_emul import emul_bins  # noqa: F401  (the host builds of the device body)
 
 
 def _dest(oracle, s, m):
@@ -88,16 +87,9 @@ def test_dead_agents_are_roots(oracle):  # :154-172
 
 
 # ---- the same vectors through the device tick body's preparation functions (tests/emul/pom_emul.cpp: pom_emul_prep) -------------
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
 @pytest.fixture(scope="module")
-def prep():
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    so = os.path.join(ROOT, "build", "libpom_emul_prep.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wno-unknown-pragmas", "-fPIC", "-shared", "-I" + os.path.join(ROOT, "include"),
-                    "-I" + os.path.join(ROOT, "pomcpp_amd/csrc"), "tests/emul/pom_emul.cpp", "-o", so], check=True, cwd=ROOT)
-    lib = C.CDLL(so)
+def prep(emul_bins):
+    lib = emul_bins
     lib.pom_emul_prep.argtypes = [C.c_void_p] * 6
     lib.pom_emul_prep.restype = C.c_int
 

@@ -5,8 +5,6 @@ which is asserted to exercise every clause of the rule —; the wrapper's refusa
 import ctypes as C
 import importlib.util
 import os
-import re
-import subprocess
 import sys
 
 import numpy as np
@@ -17,10 +15,9 @@ from pomcpp_amd.batch import BatchEnvironment, _MemorySpec
 from tests import view_memory_cases as VC
 from tests import view_memory_oracle as VM
 from tests import wrapper_standin as W
+from tests.host_build import ROOT, header_constant, shared_lib, syntax_check
 from tests.wrapper_standin import Duck
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "build")
 RADII, MASKS = (0, 1, 4, 10), (1, 0b1010, 15)
 
 
@@ -35,12 +32,7 @@ def obs():
 @pytest.fixture(scope="module")
 def emul():
     """the kernel's rule functions (pomcpp_amd/csrc/pom_view_memory.h) built for the host"""
-    os.makedirs(BUILD, exist_ok=True)
-    inc = ["-I" + os.path.join(ROOT, p) for p in ("include", "pomcpp_amd/csrc")]
-    path = os.path.join(BUILD, "libpom_view_memory_emul.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-Wno-unknown-pragmas", "-shared", "-fPIC", *inc,
-                    "tests/emul/pom_view_memory_emul.cpp", "-o", path], check=True, cwd=ROOT)
-    lib = C.CDLL(path)
+    lib = C.CDLL(shared_lib("tests/emul/pom_view_memory_emul.cpp"))
     lib.pom_emul_remember.argtypes = [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6
 
     def run(memory, stamp, codes, agent_attrs, env_attrs, episodes, radius, mask=15):
@@ -265,12 +257,9 @@ int use(PomBatch* h, void* stream)
 
 @pytest.mark.parametrize("compiler,std", [("gcc", "-std=c99"), ("g++", "-std=c++17")])
 def test_header_compiles_with_the_spec(tmp_path, compiler, std):
-    src = tmp_path / ("spec.c" if compiler == "gcc" else "spec.cpp")
-    src.write_text(SPEC_PROGRAM)
-    subprocess.run([compiler, std, "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), str(src)], check=True)
-    header = open(os.path.join(ROOT, "include", "pom_batch.h")).read()
-    assert int(re.search(r"POM_MEMORY_SPEC_SIZE = (\d+)", header).group(1)) == 48 == C.sizeof(_MemorySpec)
-    assert int(re.search(r"POM_MEMORY_PLANES = (\d+)", header).group(1)) == 6 == pa.batch.MEMORY_PLANES == VM.PLANES
+    syntax_check(SPEC_PROGRAM, tmp_path, compiler, std)
+    assert header_constant("POM_MEMORY_SPEC_SIZE") == 48 == C.sizeof(_MemorySpec)
+    assert header_constant("POM_MEMORY_PLANES") == 6 == pa.batch.MEMORY_PLANES == VM.PLANES
 
 
 def test_header_struct_equals_the_ctypes_struct(tmp_path):
